@@ -8,9 +8,14 @@ per-stage features and context already sit in HBM.  N > 1: one process per GPU (
 by view with no data-path collective); the only collective is the final RCCL gather of the
 finished depth / confidence maps to rank 0, which is inside the timed region.
 
-One JSON line on stdout (rank 0).  ``roofline`` is measured live with HIP events around the launches of
-the dominant kernel during the timed steps; ``cpu_baseline`` times the CPU oracle (a restatement that
-is bitwise-equal to the reference's PyTorch CPU path) on this box's host cores, rank 0 / N=1 only.
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and prints the headline
+(``value`` views/s, ``ms_per_step``).  ``--full`` adds everything else the benchmark measures and checks, after the
+timed steps: ``roofline`` (HIP events around the launches of the dominant kernel), the single-stream figure and the
+bitwise check of every timed view against it, per-stage times, the other arithmetics, the secondary paths, and
+``cpu_baseline``, which times the CPU oracle (a restatement that is bitwise-equal to the reference's PyTorch CPU path) on
+the host cores, rank 0 / N=1 only.  ``--dump-outputs DIR`` writes what the last timed step computed (the hot path's 13
+depth maps and its confidence map) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -75,6 +80,25 @@ def path_work(H, W, N, nd):
     return fl, by
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, out, np):
+    """``--dump-outputs``: the arrays a caller of the timed path receives from its last step -> ``path/<name>.npy`` (float32).
+    ``out`` is ``forward_hot``'s result ({"depth": [13 maps], "photometric_confidence": map}).  Should they exceed 64 MB in all,
+    every array is thinned to the same fixed stride over its flattened elements (the same sample on every run)."""
+    arrays = {f"depth_{i:02d}": d for i, d in enumerate(out["depth"])}
+    arrays["photometric_confidence"] = out["photometric_confidence"]
+    total = sum(a.numel() * 4 for a in arrays.values())
+    stride = -(-total // DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        host = a.detach().float().cpu().numpy()
+        if stride > 1:
+            host = host.reshape(-1)[::stride]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(host, dtype=np.float32))
+
+
 def run_cfg5(args, torch, dist, rank, world, dev):
     """BASELINE.json cfg5: every (scan, reference view) of an evaluation set, sharded contiguously over the ranks.
     Inside the timed region, per item (effi_mvs_plus_amd.scan_eval.ScanRunner): the synthetic image and feature pyramid of each image
@@ -126,6 +150,9 @@ def run_cfg5(args, torch, dist, rank, world, dev):
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0 and res is not None:      # the maps of the last item of the set
+            import numpy as np
+            dump_outputs(args.dump_outputs, {"depth": [res["depth"][-1]], "photometric_confidence": res["confidence"][-1]}, np)
         feats = runner.cache
         # a sample of this rank's views again, one at a time, eagerly, from freshly computed pyramids: bitwise the gathered maps?
         n_checked = n_bad = 0
@@ -258,6 +285,11 @@ def main():
     ap.add_argument("--fusion-torch-baseline", action="store_true",
                     help="also time the reference's fusion op sequence on the GPU (element-wise 3x3 algebra instead of the 19 M-batch "
                          "GEMM that faulted in round 1); opt-in, never part of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (roofline, single-stream figure and bitwise "
+                         "check of the timed views, per-stage times, other arithmetics, secondary paths, CPU / PyTorch baselines)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
 
     import numpy as np
@@ -355,22 +387,23 @@ def main():
         torch.cuda.synchronize()
 
     with torch.no_grad():
-        # ---- discovery pass (untimed): which kernel dominates? ------------------------------------
         for i in range(max(1, args.warmup - 1)):
             step(i)
-        prof = ops.KernelProfile()
-        br0 = ops.get_branches()
-        ops.set_branches(False)                   # one stream: per-kernel durations are not inflated by overlap
-        ops.set_profile(prof)
-        step(0)
-        ops.set_profile(None)
-        ops.set_branches(br0)
-        disc = prof.summary()
-        fam_ms = {}
-        for k_, v_ in disc.items():
-            fam_ms[family_of(k_)] = fam_ms.get(family_of(k_), 0.0) + v_["ms"]
-        key = args.profile_key or max(fam_ms, key=lambda k: fam_ms[k])      # the kernel TEMPLATE with the largest share of a view
-        fam_keys = sorted(k_ for k_ in disc if family_of(k_) == key or k_ == key)
+        if args.full:
+            # ---- discovery pass (untimed): which kernel dominates? --------------------------------
+            prof = ops.KernelProfile()
+            br0 = ops.get_branches()
+            ops.set_branches(False)               # one stream: per-kernel durations are not inflated by overlap
+            ops.set_profile(prof)
+            step(0)
+            ops.set_profile(None)
+            ops.set_branches(br0)
+            disc = prof.summary()
+            fam_ms = {}
+            for k_, v_ in disc.items():
+                fam_ms[family_of(k_)] = fam_ms.get(family_of(k_), 0.0) + v_["ms"]
+            key = args.profile_key or max(fam_ms, key=lambda k: fam_ms[k])  # the kernel TEMPLATE with the largest share of a view
+            fam_keys = sorted(k_ for k_ in disc if family_of(k_) == key or k_ == key)
         step(1)                                   # last warm-up step, no instrumentation
         if graphed is not None and args.in_flight > 1:
             # ... and W warm-up steps launched exactly as the timed ones are: slot i's graph on lane i.  A stream's hardware queue
@@ -388,11 +421,12 @@ def main():
             torch.cuda.synchronize()
 
         # ---- timed region: exactly K steps + the final gather ---------------------------------------
-        # eager launches: the dominant kernel's launches are bracketed with HIP events inside the timed region;
+        # --full, eager launches: the dominant kernel's launches are bracketed with HIP events inside the timed region;
         # graph replay has no per-kernel events, there the same K steps are repeated eagerly right after it
-        prof = ops.KernelProfile(keys=fam_keys)
-        if graphed is None:
-            ops.set_profile(prof)
+        if args.full:
+            prof = ops.KernelProfile(keys=fam_keys)
+            if graphed is None:
+                ops.set_profile(prof)
         finals, confs = [], []
         barrier()
         t0 = time.perf_counter()
@@ -425,7 +459,9 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         ops.set_profile(None)
-        if graphed is not None:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out, np)    # the last timed step's outputs, before anything replays its slot again
+        if graphed is not None and args.full:
             br = ops.get_branches()
             ops.set_branches(False)                   # one stream: the bracketed launch runs alone, its duration is its own
             ops.set_profile(prof)
@@ -436,7 +472,7 @@ def main():
             torch.cuda.synchronize()
         # the same K steps strictly one view after the other (a view's latency): linear graphs, one stream, outputs cloned per step
         single_stream = None
-        if graphed is not None and args.in_flight > 1 and rank == 0:
+        if graphed is not None and args.in_flight > 1 and rank == 0 and args.full:
             from effi_mvs_plus_amd.graph import HotPathGraph
             try:
                 sg = HotPathGraph(net, *inputs[0], slots=n_scenes)
@@ -469,7 +505,7 @@ def main():
     # single-stream passes (stage k = its cost volume + regularisation / cross-scale blocks + its three GRU iterations + upsampling;
     # stage 1 also carries the preparation of all stages)
     stage_ms = stage_marks_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():
             br = ops.get_branches()
             ops.set_branches(False)
@@ -501,13 +537,38 @@ def main():
         tmax = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    kinst = prof.summary()                        # per instantiation (profile key) of the bracketed kernel template
-    ksum = {f_: sum(v_[f_] for v_ in kinst.values()) for f_ in ("launches", "ms", "flops", "bytes")}
-
     result = None
     bf16_outputs = None
     if rank == 0:
         views = args.steps * world
+        result = {
+            "metric": "ref-views/sec (cost-volume hot path: warp + cost volume + 3-D regularisation + cascaded GRU refinement)",
+            "value": views / dt, "unit": "views/s", "n_gpus": (dist.get_world_size() if distributed else 1),       # as the process group reports it
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": DTYPE[precision], "data": "synthetic",
+            "config": {"workload": f"{args.workload}: DTU-shaped {W}x{H}, N={N} views (S={N - 1} sources), 3-stage cascade "
+                                   f"ndepths={nd}, GRU iters 3,3,3, seeded-random weights, features of the stock FPN resident in HBM",
+                       "launch": ("hipGraph replay of the captured hot path (" + ("two streams" if graph_branches else "one stream, linear graph")
+                                  + ") on double-buffered static input slots that hold the "
+                                  f"synthetic views; each step replays one slot and clones the outputs it keeps, inside the timed region; "
+                                  f"{max(1, args.in_flight)} independent view(s) in flight, one stream each"
+                                  if graphed is not None else "eager: every kernel enqueued from Python"),
+                       "parallelism": f"view-sharded x{world}, {'RCCL' if args.backend == 'nccl' else 'gloo (rehearsal)'} gather of "
+                                      f"depth+confidence to rank 0 inside the timed region" if world > 1 else "single GPU",
+                       # what 'value' is and is not: views in flight, split-precision products; the other two figures beside it (--full)
+                       "views_in_flight": (max(1, args.in_flight) if graphed is not None else 1),
+                       "single_stream_ms": (single_stream or {}).get("ms_per_view"),
+                       "single_stream_views_per_s": (single_stream or {}).get("value"),
+                       "fp32_strict_views_per_s": None, "fp32_strict_ms_per_view": None,
+                       "arithmetic": precision},
+            "in_flight": (max(1, args.in_flight) if graphed is not None else 1),
+            **({"graph_fallback": graph_fallback} if graph_fallback else {}),
+        }
+    if args.full:
+        kinst = prof.summary()                    # per instantiation (profile key) of the bracketed kernel template
+        ksum = {f_: sum(v_[f_] for v_ in kinst.values()) for f_ in ("launches", "ms", "flops", "bytes")}
+    if rank == 0 and args.full:
         avg_ms = ksum["ms"] / ksum["launches"]
         flops_per_launch = ksum["flops"] / ksum["launches"]
         bytes_per_launch = ksum["bytes"] / ksum["launches"]
@@ -589,28 +650,7 @@ def main():
                                         "note": "sum over ALL kernels of a view of (FETCH_SIZE x calibration + WRITE_SIZE) x launches / views "
                                                 "(tools/pmc_traffic.sh); the excess over the path's algorithmic bytes is what the layer-by-layer "
                                                 "update block writes and reads back"}
-        result = {
-            "metric": "ref-views/sec (cost-volume hot path: warp + cost volume + 3-D regularisation + cascaded GRU refinement)",
-            "value": views / dt, "unit": "views/s", "n_gpus": (dist.get_world_size() if distributed else 1),       # as the process group reports it
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE[precision], "data": "synthetic",
-            "config": {"workload": f"{args.workload}: DTU-shaped {W}x{H}, N={N} views (S={N - 1} sources), 3-stage cascade "
-                                   f"ndepths={nd}, GRU iters 3,3,3, seeded-random weights, features of the stock FPN resident in HBM",
-                       "launch": ("hipGraph replay of the captured hot path (" + ("two streams" if graph_branches else "one stream, linear graph")
-                                  + ") on double-buffered static input slots that hold the "
-                                  f"synthetic views; each step replays one slot and clones the outputs it keeps, inside the timed region; "
-                                  f"{max(1, args.in_flight)} independent view(s) in flight, one stream each"
-                                  if graphed is not None else "eager: every kernel enqueued from Python"),
-                       "parallelism": f"view-sharded x{world}, {'RCCL' if args.backend == 'nccl' else 'gloo (rehearsal)'} gather of "
-                                      f"depth+confidence to rank 0 inside the timed region" if world > 1 else "single GPU",
-                       # what 'value' is and is not: views in flight, split-precision products; the other two figures beside it
-                       "views_in_flight": (max(1, args.in_flight) if graphed is not None else 1),
-                       "single_stream_ms": (single_stream or {}).get("ms_per_view"),
-                       "single_stream_views_per_s": (single_stream or {}).get("value"),
-                       "fp32_strict_views_per_s": None, "fp32_strict_ms_per_view": None,
-                       "arithmetic": precision},
-            "in_flight": (max(1, args.in_flight) if graphed is not None else 1),
+        result.update({
             # one view after the other (a view's latency) next to the headline's views in flight; strict-fp32 figure filled in below
             "value_single_stream": (single_stream or {}).get("value"),
             "ms_per_view_single_stream": (single_stream or {}).get("ms_per_view"),
@@ -622,15 +662,14 @@ def main():
                                              "'ms_per_cost_volume_stage_event_marks' = events at the stage boundaries of eager passes, which "
                                              "also contain the gaps of a host-bound eager launch sequence",
             "ms_per_cost_volume_stage_event_marks": stage_marks_ms,
-            **({"graph_fallback": graph_fallback} if graph_fallback else {}),
             "roofline": roof,
             "kernel_breakdown_ms": {k: round(v["ms"], 4) for k, v in sorted(disc.items(), key=lambda kv: -kv[1]["ms"])},
-        }
+        })
 
     # ---- secondary (rank 0, N = 1, outside the timed region): the same K steps with the other conv arithmetic -- measured the
     # same way as the headline (its own captured graph, K replays + output clones) and, for reference, eagerly -- and the
     # distance between the two modes' final depth maps (normalised by the depth range, as the parity tests do)
-    if rank == 0 and world == 1 and not args.no_other_precision:
+    if rank == 0 and world == 1 and args.full and not args.no_other_precision:
         other = "fp32" if precision != "fp32" else "split"
         with torch.no_grad():
             ref_out = step(0)["depth"][-1].clone()
@@ -726,7 +765,7 @@ def main():
     # ---- secondary (rank 0, N = 1): throughput with several independent views in flight (their graphs on separate streams, the
     # second stream inside each graph enabled): bubbles of one view are filled by kernels of the others.  Not the headline: a
     # view's latency rises to ~in_flight x ms_per_view.
-    if rank == 0 and world == 1 and graphed is not None and args.pipelined > 1 and args.in_flight <= 1 and not args.no_whole_forward:
+    if rank == 0 and world == 1 and args.full and graphed is not None and args.pipelined > 1 and args.in_flight <= 1 and not args.no_whole_forward:
         from effi_mvs_plus_amd.graph import HotPathGraph
         br0 = ops.get_branches()
         ops.set_branches(True)
@@ -769,7 +808,7 @@ def main():
     # ---- secondary (rank 0, N = 1, outside the timed region): the whole forward as the reference's drivers time it
     # (test_dtu_dypcd.py:437-442: images -> 13 depth maps), with the feature pyramid on the HIP kernels (scope row n1)
     # and, for comparison, with the stock PyTorch-ROCm pyramid in front of the same hot path
-    if rank == 0 and world == 1 and not args.no_whole_forward:
+    if rank == 0 and world == 1 and args.full and not args.no_whole_forward:
         imgs, pm_c, dv_c = synth.synth_sample(H, W, N, seed=0)
         imgs = imgs.to(dev)
         pm_d = {k: v.to(dev) for k, v in pm_c.items()}
@@ -807,7 +846,7 @@ def main():
 
     # ---- secondary (rank 0, N = 1): scope row n3, the consumer of the path's depth maps -- dynamic geometric-consistency
     # filter + depth averaging (misc/fusion.py, test_tank.py:466-512) on full-resolution synthetic depth maps
-    if rank == 0 and world == 1 and not args.no_whole_forward:
+    if rank == 0 and world == 1 and args.full and not args.no_whole_forward:
         from oracle import effi_oracle as Of
         Vf = 10
         dmaps, fcams = synth.synth_depth_maps(H, W, Vf + 1, seed=4)
@@ -867,7 +906,7 @@ def main():
 
     # ---- secondary (rank 0, N = 1): scope row n4, the producer of the path's inputs -- decoded 8-bit images resident in HBM ->
     # [N,3,H,W] fp32 planes (/255, bilinear resize as scale_mvs_input does it, HWC -> CHW; datasets/general_eval.py:83-117,189)
-    if rank == 0 and world == 1 and not args.no_whole_forward:
+    if rank == 0 and world == 1 and args.full and not args.no_whole_forward:
         src_h = H + 16                      # DTU: 1200 -> 1184 rows (general_eval.py:104-109); same 16-row difference elsewhere
         raws = [torch.randint(0, 256, (src_h, W, 3), dtype=torch.uint8, device=dev) for _ in range(N)]
         planes = torch.empty(N, 3, H, W, device=dev)
@@ -888,7 +927,7 @@ def main():
 
     # ---- secondary (rank 0, N = 1): scope row n2, first piece -- forward + backward of the stage-1 warp + correlation
     # (effi_mvs_plus_amd.autograd.warp_correlate) against torch autograd through the reference's grid_sample formulation
-    if rank == 0 and world == 1 and not args.no_whole_forward:
+    if rank == 0 and world == 1 and args.full and not args.no_whole_forward:
         from effi_mvs_plus_amd import autograd as A
         from oracle import effi_oracle as Ob
         f0, c0, p0, d0 = inputs[0]
@@ -932,7 +971,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- baselines (rank 0, N = 1 only): bounded samples of the same workload ------------------------
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         from oracle import effi_oracle as O
         f, c, p, d = inputs[0]
         hip_ms = dt / args.steps * 1e3

@@ -84,3 +84,40 @@ def conv_tol(precision, want, rtol, atol, layers=1):
         peak = float(torch.as_tensor(want).abs().max())
         return dict(rtol=rtol, atol=atol + 4e-5 * layers * peak)
     return dict(rtol=rtol, atol=atol)
+
+
+# ---- gradients too large to store in full (tests/golden/make_golden_reference.py, tests/test_oracle_vs_reference.py) ----------
+GRAD_FULL_MAX = 1024          # a gradient with at most this many elements is stored whole
+GRAD_SAMPLE = 512             # elements of a larger one stored at fixed positions
+GRAD_PROJECTIONS = 8          # +-1 projections of the whole tensor stored beside them
+
+
+def grad_sample_index(n, name):
+    """GRAD_SAMPLE fixed positions spread over a flattened tensor of n elements, by integer arithmetic only (the same on every
+    host and library version): a stride coprime with n from an offset derived from the parameter's name."""
+    import math
+    import zlib
+    stride = 7919
+    while math.gcd(stride, n) != 1:
+        stride += 2
+    return (torch.arange(GRAD_SAMPLE, dtype=torch.int64) * stride + zlib.crc32(name.encode()) % n) % n
+
+
+def grad_signs(n):
+    """[GRAD_PROJECTIONS, n] fixed +-1 patterns (an integer hash of position and row), float64."""
+    i = torch.arange(n, dtype=torch.int64)
+    rows = []
+    for j in range(GRAD_PROJECTIONS):
+        h = (i * 2654435761 + (j + 1) * 0x9E3779B1) & 0xFFFFFFFF
+        h = h ^ (h >> 15)
+        h = (h * 0x2C1B3C6D) & 0xFFFFFFFF
+        h = h ^ (h >> 12)
+        rows.append(1.0 - 2.0 * ((h >> 7) & 1).double())
+    return torch.stack(rows)
+
+
+def grad_summary(g):
+    """What is stored of a large gradient beside its sampled elements: [sum |g|, ||g||_2, max |g|] and the +-1 projections,
+    all in float64 over the whole tensor."""
+    f = g.detach().double().reshape(-1)
+    return (torch.stack([f.abs().sum(), f.norm(), f.abs().max()]), grad_signs(f.numel()) @ f)

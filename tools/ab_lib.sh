@@ -2,13 +2,14 @@
 # A/B runs of bench.py with two builds of the library on one box:  tools/ab_lib.sh <tag> <lib a> <lib b>   (each twice)
 tag=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+mkdir -p $R/out
 cd $R
 for rep in 1 2; do
   i=0
   for lib in "$@"; do
     i=$((i+1))
-    out=gpurun_out/ab_${tag}_${i}_$rep.json
-    EFFI_MVS_LIB=$R/$lib timeout -k 10 300 python bench.py --steps 40 --cpu-views 1 --torch-baseline-views 0 --no-whole-forward --no-other-precision > $out 2> ${out%.json}.err || { echo "[$lib] FAILED"; tail -3 ${out%.json}.err; exit 1; }
+    out=out/ab_${tag}_${i}_$rep.json
+    EFFI_MVS_LIB=$R/$lib timeout -k 10 300 python bench.py --full --steps 40 --cpu-views 1 --torch-baseline-views 0 --no-whole-forward --no-other-precision > $out 2> ${out%.json}.err || { echo "[$lib] FAILED"; tail -3 ${out%.json}.err; exit 1; }
     python - "$out" "$lib" <<'PY'
 import json, sys
 r = json.load(open(sys.argv[1])); ss = r.get("single_stream", {}); kb = r["kernel_breakdown_ms"]; po = r.get("parity_vs_oracle", {})

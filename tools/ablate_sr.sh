@@ -1,6 +1,6 @@
 #!/bin/bash
 # Ablation builds of the split-resident 3x3 convolution tile (conv2d_x3.hpp, -DEFFI_ABL=<bits>): one extra library per variant under
-# gpurun_out/abl/ (built HERE, cross-compiled; they travel with the snapshot), then tools/bench_sr.py once per library on the GPU box.
+# out/abl/ (built HERE, cross-compiled; they travel with the snapshot), then tools/bench_sr.py once per library on the GPU box.
 # Usage (build container):  tools/ablate_sr.sh build "1 2 4 8 16 3 24 31"      (GPU box):  tools/ablate_sr.sh run "0 1 2 ..." [stages]
 set -e
 cd "$(dirname "$0")/.."

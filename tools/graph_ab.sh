@@ -1,12 +1,12 @@
 #!/bin/bash
 # usage (GPU box): tools/graph_ab.sh <tag> "<ENV=.. for A>" "<ENV=.. for B>"  -- rocprofv3 kernel trace of linear-graph replays (one view
-# after the other) under two environments; timeline of one replay each -> gpurun_out/<tag>_{a,b}_timeline.txt and a per-kernel diff
+# after the other) under two environments; timeline of one replay each -> out/<tag>_{a,b}_timeline.txt and a per-kernel diff
 tag=$1; ea=$2; eb=$3
-R=$GRAFT_REPO_ROOT; O=$R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd); O=$R/out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for v in a b; do
   e=$ea; [ $v = b ] && e=$eb
-  env $e rocprofv3 --kernel-trace --output-format csv -d $O/${tag}_prof_$v -o p -- python3 $R/bench.py --in-flight 1 --no-cpu-baseline --torch-baseline-views 0 --no-whole-forward --no-other-precision --steps 10 > $O/${tag}_prof_$v.log 2>&1 || exit 1
+  env $e rocprofv3 --kernel-trace --output-format csv -d $O/${tag}_prof_$v -o p -- python3 $R/bench.py --full --in-flight 1 --no-cpu-baseline --torch-baseline-views 0 --no-whole-forward --no-other-precision --steps 10 > $O/${tag}_prof_$v.log 2>&1 || exit 1
   python3 $R/tools/graph_timeline.py $(find $O/${tag}_prof_$v -name "p_kernel_trace.csv" | head -1) 14 > $O/${tag}_${v}_timeline.txt
   rm -rf $O/${tag}_prof_$v
   tail -1 $O/${tag}_${v}_timeline.txt

@@ -1,16 +1,16 @@
 #!/bin/bash
 # A/B runs of the rows-per-wave rule of the split-precision 3x3 convolutions (EFFI_MR4_MIN / EFFI_MR4_NT2_MAX / EFFI_MR2_MIN,
 # csrc/conv2d.hip) on ONE box: headline (3 views in flight) and single-stream ms per view for each setting.
-#   tools/sweep_tiles.sh [workload]      outputs under gpurun_out/tiles_*.json, summary on stdout
+#   tools/sweep_tiles.sh [workload]      outputs under out/tiles_*.json, summary on stdout
 wl=${1:-cfg3}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-O=$R/gpurun_out
+O=$R/out
 mkdir -p $O
 cd $R
 XARGS=""
 run() {
   tag=$1; shift
-  env "$@" python bench.py $XARGS --workload $wl --steps 40 --no-cpu-baseline --torch-baseline-views 0 --no-whole-forward --no-other-precision \
+  env "$@" python bench.py --full $XARGS --workload $wl --steps 40 --no-cpu-baseline --torch-baseline-views 0 --no-whole-forward --no-other-precision \
       > $O/tiles_${wl}_$tag.json 2> $O/tiles_${wl}_$tag.err || { echo "$tag FAILED"; tail -3 $O/tiles_${wl}_$tag.err; return 1; }
   python - <<PY
 import json
