@@ -159,33 +159,37 @@ __global__ void reduce_partials_kernel(const float* __restrict__ partial, int C,
 // shift_partial (with P = 2): the first pass' partial sums [C][ns_in] instead of a finished mean -- every workgroup adds them (in
 // ascending order: all get the same bits) and divides by N itself, which saves the launch that used to do it; workgroup (c, 0) also
 // publishes the mean to mean_out.
+// The sums of the first pass (P = 1) and the mean finished from them are formed in double: with a mean of 10^3 standard deviations
+// an fp32 running sum left the mean 3-4 ulp off, and every xhat of the channel moves with it (grad gamma = sum g' xhat was 1.3e-2 of
+// its peak off fp64 where torch's fp32 BatchNorm is 2e-3).  The centred squares (P = 2) do not cancel and stay fp32.
 template <int P>
 __global__ __launch_bounds__(TPB) void bn_moment_kernel(const float* __restrict__ x, int Bn, int C, long n, const float* __restrict__ shift,
                                                         float* __restrict__ out, float* __restrict__ partial,
                                                         const float* __restrict__ shift_partial = nullptr, int ns_in = 0,
                                                         float* __restrict__ mean_out = nullptr) {
+    using Acc = typename std::conditional<P == 1, double, float>::type;
     const int c = blockIdx.x;
     const long total = (long)Bn * n;
     const long per = (total + gridDim.y - 1) / gridDim.y;
     const long i0 = blockIdx.y * per, i1 = min(total, i0 + per);
     float sh = shift ? shift[c] : 0.0f;
     if (shift_partial) {
-        float m = 0.0f;
-        for (int j = 0; j < ns_in; ++j) m += shift_partial[(long)c * ns_in + j];
-        sh = m / (float)total;
+        double m = 0.0;
+        for (int j = 0; j < ns_in; ++j) m += (double)shift_partial[(long)c * ns_in + j];
+        sh = (float)(m / (double)total);
         if (blockIdx.y == 0 && threadIdx.x == 0) mean_out[c] = sh;
     }
-    float s = 0.0f;
+    Acc s = 0;
     EFFI_FOR_BATCH_RANGE(i0, i1, n, b, r) {
         const float v = x[((long)b * C + c) * n + r] - sh;
-        s += (P == 1) ? v : v * v;
+        s += (P == 1) ? (Acc)v : (Acc)(v * v);
     }
-    __shared__ float red[TPB / 64];
+    __shared__ Acc red[TPB / 64];
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float t = red[0] + red[1] + red[2] + red[3];
+        const float t = (float)(red[0] + red[1] + red[2] + red[3]);
         if (partial) partial[(long)c * gridDim.y + blockIdx.y] = t;
         else out[c] = t;
     }
