@@ -45,6 +45,7 @@ SIGNATURES = {
     "effi_conv3d_k3s1_mfma_f32": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "effi_deconv3d_k3_f32": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "effi_softmax_regress_conf_f32": [_vp, _vp, _l, _l, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
+    "effi_softmax_regress_conf_up_f32": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp],
     "effi_vol_lookup1d_f32": [_vp, _l, _l, _i, _vp, _l, _l, _l, _i, _vp, _vp, _l, _i, _i, _vp, _vp],
     "effi_bilinear_sampler1d_f32": [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _vp],
     "effi_getcost_conv1x1_f32": [_vp, _vp, _i, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _i,
@@ -79,6 +80,7 @@ SIGNATURES = {
     "effi_conv2d_c1k7_relu_bf16x3_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "effi_convex_upsample2x_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "effi_compose_rel_proj_stages_f32": [_vp, _i, _i, _vp, _vp],
+    "effi_cascade_setup_f32": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "effi_split_tanh_relu_stages_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "effi_split_tanh_relu_f32": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_depth_to_inv_f32": [_vp, _vp, _i, _i, _vp, _vp],
@@ -92,6 +94,8 @@ SIGNATURES = {
     "effi_sr_clear_border": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "effi_sr_from_planar_f32": [_vp, _i, _i, _i, _vp, _i, _i, _vp],
     "effi_split_tanh_relu_stages_sr_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "effi_split_tanh_relu_stages_sr_clear_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "effi_depth_head_bf16x3_sr": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "effi_encoder_inputs_bf16x3_sr": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp,
                                       _i, _vp, _vp, _i, _i, _vp],
     "effi_encoder_pair_gen_bf16x3_sr": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp,
@@ -126,7 +130,7 @@ BF16X3_ENTRIES = ("effi_conv2d_k3_bf16x3_pair_f32", "effi_conv2d_k3_bf16x3_f32",
                   "effi_conv3d_k3s1_roll_bf16x3_pair_f32", "effi_csp_gen_roll_bf16x3_pair_f32", "effi_deconv3d_k3s2_bf16x3_f32", "effi_encoder_tail_bf16x3_f32", "effi_conv2d_k3_twice_bf16x3_f32",
                   "effi_conv2d_k5s2_bf16x3_f32", "effi_conv3d_k3s2_bf16x3_f32",
                   "effi_conv2d_k3_bf16x3_sr", "effi_conv2d_k3_bf16x3_pair_sr", "effi_conv2d_k3_k1_bf16x3_sr", "effi_conv2d_k3_k1_up2x_bf16x3_sr",
-                  "effi_encoder_pair_gen_bf16x3_sr", "effi_gru_zr_q_fused_bf16x3_sr")
+                  "effi_encoder_pair_gen_bf16x3_sr", "effi_gru_zr_q_fused_bf16x3_sr", "effi_depth_head_bf16x3_sr")
 for _n in BF16X3_ENTRIES:
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 

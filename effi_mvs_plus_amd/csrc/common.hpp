@@ -146,6 +146,28 @@ __device__ __forceinline__ float effi_depth_to_inv(float depth, float lo, float 
     return (s_ - min_disp) / den;
 }
 
+// Stage-1 hypotheses and the cascade's intervals (models/Effi_MVS_plus.py:413-414,424,464-474; models/module.py:578-583), the work of
+// ONE workgroup: D uniform inverse-depth samples between the ends of the range, inverted, and intervals[0..4] (see
+// effi_stage1_hypotheses_f32).  Shared by stage1_hypotheses_kernel (volume_ops.hip) and cascade_setup_kernel (proj.hip).
+__device__ __forceinline__ void effi_stage1_hypotheses_block(const float* __restrict__ disp_range, int n_range, int D,
+                                                             float* __restrict__ depths, float* __restrict__ intervals) {
+    const float lo = disp_range[0], hi = disp_range[n_range - 1];
+    const float step = (hi - lo) / (float)(D - 1);               // models/module.py:578-583
+    for (int d = threadIdx.x; d < D; d += blockDim.x) {
+        const float s = lo + (float)d * step;
+        depths[d] = 1.0f / s;                                    // models/Effi_MVS_plus.py:473-474
+    }
+    if (threadIdx.x < 3) {
+        const float base = (hi - lo) / (float)n_range;           // models/Effi_MVS_plus.py:424
+        const float ratio = (threadIdx.x == 0) ? 4.0f : (threadIdx.x == 1 ? 2.0f : 1.0f);   // :316
+        intervals[threadIdx.x] = base * ratio;
+    } else if (threadIdx.x == 3) {
+        intervals[3] = 1.0f / hi;                                // depth_min_ (:414)
+    } else if (threadIdx.x == 4) {
+        intervals[4] = 1.0f / lo;                                // depth_max_ (:413)
+    }
+}
+
 // Divisions of the volume look-ups (lookup1d_index, effi_getcost_pixel): a refined reciprocal (v_rcp_f32 + one Newton step, <= 1 ulp) and,
 // for a quotient, one residual step on top -- 3 / 6 instructions instead of the ~11 of the IEEE sequence, correctly rounded except for
 // rare 1-ulp cases of CONTINUOUS functions of the query depth (linear interpolation has no jumps), as the warp kernels' projection

@@ -188,6 +188,40 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_bf16x3_sr)(const void* const* srcs, con
     }
 }
 
+// The depth head in ONE launch (models/update.py:15,21,125-127): effi_conv2d_k3_k1_bf16x3_sr with the nine tap projections of conv2
+// (packing.pack_head_taps) followed by effi_head_update_f32, without the nine tap planes in memory -- a workgroup computes the taps of
+// its output pixels plus a one-pixel ring and sums them through LDS (EFFI_EPI_K1HEAD, conv2d_x3.hpp).  Bitwise the two launches.
+// ``tile``: 2 = 8 x 16 computed pixels per workgroup, 4 = 16 x 16, 8 = 16 x 16 on eight waves.
+extern "C" int EFFI_FN(effi_depth_head_bf16x3_sr)(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                                  const float* bias, int cout1, const void* w2pack_bf16, const float* bias2_taps,
+                                                  const float* bias2, const float* inv_depth, const float* disp_range, int n_range,
+                                                  int h, int w, int hp, int wp, int tile, float* out_inv, float* out_depth,
+                                                  effi_stream_t stream) {
+    if (!w2pack_bf16 || !bias2_taps || !bias2 || !inv_depth || !disp_range || n_range < 2 || !out_inv || !out_depth) return EFFI_ERR_BADARG;
+    if (cout1 < 1 || cout1 > 48) return EFFI_ERR_UNSUPPORTED;
+    Conv2dArgs a;
+    const int rc = fill_sr(a, srcs, src_channels, n_src, wpack_bf16, bias, cout1, h, w, hp, wp);
+    if (rc != EFFI_OK) return rc;
+    a.kgroups = 1;                          // ReLU between conv1 and the tap projections (models/update.py:21)
+    a.hd = 0;
+    a.aux0 = inv_depth;
+    a.aux1 = reinterpret_cast<const float*>(w2pack_bf16);
+    a.disp_range = bias2_taps;
+    a.n_range = 9;
+    a.zeros = bias2;
+    a.out0 = out_inv;
+    a.out1 = out_depth;
+    a.zin = n_range;
+    a.xptr0 = disp_range;
+    hipStream_t st = effi_s(stream);
+    switch ((cout1 + 15) / 16) {
+        case 1: return launch_bf16x3_head<1>(a, tile, st);
+        case 2: return launch_bf16x3_head<2>(a, tile, st);
+        case 3: return launch_bf16x3_head<3>(a, tile, st);
+        default: return EFFI_ERR_UNSUPPORTED;
+    }
+}
+
 extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_sr)(const void* const* srcs, const int* src_channels, int n_src,
                                                          const void* wpack_bf16, const float* bias, int cout1, const void* w2pack_bf16,
                                                          const float* bias2, const float* inv_depth, const float* disp_range,

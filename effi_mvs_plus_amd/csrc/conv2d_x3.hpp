@@ -267,6 +267,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 //     4-way instead of 2-way conflicted, ~0.5k LDS cycles per tile, against ~150 address instructions per wave).
 #define EFFI_EPI_K1 6        // internal: the 3x3 result (+ extra channels) goes through a fused 1x1 convolution (see below)
 #define EFFI_EPI_K1UP 8      // internal: K1 producing the 36-channel convex-upsampling mask, consumed in registers (see below)
+#define EFFI_EPI_K1HEAD 7    // internal: K1 producing the depth head's nine tap projections, summed over 3x3 through LDS (see below)
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -316,7 +317,11 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
     static_assert(SR || NITEMS <= 256, "one staging item per thread");
     static_assert(!(SR && ZB), "split-resident maps are 2-D");
     static_assert(EPI != EFFI_EPI_HEAD && EPI != EFFI_EPI_ADD_UP2, "epilogue not instantiated for the split-precision kernel");
-    static_assert((EPI != EFFI_EPI_K1 && EPI != EFFI_EPI_K1UP) || !ZB, "the fused 1x1 epilogue is 2-D only");
+    static_assert((EPI != EFFI_EPI_K1 && EPI != EFFI_EPI_K1UP && EPI != EFFI_EPI_K1HEAD) || !ZB, "the fused 1x1 epilogue is 2-D only");
+    // K1HEAD: the workgroup's TR x TW pixels are its (TR - 2) x (TW - 2) OUTPUT pixels plus a one-pixel ring (tiles overlap by two
+    // rows / columns), so the image it stages reaches two pixels beyond its outputs
+    constexpr bool kHead = EPI == EFFI_EPI_K1HEAD;
+    static_assert(!kHead || (SR && !WIDE && !GEN), "the one-launch depth head reads split-resident maps on 16-column tiles");
     __shared__ __attribute__((aligned(16))) unsigned short lds_ah[SR ? NUA * NTHR * 8 : APIX * CCH];
     __shared__ __attribute__((aligned(16))) unsigned short lds_al[SR ? 8 : APIX * CCH];
     __shared__ __attribute__((aligned(16))) unsigned short lds_b[NB4 * NTHR * 8];
@@ -332,7 +337,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
     const int tile = effi_xcd_remap(bid, nbid);
     if (tile >= ntiles) return;
     const int ty_ = tile / tiles_x;
-    const int x0 = (tile - ty_ * tiles_x) * TW, y0 = ty_ * TR;
+    const int x0 = kHead ? (tile - ty_ * tiles_x) * (TW - 2) - 1 : (tile - ty_ * tiles_x) * TW, y0 = kHead ? ty_ * (TR - 2) - 1 : ty_ * TR;
     const int zpl = ZB ? bidy : 0;
 
     // staging item of this thread
@@ -359,7 +364,10 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
             const int part = u / (2 * APIXP), r_ = u - part * (2 * APIXP);
             const int oct = r_ / APIXP, p = r_ - oct * APIXP;
             const int row = p / AW, col = p - row * AW;
-            const bool valid = (part < NPART) & (p < APIX);
+            bool valid = (part < NPART) & (p < APIX);
+            // K1HEAD: the ring's own halo leaves the map's one-pixel border (and, past the last tile, the plane): those units only
+            // feed ring pixels outside the map, whose taps are never summed -- any readable unit will do
+            if (kHead) valid &= (y0 + row >= 0) & (y0 + row < a.sr_hp) & (x0 + col >= 0) & (x0 + col < a.sr_wp);
             goff[j] = valid ? ((oct * 2 + part) * a.sr_hp + (y0 + row)) * a.sr_wp + (x0 + col) : 0;
         }
     }
@@ -613,7 +621,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
     // here, unconditionally from clamped addresses, instead of element by element behind bounds branches after the K loop (as the
     // compiler laid that out: 16 single-dword loads in 8 dependent round trips per wave, profiles/r04_e_ablate_sr.txt: 10-13 us of a
     // 21-32 us launch).  Same values: bitwise.
-    constexpr bool kK1 = (EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP) && !(EFFI_ABL & 24) && EFFI_EPI_BATCH != 0;
+    constexpr bool kK1 = (EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP || kHead) && !(EFFI_ABL & 24) && EFFI_EPI_BATCH != 0;
     f32x4 kb[kK1 ? NT : 1], kex[kK1 ? MR : 1];
     if constexpr (kK1) {
 #pragma unroll
@@ -750,7 +758,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
         }
         return;
     }
-    if (EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP) {
+    if (EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP || kHead) {
         // Fused 1x1 convolution (convd -> convc of the encoder, models/update.py:78-80,93-96): the 3x3 result of a lane
         // -- channels 4*lk..4*lk+3 of pixel li, per N-tile -- is exactly the B fragment of v_mfma_f32_16x16x16_bf16 (K = 16
         // channels), so out2[co2][px] = sum_k W2[co2][k] * cat(conv3x3 + b1, extra)[k][px] needs no data movement: one K = 16 step
@@ -771,7 +779,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
         for (int m = 0; m < MR; ++m) {
             const int x = x0 + li + (WIDE ? 16 * m : 0);
             const int y = y0 + (WIDE ? wv : wv * MR + m);
-            inside[m] = (y < h) & (x < w);
+            inside[m] = (y < h) & (x < w) & (!kHead || ((y >= 0) & (x >= 0)));
             pixm[m] = inside[m] ? (long)y * w + x : 0;
             if constexpr (kK1) {
                 ex[m] = kex[m];
@@ -877,6 +885,70 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
             }
             return;
         }
+        if constexpr (kHead) {
+            // Depth head in one launch (models/update.py:15,21,125-127): conv2 has ONE output channel, so it is the nine tap projections
+            // s_tap[q] of the hidden map (rows 0..8 of the 1x1 convolution, exactly as the K1 form below computes and stores them) summed
+            // over the 3x3 neighbourhood.  The taps of the workgroup's pixels -- outputs + ring -- go to LDS (over the A image, which
+            // every wave has finished reading at the barrier) instead of nine planes in memory, and each interior lane then does what
+            // head_update_kernel (volume_ops.hip) does for its pixel, operation for operation: sum from 0.0f, ky outer, kx inner, rows
+            // outside the map skipped, columns outside the map adding 0.0f; + bias2, tanhf, + inv, effi_inv_to_depth.
+            // Fields: aux0 = inverse depth [h][w], zeros = conv2's bias (one float), xptr0 / zin = the hypotheses' range, out0 / out1 =
+            // new inverse depth / depth.
+            constexpr int TPIX = TR * TW;
+            static_assert(9 * TPIX * 4 <= (int)sizeof(lds_ah), "the tap planes fit the A image");
+            float* taps = reinterpret_cast<float*>(lds_ah);
+            bf16x4 wh[NT + 1], wl[NT + 1];
+#pragma unroll
+            for (int n = 0; n <= NT; ++n) {
+                const long f = ((long)n * 2) * 64 + lane;
+                wh[n] = *reinterpret_cast<const bf16x4*>(w2 + f * 4);
+                wl[n] = *reinterpret_cast<const bf16x4*>(w2 + (f + 64) * 4);
+            }
+            float b2[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) b2[r] = a.disp_range[4 * lk + r];
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int n = 0; n <= NT; ++n) {
+                    o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wh[n], xh[m][n], o, 0, 0, 0);
+                    if (!kHiOnly) {
+                        o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wl[n], xh[m][n], o, 0, 0, 0);
+                        o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wh[n], xl[m][n], o, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (4 * lk + r < 9) taps[(4 * lk + r) * TPIX + (wv * MR + m) * TW + li] = o[r] + b2[r];
+            }
+            __syncthreads();
+            const float b = a.zeros[0], lo = a.xptr0[0], hi = a.xptr0[a.zin - 1];
+            constexpr int IR = TR - 2, IC = TW - 2;
+            for (int p = tid; p < IR * IC; p += NTHR) {
+                const int iy = p / IC, ix = p - iy * IC;
+                const int y = y0 + 1 + iy, x = x0 + 1 + ix;                // >= 0
+                if (y >= h || x >= w) continue;
+                float s = 0.0f;
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+                    const int yy = y + ky - 1;
+                    if (yy < 0 || yy >= h) continue;
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int xx = x + kx - 1;
+                        const float t_ = taps[(ky * 3 + kx) * TPIX + (iy + ky) * TW + ix + kx];
+                        s = s + ((xx >= 0 && xx < w) ? t_ : 0.0f);
+                    }
+                }
+                const long pix = (long)y * w + x;
+                const float o = a.aux0[pix] + tanhf(s + b);
+                a.out0[pix] = o;
+                a.out1[pix] = effi_inv_to_depth(o, lo, hi);
+            }
+            return;
+        }
         for (int t = 0; t < nt2; ++t) {
             bf16x4 wh[NT + 1], wl[NT + 1];
 #pragma unroll
@@ -978,7 +1050,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
         const long pix = (long)y * w + x;
 #pragma unroll
         for (int n = 0; n < NT; ++n)
-            conv_epilogue_store_t<((EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP) ? EFFI_EPI_PLAIN : EPI), SR>(a, acc[m][n], n * 16 + 4 * lk, pix, hw, zpl, y, x,
+            conv_epilogue_store_t<((EPI == EFFI_EPI_K1 || EPI == EFFI_EPI_K1UP || EPI == EFFI_EPI_K1HEAD) ? EFFI_EPI_PLAIN : EPI), SR>(a, acc[m][n], n * 16 + 4 * lk, pix, hw, zpl, y, x,
                                                                                                           kBiasQ ? &gb[n] : nullptr);
     }
 }
@@ -1071,6 +1143,20 @@ static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
     if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 4, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
     else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
     else hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 1, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+// One-launch depth head (EFFI_EPI_K1HEAD, split-resident input): workgroups of ``tile`` = 2 (8 x 16 pixels, four waves), 4 (16 x 16,
+// four waves) or 8 (16 x 16, eight waves) computed pixels, of which the interior (rows - 2) x 14 are outputs.
+template <int NT>
+static int launch_bf16x3_head(const Conv2dArgs& a, int tile, hipStream_t st) {
+    const int tr = tile == 2 ? 8 : 16;
+    const int tiles_x = effi_cdiv(a.w, 14), ntiles = tiles_x * effi_cdiv(a.h, tr - 2);
+    const dim3 grid(ntiles, 1);
+    if (tile == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EFFI_EPI_K1HEAD, false, false, true, 4>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
+    else if (tile == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 4, EFFI_EPI_K1HEAD, false, false, true, 4>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
+    else if (tile == 8) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EFFI_EPI_K1HEAD, false, false, true, 8>), grid, dim3(512), 0, st, a, tiles_x, ntiles);
+    else return EFFI_ERR_BADARG;
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 

@@ -79,18 +79,29 @@ __global__ void compose_rel_proj_kernel(const float* __restrict__ pairs, int n_v
 
 // all stages of the cascade in one launch: blockIdx.x = stage
 struct PairList { const float* p[4]; };
-__global__ void compose_rel_proj_stages_kernel(PairList pl, int n_views, float* __restrict__ rt_all) {
+__device__ __forceinline__ void compose_rel_proj_stage(const PairList& pl, int stage, int n_views, float* __restrict__ rt_all) {
     const int v = threadIdx.x;
     if (v >= n_views - 1) return;
     const float* pairs = pl.p[0];
 #pragma unroll
     for (int j = 1; j < 4; ++j)
-        if ((int)blockIdx.x == j) pairs = pl.p[j];
+        if (stage == j) pairs = pl.p[j];
     double R[4][4], Rinv[4][4], S[4][4];
     compose_k_rt(pairs, R);
     invert4x4(R, Rinv);
     compose_k_rt(pairs + (long)(v + 1) * 32, S);
-    write_rt(S, Rinv, rt_all + ((long)blockIdx.x * (n_views - 1) + v) * 12);
+    write_rt(S, Rinv, rt_all + ((long)stage * (n_views - 1) + v) * 12);
+}
+__global__ void compose_rel_proj_stages_kernel(PairList pl, int n_views, float* __restrict__ rt_all) {
+    compose_rel_proj_stage(pl, (int)blockIdx.x, n_views, rt_all);
+}
+
+// The cascade's two set-up steps in one launch: block 0 = stage1_hypotheses_kernel (volume_ops.hip), block 1 + s =
+// compose_rel_proj_stages_kernel's block s.  Each reads a few hundred bytes; as two launches they cost two launch latencies.
+__global__ void cascade_setup_kernel(const float* __restrict__ disp_range, int n_range, int D, float* __restrict__ depths,
+                                     float* __restrict__ intervals, PairList pl, int n_views, float* __restrict__ rt_all) {
+    if (blockIdx.x == 0) effi_stage1_hypotheses_block(disp_range, n_range, D, depths, intervals);
+    else compose_rel_proj_stage(pl, (int)blockIdx.x - 1, n_views, rt_all);
 }
 
 __global__ void rel_proj_kernel(const float* __restrict__ src, const float* __restrict__ ref, float* __restrict__ rt) {
@@ -120,6 +131,21 @@ extern "C" int effi_compose_rel_proj_stages_f32(const float* const* pairs, int n
         if (!pl.p[k]) return EFFI_ERR_BADARG;
     }
     hipLaunchKernelGGL(compose_rel_proj_stages_kernel, dim3(n_stages), dim3(64), 0, effi_s(stream), pl, n_views, rt_out);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_cascade_setup_f32(const float* disp_range, int n_range, int D, float* depths, float* intervals,
+                                      const float* const* pairs, int n_stages, int n_views, float* rt_out, effi_stream_t stream) {
+    if (!disp_range || !depths || !intervals || n_range < 2 || D < 2) return EFFI_ERR_BADARG;
+    if (!pairs || !rt_out || n_stages < 1 || n_stages > 4 || n_views < 2 || n_views > EFFI_MAX_VIEWS + 1) return EFFI_ERR_BADARG;
+    PairList pl;
+    for (int k = 0; k < 4; ++k) {
+        pl.p[k] = pairs[k < n_stages ? k : 0];
+        if (!pl.p[k]) return EFFI_ERR_BADARG;
+    }
+    hipLaunchKernelGGL(cascade_setup_kernel, dim3(1 + n_stages), dim3(128), 0, effi_s(stream), disp_range, n_range, D, depths, intervals, pl,
+                       n_views, rt_out);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }

@@ -106,21 +106,7 @@ __global__ void depth_to_inv_kernel(const float* __restrict__ depth, const float
 
 __global__ void stage1_hypotheses_kernel(const float* __restrict__ disp_range, int n_range, int D,
                                          float* __restrict__ depths, float* __restrict__ intervals) {
-    const float lo = disp_range[0], hi = disp_range[n_range - 1];
-    const float step = (hi - lo) / (float)(D - 1);               // models/module.py:578-583
-    for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        const float s = lo + (float)d * step;
-        depths[d] = 1.0f / s;                                    // models/Effi_MVS_plus.py:473-474
-    }
-    if (threadIdx.x < 3) {
-        const float base = (hi - lo) / (float)n_range;           // models/Effi_MVS_plus.py:424
-        const float ratio = (threadIdx.x == 0) ? 4.0f : (threadIdx.x == 1 ? 2.0f : 1.0f);   // :316
-        intervals[threadIdx.x] = base * ratio;
-    } else if (threadIdx.x == 3) {
-        intervals[3] = 1.0f / hi;                                // depth_min_ (:414)
-    } else if (threadIdx.x == 4) {
-        intervals[4] = 1.0f / lo;                                // depth_max_ (:413)
-    }
+    effi_stage1_hypotheses_block(disp_range, n_range, D, depths, intervals);
 }
 
 __global__ void upsample_nearest_kernel(const float* __restrict__ in, int C, int h, int w, int f,
@@ -221,10 +207,26 @@ __global__ void view_aggregate_kernel(const float* __restrict__ sim_views, const
 // ------------------------------------------------------------------------------------------------
 // K7: softmax over D, depth regression, 4-window confidence (models/Effi_MVS_plus.py:79-88)
 // ------------------------------------------------------------------------------------------------
+// the confidence of pixel p = (y, x) of a w-wide map replicated f x f into the [h*f][w*f] map the cascade returns (F.interpolate
+// nearest, models/Effi_MVS_plus.py:479): what upsample_nearest_kernel would copy there from out_conf
+__device__ __forceinline__ void conf_store_up(float* __restrict__ out_up, float conf, int p, int w, int f) {
+    const int y = p / w, x = p - y * w;
+    float* dst = out_up + ((long)y * f) * ((long)w * f) + (long)x * f;
+    if (f == 4) {                                     // 16-byte stores (the entry checks the alignment)
+        const float4 v = make_float4(conf, conf, conf, conf);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<float4*>(dst + (long)j * w * 4) = v;
+        return;
+    }
+    for (int j = 0; j < f; ++j)
+        for (int i = 0; i < f; ++i) dst[(long)j * w * f + i] = conf;
+}
+
 __global__ void softmax_regress_conf_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
                                             long dds, long dps, int D, int hw,
                                             float* __restrict__ out_depth, float* __restrict__ out_conf,
-                                            const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv) {
+                                            const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv,
+                                            float* __restrict__ out_conf_up, int w, int f) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;     // launched with 64-thread blocks
     if (p >= hw) return;
     float m = -INFINITY;
@@ -245,8 +247,10 @@ __global__ void softmax_regress_conf_kernel(const float* __restrict__ logits, co
         s4 = s4 + pr;
     }
     out_depth[p] = dep;
-    out_conf[p] = 4.0f * (s4 / 4.0f);
+    const float conf = 4.0f * (s4 / 4.0f);
+    out_conf[p] = conf;
     if (out_dinv) out_dinv[p] = effi_depth_to_inv(dep, disp_range[0], disp_range[n_range - 1]);   // models/Effi_MVS_plus.py:538
+    if (out_conf_up) conf_store_up(out_conf_up, conf, p, w, f);
 }
 
 // Same arithmetic, same order, for the depth counts the cascade uses: the D logits of a pixel are loaded ONCE into registers
@@ -256,7 +260,8 @@ template <int DT>
 __global__ __launch_bounds__(64) void softmax_regress_conf_reg_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
                                                                       long dds, long dps, int hw, float* __restrict__ out_depth,
                                                                       float* __restrict__ out_conf, const float* __restrict__ disp_range,
-                                                                      int n_range, float* __restrict__ out_dinv) {
+                                                                      int n_range, float* __restrict__ out_dinv,
+                                                                      float* __restrict__ out_conf_up, int w, int f) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= hw) return;
     float e[DT], dv[DT];
@@ -289,8 +294,10 @@ __global__ __launch_bounds__(64) void softmax_regress_conf_reg_kernel(const floa
         s4 = in ? s4 + e[d] : s4;
     }
     out_depth[p] = dep;
-    out_conf[p] = 4.0f * (s4 / 4.0f);
+    const float conf = 4.0f * (s4 / 4.0f);
+    out_conf[p] = conf;
     if (out_dinv) out_dinv[p] = effi_depth_to_inv(dep, disp_range[0], disp_range[n_range - 1]);   // models/Effi_MVS_plus.py:538
+    if (out_conf_up) conf_store_up(out_conf_up, conf, p, w, f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -601,16 +608,18 @@ extern "C" int effi_view_aggregate_f32(const float* sim_views, const float* weig
     return EFFI_OK;
 }
 
-extern "C" int effi_softmax_regress_conf_f32(const float* logits, const float* depth, long dds, long dps, int D,
-                                             int hw, float* out_depth, float* out_conf, const float* disp_range, int n_range,
-                                             float* out_depth_inv, effi_stream_t stream) {
+static int softmax_regress_conf_launch(const float* logits, const float* depth, long dds, long dps, int D, int hw, float* out_depth,
+                                       float* out_conf, const float* disp_range, int n_range, float* out_depth_inv,
+                                       float* out_conf_up, int w, int f, effi_stream_t stream) {
     if (!logits || !depth || !out_depth || !out_conf || D < 1 || hw < 1) return EFFI_ERR_BADARG;
     if (out_depth_inv && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
+    if (out_conf_up && (w < 1 || f < 1 || hw % w != 0)) return EFFI_ERR_BADARG;
+    if (out_conf_up && f == 4 && (reinterpret_cast<uintptr_t>(out_conf_up) & 15)) return EFFI_ERR_BADARG;
     const dim3 grid(effi_cdiv(hw, 64));
     hipStream_t st = effi_s(stream);
 #define EFFI_SM(DT)                                                                                                      \
     hipLaunchKernelGGL(softmax_regress_conf_reg_kernel<DT>, grid, dim3(64), 0, st, logits, depth, dds, dps, hw, out_depth, \
-                       out_conf, disp_range, n_range, out_depth_inv)
+                       out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f)
     switch (D) {
         case 8: EFFI_SM(8); break;
         case 16: EFFI_SM(16); break;
@@ -620,11 +629,26 @@ extern "C" int effi_softmax_regress_conf_f32(const float* logits, const float* d
         case 96: EFFI_SM(96); break;
         default:
             hipLaunchKernelGGL(softmax_regress_conf_kernel, grid, dim3(64), 0, st, logits, depth, dds, dps, D, hw, out_depth, out_conf,
-                               disp_range, n_range, out_depth_inv);
+                               disp_range, n_range, out_depth_inv, out_conf_up, w, f);
     }
 #undef EFFI_SM
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
+}
+
+extern "C" int effi_softmax_regress_conf_f32(const float* logits, const float* depth, long dds, long dps, int D,
+                                             int hw, float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                             float* out_depth_inv, effi_stream_t stream) {
+    return softmax_regress_conf_launch(logits, depth, dds, dps, D, hw, out_depth, out_conf, disp_range, n_range, out_depth_inv, nullptr, 0,
+                                       0, stream);
+}
+
+extern "C" int effi_softmax_regress_conf_up_f32(const float* logits, const float* depth, long dds, long dps, int D, int h, int w,
+                                                float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                                float* out_depth_inv, float* out_conf_up, int f, effi_stream_t stream) {
+    if (h < 1 || w < 1 || !out_conf_up) return EFFI_ERR_BADARG;
+    return softmax_regress_conf_launch(logits, depth, dds, dps, D, h * w, out_depth, out_conf, disp_range, n_range, out_depth_inv,
+                                       out_conf_up, w, f, stream);
 }
 
 extern "C" int effi_vol_lookup1d_f32(const float* vol, long vds, long vps, int Dp, const float* query, long qds,
@@ -771,19 +795,11 @@ struct SrMaps {                       // up to 4 groups of planes with one geome
     int planes[4], h[4], w[4], hp[4], wp[4];
     int first[5];                     // first block of each group
 };
-// zero what a producer never writes: row 0, rows h+1.., column 0, columns w+1.. of every plane (16-byte units)
-__global__ __launch_bounds__(TPB) void sr_clear_border_kernel(SrMaps a) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < 4; ++j) k += ((int)blockIdx.x >= a.first[j]) ? 1 : 0;
-    unsigned short* base = a.base[0];
-    int planes = a.planes[0], h = a.h[0], w = a.w[0], hp = a.hp[0], wp = a.wp[0], b0 = a.first[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-        if (k == j) { base = a.base[j]; planes = a.planes[j]; h = a.h[j]; w = a.w[j]; hp = a.hp[j]; wp = a.wp[j]; b0 = a.first[j]; }
+// zero what a producer never writes: row 0, rows h+1.., column 0, columns w+1.. of every plane (16-byte units); i = index of the
+// unit among the border units of ``planes`` planes
+__device__ __forceinline__ void sr_clear_border_unit(unsigned short* __restrict__ base, int planes, int h, int w, int hp, int wp, long i) {
     // border units of one plane: (hp - h) full rows + h rows of (wp - w) units
     const int rowpart = (hp - h) * wp, per_plane = rowpart + h * (wp - w);
-    const long i = (long)(blockIdx.x - b0) * TPB + threadIdx.x;
     if (i >= (long)planes * per_plane) return;
     const int pl = (int)(i / per_plane), r = (int)(i - (long)pl * per_plane);
     int y, x;
@@ -797,6 +813,17 @@ __global__ __launch_bounds__(TPB) void sr_clear_border_kernel(SrMaps a) {
         x = cx == 0 ? 0 : w + cx;                                  // column 0, then columns w+1 .. wp-1
     }
     *reinterpret_cast<float4*>(base + (((long)pl * hp + y) * wp + x) * 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+__global__ __launch_bounds__(TPB) void sr_clear_border_kernel(SrMaps a) {
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) k += ((int)blockIdx.x >= a.first[j]) ? 1 : 0;
+    unsigned short* base = a.base[0];
+    int planes = a.planes[0], h = a.h[0], w = a.w[0], hp = a.hp[0], wp = a.wp[0], b0 = a.first[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (k == j) { base = a.base[j]; planes = a.planes[j]; h = a.h[j]; w = a.w[j]; hp = a.hp[j]; wp = a.wp[j]; b0 = a.first[j]; }
+    sr_clear_border_unit(base, planes, h, w, hp, wp, (long)(blockIdx.x - b0) * TPB + threadIdx.x);
 }
 
 // fp32 planar [C][h][w] -> split-resident map: a thread owns (octet, pixel)
@@ -821,6 +848,10 @@ struct SplitStagesSr {
     unsigned short* hidden_sr[4];
     int hd[4], cd[4], h[4], w[4], hp[4], wp[4], q4[4];
     int first[5];
+    // border clearing folded into the launch (effi_split_tanh_relu_stages_sr_clear_f32): the last blocks of a stage, from local block
+    // nsplit[k] on, zero the border units of clear_planes[k] planes of the stage's geometry starting at clear_base[k] (0 planes: none)
+    unsigned short* clear_base[4];
+    int clear_planes[4], nsplit[4];
 };
 __global__ __launch_bounds__(TPB) void split_tanh_relu_stages_sr_kernel(SplitStagesSr a) {
     int k = 0;
@@ -837,6 +868,17 @@ __global__ __launch_bounds__(TPB) void split_tanh_relu_stages_sr_kernel(SplitSta
             ctx = a.ctx[j]; hidden = a.hidden[j]; inp = a.inp[j]; hsr = a.hidden_sr[j];
             hd = a.hd[j]; cd = a.cd[j]; h = a.h[j]; w = a.w[j]; hp = a.hp[j]; wp = a.wp[j]; b0 = a.first[j]; q4 = a.q4[j];
         }
+    {
+        unsigned short* cbase = a.clear_base[0];
+        int cplanes = a.clear_planes[0], nsplit = a.nsplit[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+            if (k == j) { cbase = a.clear_base[j]; cplanes = a.clear_planes[j]; nsplit = a.nsplit[j]; }
+        if ((int)blockIdx.x - b0 >= nsplit) {          // workgroup-uniform: a border block
+            sr_clear_border_unit(cbase, cplanes, h, w, hp, wp, (long)(blockIdx.x - b0 - nsplit) * TPB + threadIdx.x);
+            return;
+        }
+    }
     // work items: (octet of hidden channels, pixel) for the hidden half [hd % 8 == 0], then (channel quad, pixel) for the input half [cd % 4 == 0]
     const long hw = (long)h * w, n_h = (long)(hd >> 3) * hw, n_i = (long)(cd >> 2) * hw;
     const long i = (long)(blockIdx.x - b0) * TPB + threadIdx.x;
@@ -903,9 +945,10 @@ extern "C" int effi_sr_from_planar_f32(const float* in, int channels, int h, int
     return EFFI_OK;
 }
 
-extern "C" int effi_split_tanh_relu_stages_sr_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
-                                                  float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp,
-                                                  float* const* inp, const int* hidden_q4, int n_stages, effi_stream_t stream) {
+static int split_tanh_relu_stages_sr_launch(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
+                                            float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp,
+                                            float* const* inp, const int* hidden_q4, void* const* clear_base, const int* clear_planes,
+                                            int n_stages, effi_stream_t stream) {
     if (!ctx || !hd || !cd || !h || !w || !hidden || !hidden_sr || !hp || !wp || !inp || n_stages < 1 || n_stages > 4) return EFFI_ERR_BADARG;
     SplitStagesSr a;
     int blocks = 0;
@@ -919,12 +962,32 @@ extern "C" int effi_split_tanh_relu_stages_sr_f32(const float* const* ctx, const
         a.q4[k] = hidden_q4 ? hidden_q4[j] : 0;
         if (a.q4[k] && (reinterpret_cast<uintptr_t>(hidden[j]) & 15)) return EFFI_ERR_BADARG;
         a.first[k] = blocks;
-        if (k < n_stages) blocks += effi_cdiv((long)h[j] * w[j] * ((hd[j] >> 3) + (cd[j] >> 2)), TPB);
+        a.nsplit[k] = effi_cdiv((long)h[j] * w[j] * ((hd[j] >> 3) + (cd[j] >> 2)), TPB);
+        a.clear_base[k] = clear_base ? reinterpret_cast<unsigned short*>(clear_base[j]) : nullptr;
+        a.clear_planes[k] = clear_base ? clear_planes[j] : 0;
+        if (clear_base && (!clear_base[j] || clear_planes[j] < 1 || (reinterpret_cast<uintptr_t>(clear_base[j]) & 15))) return EFFI_ERR_BADARG;
+        if (k < n_stages)
+            blocks += a.nsplit[k] + effi_cdiv((long)a.clear_planes[k] * ((long)(hp[j] - h[j]) * wp[j] + (long)h[j] * (wp[j] - w[j])), TPB);
     }
     a.first[4] = blocks;
     hipLaunchKernelGGL(split_tanh_relu_stages_sr_kernel, dim3(blocks), dim3(TPB), 0, effi_s(stream), a);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
+}
+
+extern "C" int effi_split_tanh_relu_stages_sr_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
+                                                  float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp,
+                                                  float* const* inp, const int* hidden_q4, int n_stages, effi_stream_t stream) {
+    return split_tanh_relu_stages_sr_launch(ctx, hd, cd, h, w, hidden, hidden_sr, hp, wp, inp, hidden_q4, nullptr, nullptr, n_stages, stream);
+}
+
+extern "C" int effi_split_tanh_relu_stages_sr_clear_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
+                                                        float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp,
+                                                        float* const* inp, const int* hidden_q4, void* const* clear_base,
+                                                        const int* clear_planes, int n_stages, effi_stream_t stream) {
+    if (!clear_base || !clear_planes) return EFFI_ERR_BADARG;
+    return split_tanh_relu_stages_sr_launch(ctx, hd, cd, h, w, hidden, hidden_sr, hp, wp, inp, hidden_q4, clear_base, clear_planes, n_stages,
+                                            stream);
 }
 
 namespace {

@@ -327,21 +327,23 @@ class Effi_MVS_plus(nn.Module):
         pairs {stageK: [N,2,4,4]}; disp_range [384] ascending inverse depths."""
         D1 = self.depth_stage_nums[0]
         ops.mark("begin")
-        hyp, misc = ops.stage1_hypotheses(disp_range, D1)      # misc: 3 intervals, depth_min_, depth_max_
+        keys = ["stage{}".format(s + 1) for s in range(self.num_stage)]
+        # per-stage inputs that depend on nothing but the features / cameras / context pyramid: relative projections of all
+        # stages in one launch -- the launch that also makes the stage-1 hypotheses (option setup_fused) --, tanh / relu halves of all
+        # context maps (hidden state and context input of the update blocks) in one launch
+        if self.num_stage <= 4 and ops.option("setup_fused"):
+            (hyp, misc), rts = ops.cascade_setup(disp_range, D1, [pairs[k].contiguous() for k in keys])
+        else:
+            hyp, misc = ops.stage1_hypotheses(disp_range, D1)      # misc: 3 intervals, depth_min_, depth_max_
+            if self.num_stage <= 4:
+                rts = ops.compose_rel_proj_stages([pairs[k].contiguous() for k in keys])
+            else:
+                rts = [ops.compose_rel_proj(pairs[k]) for k in keys]
         g_min, g_max = misc[3:4], misc[4:5]
         preds, inter = [], {}
         conf = None
         weights = reg_vol = cur_vol = None
         lo_prev, hi_prev = g_min, g_max          # depth range the PREVIOUS stage's volumes are sampled on
-
-        keys = ["stage{}".format(s + 1) for s in range(self.num_stage)]
-        # per-stage inputs that depend on nothing but the features / cameras / context pyramid: relative projections of all
-        # stages in one launch, tanh / relu halves of all context maps (hidden state and context input of the update blocks)
-        # in one launch
-        if self.num_stage <= 4:
-            rts = ops.compose_rel_proj_stages([pairs[k].contiguous() for k in keys])
-        else:
-            rts = [ops.compose_rel_proj(pairs[k]) for k in keys]
 
         table = feats if isinstance(feats, ops.ViewTable) else None     # maps read through a device pointer table (scan_eval.py)
 
@@ -351,8 +353,9 @@ class Effi_MVS_plus(nn.Module):
             maps = [f[keys[s]] for f in feats]
             return ops.to_nhwc(maps), rts[s], maps[0].shape
 
-        # split-resident maps of the three update blocks (ops.SRMap): one allocation per stage, all borders zeroed by ONE launch, the
-        # initial hidden states written in both forms by the launch that splits the context maps
+        # split-resident maps of the three update blocks (ops.SRMap): one allocation per stage, the initial hidden states written in
+        # both forms by the launch that splits the context maps, which also zeroes all borders (option clear_fused; else ONE launch
+        # of its own does)
         sr_maps = None
         use_sr = (ops.uses_sr() and self.num_stage <= 4 and self.CostNum == 3
                   and all(hd in (16, 32, 48) for hd in self.hdim_stage[:self.num_stage])
@@ -369,11 +372,14 @@ class Effi_MVS_plus(nn.Module):
                 nm = BasicUpdateBlock.N_SR_MAPS
                 sr_maps = [ops.sr_alloc(nm, self.hdim_stage[s], cs[s].shape[1], cs[s].shape[2], cs[s].device, clear=False)
                            for s in range(self.num_stage)]
-                ops.sr_clear_border(sr_maps)
+                clear_fused = bool(ops.option("clear_fused"))
+                if not clear_fused:
+                    ops.sr_clear_border(sr_maps)
                 state_q4 = [self.update_block[s].state_q4_ok(not want_intermediates) and ops.uses_sr(cs[s].shape[1] * cs[s].shape[2])
                             for s in range(self.num_stage)]
                 return dict(enumerate(ops.split_tanh_relu_stages_sr(cs, self.hdim_stage[:self.num_stage], self.cdim_stage[:self.num_stage],
-                                                                    [m[-1] for m in sr_maps], q4=state_q4)))
+                                                                    [m[-1] for m in sr_maps], q4=state_q4,
+                                                                    clear=sr_maps if clear_fused else None)))
             if self.num_stage <= 4:
                 return dict(enumerate(ops.split_tanh_relu_stages(cs, self.hdim_stage[:self.num_stage], self.cdim_stage[:self.num_stage])))
             return {s: ops.split_tanh_relu(cs[s], self.hdim_stage[s], self.cdim_stage[s]) for s in range(self.num_stage)}
@@ -398,9 +404,12 @@ class Effi_MVS_plus(nn.Module):
                 weights = self.PixelwiseNet.run(entropy)
                 cur_vol = ops.view_aggregate(sim_views, weights)
                 reg_vol = self.cost_regularization.run(cur_vol.unsqueeze(0))[0][0]
-                depth, c, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)     # + depth_to_inv of it (:538)
-                with ops.Branch() as tail_branch:      # the confidence map is only an output: off the critical path
-                    conf = ops.upsample_nearest(c.unsqueeze(0), 4)[0]
+                if ops.option("conf_fused"):           # the full-size confidence map comes out of the same launch
+                    depth, c, inv_next, conf = ops.softmax_regress_conf(reg_vol, hyp, disp_range, conf_up=4)
+                else:
+                    depth, c, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)     # + depth_to_inv of it (:538)
+                    with ops.Branch() as tail_branch:      # the confidence map is only an output: off the critical path
+                        conf = ops.upsample_nearest(c.unsqueeze(0), 4)[0]
                 preds.append(depth)
                 lo_cur, hi_cur = g_min, g_max
             else:

@@ -286,6 +286,20 @@ class BasicUpdateBlock(nn.Module):
         return (bool(ops.option("state_q4")) and fuse_upsample and self.UpMask and not ops.option("gru_fused")
                 and self._sr_structure_ok(self.depth_head.conv1.in_channels))
 
+    def head_fused_tile(self, hd, h, w):
+        """Tile of the one-launch depth head (ops.depth_head_sr) for an h x w map, or 0 where conv1 + taps and ``ops.head_update`` stay
+        two launches.  Options head_fused (0 off, 1 this rule, 2 everywhere) / head_fused_tile (a tile instead of the rule's)."""
+        mode = ops.option("head_fused")
+        if not mode or hd not in (16, 32, 48):
+            return 0
+        forced = ops.option("head_fused_tile")
+        if forced:
+            return forced
+        # measured per launch (profiles/fused_small_launches_ab.txt; two launches -> tile 2 / 4 / 8): 148x200 hd 48 12.4 -> 11.6 / 12.1 /
+        # 10.8 us, 296x400 hd 32 16.9 -> 15.5 / 14.2 / 14.6, 592x800 hd 16 26.8 -> 24.1 / 21.2 / 22.0: faster at every stage; 16 x 16
+        # pixels per workgroup, on eight waves while there are fewer workgroups than CUs
+        return 8 if -(-h // 14) * -(-w // 14) < 256 else 4
+
     def run_fused_sr(self, net, lookup, inv_depth, context, seq_len, disp_range, fuse_upsample=False, maps=None, net_sr_ready=False,
                      net_owned=False, net_q4=False):
         """``run_fused`` with the iteration's maps split-resident.  ``maps``: the N_SR_MAPS SRMaps [A, B, C, D, H] of this block
@@ -327,6 +341,7 @@ class BasicUpdateBlock(nn.Module):
         wh2, bh2 = dh._c2t.get([dh.conv2.weight], lambda: packing.pack_head_taps(dh.conv2.weight, hd))
         inv_list, mask_list, depth_list = [], [], []
         gen_pair = ops.option("enc_gen") != 0 and getattr(lookup, "encoder_pair_sr", None) is not None
+        head_tile = self.head_fused_tile(hd, h, w)
         H_first = Hm
         h_pp = [None, net if net_owned else None]               # fp32 state buffers of the fused form: iteration i writes h_pp[i % 2]
                                                                 # (iteration 0 reads the caller's ``net``; it is reused from iteration 1 on if ours)
@@ -358,8 +373,11 @@ class BasicUpdateBlock(nn.Module):
             if want_mask and not fused_up:
                 with ops.Branch() as br:
                     mask = self.run_mask(net)
-            part = ops.conv2d_k3_k1_sr([Hm], wh1.wx, bh1, hd, None, wh2, bh2, 9, relu=False, relu1=True, out=head_buf)
-            inv_depth, depth = ops.head_update(part, dh.conv2.bias, inv_depth, disp_range)
+            if head_tile:                      # conv1 + ReLU + tap projections + their 3x3 sum + update in one launch
+                inv_depth, depth = ops.depth_head_sr([Hm], wh1.wx, bh1, hd, wh2, bh2, dh.conv2.bias, inv_depth, disp_range, head_tile)
+            else:
+                part = ops.conv2d_k3_k1_sr([Hm], wh1.wx, bh1, hd, None, wh2, bh2, 9, relu=False, relu1=True, out=head_buf)
+                inv_depth, depth = ops.head_update(part, dh.conv2.bias, inv_depth, disp_range)
             if fused_up:                       # needs the NEW inverse depth: after the head
                 wm, bm = _pack(self._m0, self.mask[0])
                 c1 = self.mask[0].out_channels

@@ -98,7 +98,13 @@ def _x3(name):
 # forms) in the library's own table (include/effi_mvs_hip.h: effi_set_option).  Both are initialised ONCE from the environment
 # (EFFI_<NAME>) and changed afterwards through ``set_option`` -- nothing on a per-call path reads the environment.
 _PY_OPTION_DEFAULTS = {"warp_x3": 0, "state_q4": 1, "c1k7_mfma": 1, "k5s2_split": 1, "roll": 1, "conv3d_unaligned_split": 1, "conv3d_s2_split": 1, "fpn_conv0_fused": 1,
-                       "fpn_split_head": 1, "csp_pair": 1, "head_taps": 1, "enc_tail": 0, "enc_gen": 1, "reduce_chunk": 2048, "gru_fused": 0, "csp_gen": 0}
+                       "fpn_split_head": 1, "csp_pair": 1, "head_taps": 1, "enc_tail": 0, "enc_gen": 1, "reduce_chunk": 2048, "gru_fused": 0, "csp_gen": 0,
+                       # small per-pixel launches of the hot path folded into their neighbours (0 = the separate launches, bitwise the same):
+                       # head_fused: the depth head's tap sum inside its convolution (1 = where the rule of
+                       # BasicUpdateBlock.head_fused_tile finds it faster, 2 = everywhere); head_fused_tile: 0 = that rule, else the tile
+                       # (2 / 4 / 8, effi_depth_head_bf16x3_sr); clear_fused: SR border clear inside the context split; setup_fused:
+                       # hypotheses + relative projections in one launch; conf_fused: full-size confidence written by the soft-argmin
+                       "head_fused": 1, "head_fused_tile": 0, "clear_fused": 1, "setup_fused": 1, "conf_fused": 1}
 _PY_OPTS = {k: int(os.environ.get("EFFI_" + k.upper(), v)) for k, v in _PY_OPTION_DEFAULTS.items()}
 LIB_OPTIONS = ("warp_lds_kb", "dyn_form", "dyn_setup_exact", "dyn_xchg", "pixnet_mfma", "force_mr", "mr4_min", "mr4_nt2_max", "mr2_min",
                "wide_tiles", "roll_mr", "roll_zt", "roll_rp", "deconv_mr", "sr_waves", "enc_gen_mr3", "c3_lean", "dyn_win")
@@ -362,6 +368,23 @@ def compose_rel_proj_stages(pairs_list):
     check(_lib.lib().effi_compose_rel_proj_stages_f32(_ptr_array(pairs_list), len(pairs_list), n, _p(rt), _stream()),
           "effi_compose_rel_proj_stages_f32")
     return [rt[k] for k in range(len(pairs_list))]
+
+
+def cascade_setup(disp_range, D, pairs_list):
+    """``stage1_hypotheses`` and ``compose_rel_proj_stages`` in one launch -> ((depths [D], intervals [5]), [rt [N-1,12], ...])."""
+    _t(disp_range, "disp_range")
+    for p_ in pairs_list:
+        _t(p_, "pairs")
+    n = pairs_list[0].shape[0]
+    if len(pairs_list) > 4 or any(p_.shape[0] != n for p_ in pairs_list):
+        raise ValueError("cascade_setup: up to 4 stages with the same number of views")
+    dev = disp_range.device
+    depths = torch.empty(D, device=dev, dtype=torch.float32)
+    intervals = torch.empty(5, device=dev, dtype=torch.float32)   # 3 intervals, depth_min_, depth_max_
+    rt = torch.empty(len(pairs_list), n - 1, 12, device=dev, dtype=torch.float32)
+    check(_lib.lib().effi_cascade_setup_f32(_p(disp_range), disp_range.numel(), D, _p(depths), _p(intervals), _ptr_array(pairs_list),
+                                            len(pairs_list), n, _p(rt), _stream()), "effi_cascade_setup_f32")
+    return (depths, intervals), [rt[k] for k in range(len(pairs_list))]
 
 
 def rel_proj(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch.Tensor:
@@ -867,9 +890,10 @@ def resize_planar(x, dst_h, dst_w, out=None):
     return out
 
 
-def softmax_regress_conf(logits, depth, disp_range=None):
+def softmax_regress_conf(logits, depth, disp_range=None, conf_up=0):
     """logits [D,h,w]; depth [D] / [D,h,w] -> (depth [h,w], confidence [h,w]) and, with ``disp_range``, also the regressed
-    depth as normalised inverse depth (``depth_to_inv`` of it, written by the same kernel)."""
+    depth as normalised inverse depth (``depth_to_inv`` of it, written by the same kernel).  ``conf_up`` = f > 0: the result
+    tuple ends with the confidence replicated f x f ([h*f,w*f], ``upsample_nearest`` of it) written by the same kernel."""
     D, h, w = logits.shape
     _t(logits, "logits"), _t(depth, "depth", contiguous=False)
     depth, dds, dps = _depth_strides(depth, D, h, w)
@@ -879,6 +903,11 @@ def softmax_regress_conf(logits, depth, disp_range=None):
     if disp_range is not None:
         _t(disp_range, "disp_range")
         oi, n_range = torch.empty(h, w, device=logits.device, dtype=torch.float32), disp_range.numel()
+    if conf_up:
+        ou = torch.empty(h * conf_up, w * conf_up, device=logits.device, dtype=torch.float32)
+        check(_lib.lib().effi_softmax_regress_conf_up_f32(_p(logits), _p(depth), dds, dps, D, h, w, _p(od), _p(oc), _p(disp_range), n_range,
+                                                           _p(oi), _p(ou), conf_up, _stream()), "effi_softmax_regress_conf_up_f32")
+        return (od, oc, ou) if disp_range is None else (od, oc, oi, ou)
     check(_lib.lib().effi_softmax_regress_conf_f32(_p(logits), _p(depth), dds, dps, D, h * w, _p(od), _p(oc), _p(disp_range), n_range,
                                                     _p(oi), _stream()), "effi_softmax_regress_conf_f32")
     return (od, oc) if disp_range is None else (od, oc, oi)
@@ -1256,16 +1285,22 @@ def _sr(m, name):
     return m
 
 
-def sr_clear_border(groups):
-    """Zero the borders of up to 4 groups of SR maps (each group: consecutive maps of ONE allocation and geometry) in one launch."""
-    if not 1 <= len(groups) <= 4:
-        raise ValueError("sr_clear_border: 1..4 groups")
+def _sr_groups(groups, name):
+    """(first map, plane count) of each group of SR maps: consecutive maps of ONE allocation and geometry."""
     firsts = [_sr(g[0], "SR map") for g in groups]
     planes = [2 * (g[0].channels // 8) * len(g) for g in groups]
     for g in groups:       # consecutive maps of one allocation
         step = g[0].t.numel() * 2
         if any(m.t.data_ptr() != g[0].t.data_ptr() + i * step for i, m in enumerate(g)):
-            raise ValueError("sr_clear_border: a group must be consecutive maps of one sr_alloc block")
+            raise ValueError(f"{name}: a group must be consecutive maps of one sr_alloc block")
+    return firsts, planes
+
+
+def sr_clear_border(groups):
+    """Zero the borders of up to 4 groups of SR maps (each group: consecutive maps of ONE allocation and geometry) in one launch."""
+    if not 1 <= len(groups) <= 4:
+        raise ValueError("sr_clear_border: 1..4 groups")
+    firsts, planes = _sr_groups(groups, "sr_clear_border")
     check(_lib.lib().effi_sr_clear_border(_ptr_array([m.t for m in firsts]), _int_array(planes), _int_array([m.h for m in firsts]),
                                            _int_array([m.w for m in firsts]), _int_array([m.hp for m in firsts]),
                                            _int_array([m.wp for m in firsts]), len(groups), _stream()), "effi_sr_clear_border")
@@ -1281,9 +1316,10 @@ def sr_from_planar(x, out=None):
     return out
 
 
-def split_tanh_relu_stages_sr(ctxs, hds, cds, hidden_srs, q4=None):
+def split_tanh_relu_stages_sr(ctxs, hds, cds, hidden_srs, q4=None, clear=None):
     """``split_tanh_relu_stages`` that also writes each hidden state into the given SRMap -> [(hidden, inp), ...] (fp32).
-    ``q4``: per stage, write the fp32 hidden state in the Q4 layout (same shape [hd,h,w] tensor, values ordered [hd/4][h][w][4])."""
+    ``q4``: per stage, write the fp32 hidden state in the Q4 layout (same shape [hd,h,w] tensor, values ordered [hd/4][h][w][4]).
+    ``clear``: per stage, a group of SR maps of the stage's geometry (as for ``sr_clear_border``) whose borders the same launch zeroes."""
     outs = []
     for c_, hd, cd, m in zip(ctxs, hds, cds, hidden_srs):
         _t(c_, "context"), _sr(m, "hidden SR map")
@@ -1294,6 +1330,17 @@ def split_tanh_relu_stages_sr(ctxs, hds, cds, hidden_srs, q4=None):
                      torch.empty(cd, h, w, device=c_.device, dtype=torch.float32)))
     if len(ctxs) > 4:
         raise ValueError("split_tanh_relu_stages_sr: up to 4 stages")
+    if clear is not None:
+        if len(clear) != len(ctxs) or any((g[0].h, g[0].w, g[0].hp, g[0].wp) != (m.h, m.w, m.hp, m.wp) for g, m in zip(clear, hidden_srs)):
+            raise ValueError("split_tanh_relu_stages_sr: one group of maps of the stage's geometry per stage")
+        firsts, planes = _sr_groups(clear, "split_tanh_relu_stages_sr")
+        check(_lib.lib().effi_split_tanh_relu_stages_sr_clear_f32(
+            _ptr_array(ctxs), _int_array(list(hds)), _int_array(list(cds)), _int_array([c_.shape[1] for c_ in ctxs]),
+            _int_array([c_.shape[2] for c_ in ctxs]), _ptr_array([o[0] for o in outs]), _ptr_array([m.t for m in hidden_srs]),
+            _int_array([m.hp for m in hidden_srs]), _int_array([m.wp for m in hidden_srs]), _ptr_array([o[1] for o in outs]),
+            _int_array([int(bool(v)) for v in (q4 if q4 is not None else [0] * len(ctxs))]), _ptr_array([m.t for m in firsts]),
+            _int_array(planes), len(ctxs), _stream()), "effi_split_tanh_relu_stages_sr_clear_f32")
+        return outs
     check(_lib.lib().effi_split_tanh_relu_stages_sr_f32(
         _ptr_array(ctxs), _int_array(list(hds)), _int_array(list(cds)), _int_array([c_.shape[1] for c_ in ctxs]),
         _int_array([c_.shape[2] for c_ in ctxs]), _ptr_array([o[0] for o in outs]), _ptr_array([m.t for m in hidden_srs]),
@@ -1456,6 +1503,25 @@ def conv2d_k3_k1_sr(srcs, wpack, bias, cout1, extra, w2pack, bias2, cout2, relu=
                 _p(w2pack), _p(bias2), cout2, int(relu), h, w, g.hp, g.wp, _p(None if out_sr is not None else out),
                 _p(out_sr.t if out_sr is not None else None), _stream()), "effi_conv2d_k3_k1_bf16x3_sr")
     return out_sr if out_sr is not None else out
+
+
+def depth_head_sr(srcs, wpack, bias, cout1, w2pack, bias2_taps, bias2, inv_depth, disp_range, tile):
+    """``conv2d_k3_k1_sr`` with the depth head's nine tap projections + ``head_update`` in one launch (the tap planes stay in LDS)
+    -> (inv_depth + tanh(conv2(relu(conv1)))), its depth), both [1,h,w].  ``tile``: 2, 4 or 8 (effi_depth_head_bf16x3_sr)."""
+    g = _sr_srcs(srcs)
+    _t(inv_depth, "inv_depth"), _t(disp_range, "disp_range"), _t(bias2, "bias")
+    h, w = g.h, g.w
+    if inv_depth.numel() != h * w:
+        raise ValueError("depth_head_sr: inv_depth must hold h*w values")
+    out_inv = torch.empty(1, h, w, device=g.t.device, dtype=torch.float32)
+    out_depth = torch.empty(1, h, w, device=g.t.device, dtype=torch.float32)
+    cin = sum(m.channels for m in srcs)
+    work = lambda: {"flops": 2.0 * h * w * (cin * cout1 * 9 + cout1 * 9), "bytes": 4.0 * h * w * (cin + 3)}
+    check(_call(f"depth_head_nt{(cout1 + 15) // 16}", work, _x3("effi_depth_head_bf16x3_sr"), _ptr_array([m.t for m in srcs]),
+                _int_array([m.channels for m in srcs]), len(srcs), _p(wpack), _p(bias), cout1, _p(w2pack), _p(bias2_taps), _p(bias2),
+                _p(inv_depth), _p(disp_range), disp_range.numel(), h, w, g.hp, g.wp, int(tile), _p(out_inv), _p(out_depth), _stream()),
+          "effi_depth_head_bf16x3_sr")
+    return out_inv, out_depth
 
 
 def conv2d_k3_k1_up2x_sr(srcs, wpack, bias, cout1, w2pack, bias2, inv_depth, disp_range, want_depth_inv=True):

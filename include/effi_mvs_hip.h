@@ -88,6 +88,10 @@ int effi_compose_rel_proj_f32(const float* pairs, int n_views, float* rt_out, ef
 int effi_compose_rel_proj_stages_f32(const float* const* pairs, int n_stages, int n_views, float* rt_out,
                                      effi_stream_t stream);
 int effi_rel_proj_f32(const float* src_proj, const float* ref_proj, float* rt_out, effi_stream_t stream);
+/* The cascade's set-up in ONE launch: effi_stage1_hypotheses_f32 (disp_range .. intervals) and effi_compose_rel_proj_stages_f32
+ * (pairs .. rt_out), same arguments, same results bit for bit. */
+int effi_cascade_setup_f32(const float* disp_range, int n_range, int D, float* depths, float* intervals,
+                           const float* const* pairs, int n_stages, int n_views, float* rt_out, effi_stream_t stream);
 
 /* ---- layout: planar [C][HW] -> nhwc [HW][C] for n tensors (feature maps arrive NCHW from the FPN,
  * models/module.py:400-409).  srcs/dsts: HOST arrays of n device pointers, n <= EFFI_MAX_VIEWS+1. */
@@ -268,6 +272,12 @@ int effi_deconv3d_k3s2_bf16x3_f32(const float* in, int cin, const void* wpack_bf
 int effi_softmax_regress_conf_f32(const float* logits, const float* depth, long depth_dstride,
                                   long depth_pstride, int D, int hw, float* out_depth, float* out_conf,
                                   const float* disp_range, int n_range, float* out_depth_inv, effi_stream_t stream);
+/* The same on an [h][w] map (hw = h * w), ALSO writing the confidence replicated f x f into out_conf_up [h*f][w*f] (F.interpolate
+ * nearest, models/Effi_MVS_plus.py:479): what effi_upsample_nearest_f32 would make of out_conf, without that launch.  f == 4:
+ * out_conf_up 16-byte aligned. */
+int effi_softmax_regress_conf_up_f32(const float* logits, const float* depth, long depth_dstride, long depth_pstride, int D, int h,
+                                     int w, float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                     float* out_depth_inv, float* out_conf_up, int f, effi_stream_t stream);
 
 /* ---- K8: 1-D volume lookup (pro_bilinear_sampler), models/Effi_MVS_plus.py:102-134,151-164.
  * vol: value k of pixel p at vol[k*vol_dstride + p*vol_pstride], Dp entries per pixel, (h,w) pixels.
@@ -724,6 +734,13 @@ int effi_sr_from_planar_f32(const float* in, int channels, int h, int w, void* s
 int effi_split_tanh_relu_stages_sr_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
                                        float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp, float* const* inp,
                                        const int* hidden_q4, int n_stages, effi_stream_t stream);
+/* The same launch ALSO zeroing the borders of the stages' SR maps (what effi_sr_clear_border does): clear_base[k] = first of
+ * clear_planes[k] consecutive planes of stage k's geometry (h, w, hp, wp)[k] -- all maps of the stage's update block, the hidden
+ * state's among them.  The maps may come from an allocator that recycles memory: the borders are cleared on every call. */
+int effi_split_tanh_relu_stages_sr_clear_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
+                                             float* const* hidden, void* const* hidden_sr, const int* hp, const int* wp,
+                                             float* const* inp, const int* hidden_q4, void* const* clear_base, const int* clear_planes,
+                                             int n_stages, effi_stream_t stream);
 /* effi_encoder_inputs_bf16x3_f32 (models/update.py:86,90) writing both maps split-resident (sr_c1 = relu(convc1(cost)),
  * sr_d1 = relu(convd1(inv_depth)); [cout/8][2][hp][wp][8]). */
 int effi_encoder_inputs_bf16x3_sr(const float* inv_depth, const float* disp_range, int n_range, const float* interval,
@@ -758,6 +775,15 @@ int effi_conv2d_k3_bf16x3_pair_sr(const void* const* srcs_a, const int* src_chan
 int effi_conv2d_k3_k1_bf16x3_sr(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16, const float* bias,
                                 int cout1, int relu1, const float* extra, int c_extra, const void* w2pack_bf16, const float* bias2,
                                 int cout2, int relu, int h, int w, int hp, int wp, float* out, void* out_sr, effi_stream_t stream);
+/* The depth head in ONE launch (models/update.py:14-15,21,125-127): effi_conv2d_k3_k1_bf16x3_sr with conv2's nine tap projections
+ * (relu1 = 1, cout2 = 9, w2pack / bias2_taps = packing.pack_head_taps) followed by effi_head_update_f32 (bias2 = conv2's bias),
+ * bitwise, without the nine tap planes in memory: a workgroup computes the taps of its output pixels plus a one-pixel ring and sums
+ * them through LDS.  tile: computed pixels per workgroup, 2 = 8 x 16, 4 = 16 x 16, 8 = 16 x 16 on eight waves (outputs: the interior
+ * (rows - 2) x 14).  cout1 in {16, 32, 48}. */
+int effi_depth_head_bf16x3_sr(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16, const float* bias,
+                              int cout1, const void* w2pack_bf16, const float* bias2_taps, const float* bias2, const float* inv_depth,
+                              const float* disp_range, int n_range, int h, int w, int hp, int wp, int tile, float* out_inv,
+                              float* out_depth, effi_stream_t stream);
 /* effi_conv2d_k3_k1_up2x_bf16x3_f32 on SR inputs (mask head + convex upsampling, models/update.py:109-112,136-138,
  * models/Effi_MVS_plus.py:167-178). */
 int effi_conv2d_k3_k1_up2x_bf16x3_sr(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
@@ -788,6 +814,10 @@ int effi_conv2d_k3_k1_up2x_bf16x3_sr_bf16(const void* const* srcs, const int* sr
                                           const float* bias, int cout1, const void* w2pack_bf16, const float* bias2,
                                           const float* inv_depth, const float* disp_range, int n_range, int h, int w, int hp, int wp,
                                           float* out_depth, float* out_depth_inv, effi_stream_t stream);
+int effi_depth_head_bf16x3_sr_bf16(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                   const float* bias, int cout1, const void* w2pack_bf16, const float* bias2_taps, const float* bias2,
+                                   const float* inv_depth, const float* disp_range, int n_range, int h, int w, int hp, int wp, int tile,
+                                   float* out_inv, float* out_depth, effi_stream_t stream);
 int effi_gru_zr_q_fused_bf16x3_sr_bf16(const void* H_in, const void* X, const float* h_in, const void* wzr_pack, const float* bias_zr,
                                        const void* wq_pack, const float* bias_q, int hd, int h, int w, int hp, int wp, float* h_out,
                                        void* H_out, effi_stream_t stream);

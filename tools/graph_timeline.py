@@ -13,7 +13,7 @@ def short(n):
 def main(path, back=2):
     rows = [r for r in csv.DictReader(open(path))]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(rows) if "stage1_hypotheses" in r["Kernel_Name"]]
+    idx = [i for i, r in enumerate(rows) if "stage1_hypotheses" in r["Kernel_Name"] or "cascade_setup" in r["Kernel_Name"]]
     a, b = idx[-back - 1], idx[-back]
     seg = rows[a:b]
     t0 = int(seg[0]["Start_Timestamp"])

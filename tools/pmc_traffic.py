@@ -134,8 +134,8 @@ def main(fetch_csv, write_csv, out_json):
                   "l2_hit_rate": hit / (hit + miss) if hit + miss else None}
         print(f"{k:24s} n={n:3d} {us:8.1f} us  fetch {raw * scale / 1e6:8.1f} MB (raw {raw / 1e6:7.1f}) write {wr / 1e6:7.1f} MB"
               f"  L2 hit {100 * (hit / (hit + miss) if hit + miss else 0):5.1f}%  clk~{clk:4.2f} GHz")
-    # reference views in the profiled run: one stage1_hypotheses launch each
-    views = len(df.get("other:stage1_hypotheses_kernel", ()))
+    # reference views in the profiled run: one set-up launch each (cascade_setup_kernel; stage1_hypotheses_kernel with setup_fused = 0)
+    views = len(df.get("other:cascade_setup_kernel", ())) or len(df.get("other:stage1_hypotheses_kernel", ()))
     out["_meta"] = {"views": views, "note": "launches_profiled / views = launches per view; bench.py's roofline.traffic_per_view sums "
                                             "(fetch_bytes + write_bytes) x launches over all kernels / views"}
     tot = sum((v["fetch_bytes"] + v["write_bytes"]) * v["launches_profiled"] for k, v in out.items() if k != "_meta")

@@ -13,7 +13,7 @@ def short(n):
 def main(path, summary_only=False):
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(rows) if "stage1_hypotheses" in r["Kernel_Name"]]
+    idx = [i for i, r in enumerate(rows) if "stage1_hypotheses" in r["Kernel_Name"] or "cascade_setup" in r["Kernel_Name"]]
     a = idx[-1]
     last_end = int(rows[a]["Start_Timestamp"])
     t0 = last_end
