@@ -18,7 +18,7 @@ namespace {
 
 
 template <int KS, int NT, int EPI>
-__global__ __launch_bounds__(256) void conv2d_mfma_kernel(const Conv2dArgs a) {
+__device__ __forceinline__ void conv2d_mfma_tile(const Conv2dArgs a) {
     constexpr int R = KS / 2, TILE = 16, IW = TILE + 2 * R, CC = 16;
     constexpr int PL = (KS == 3) ? 336 : 272;                 // plane stride, == 16 (mod 32)
     constexpr int NE = CC * IW * IW;                          // elements staged per chunk
@@ -166,6 +166,17 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const Conv2dArgs a) {
     }
 }
 
+template <int KS, int NT, int EPI>
+__global__ __launch_bounds__(256) void conv2d_mfma_kernel(const Conv2dArgs a) {
+    conv2d_mfma_tile<KS, NT, EPI>(a);
+}
+
+// n_img images in one launch (ConvBatch, conv2d_x3.hpp): blockIdx.z = image.
+template <int KS, int NT, int EPI>
+__global__ __launch_bounds__(256) void conv2d_mfma_batch_kernel(const Conv2dArgs a, const ConvBatch b) {
+    conv2d_mfma_tile<KS, NT, EPI>(conv_batch_image(a, b, blockIdx.z));
+}
+
 // Epilogue of one lane's result: v[0..3] = conv + bias for pixels x..x+3 of row y, output channel co.
 // Shared by the fp32-MFMA kernel and the split-bf16 kernel (same C/D fragment layout).
 template <int EPI, bool ALIGNED>
@@ -246,8 +257,11 @@ __device__ __forceinline__ void conv_epilogue_store(const Conv2dArgs& a, float (
 //   * the k-steps of a chunk are fully unrolled with double-buffered fragments.
 //   * MR = rows per wave (1, 2 or 4): small images use small MR so the grid still covers the 256 CUs.
 // ------------------------------------------------------------------------------------------------
-template <int KS, int NT, int MR, int EPI, int CC, bool PERSIST, bool ALIGNED = true, int S = 1>
-__global__ __launch_bounds__(256) void conv2d_mfma_v2_kernel(const Conv2dArgs a, int tiles_x, int ntiles) {
+// BATCH: the workgroup's logical tile is ``btile`` (batched launches derive image and tile from the grid themselves, see
+// conv2d_mfma_v2_batch_kernel; never persistent or z-batched), else it comes from blockIdx.x.
+template <int KS, int NT, int MR, int EPI, int CC, bool PERSIST, bool ALIGNED = true, int S = 1, bool BATCH = false>
+__device__ __forceinline__ void conv2d_mfma_v2_tile(const Conv2dArgs a, int tiles_x, int ntiles, int btile = 0) {
+    static_assert(!(BATCH && PERSIST), "batched launches are one tile per workgroup");
     // S = stride (1, or 2 for the 5x5 down-sampling convs of the feature pyramid): output tile 16 x TR, input
     // tile S*(TR-1)+KS rows x S*15+KS columns, fetched from column S*x0 - XLEFT in aligned float4 units.
     // (For S = 2 the A reads have a 2-lane stride: 2-way bank conflicts, irrelevant at ~1 LDS read per MFMA.)
@@ -272,7 +286,7 @@ __global__ __launch_bounds__(256) void conv2d_mfma_v2_kernel(const Conv2dArgs a,
     // XCD-aware tile order (non-persistent launches): workgroups are dealt round-robin to the 8 XCDs, so
     // logical tiles are assigned such that each XCD owns a contiguous run of tiles -- x/y-neighbouring tiles,
     // whose halo rows share cache lines, then hit the same L2 instead of re-fetching over the fabric.
-    int tile = PERSIST ? (int)blockIdx.x : effi_xcd_remap(blockIdx.x, gridDim.x);
+    int tile = BATCH ? btile : (PERSIST ? (int)blockIdx.x : effi_xcd_remap(blockIdx.x, gridDim.x));
     if (tile >= ntiles) return;
 
     // per-thread state of the A prefetch: LDS slot and global offset (inside one channel map) of each of
@@ -440,6 +454,20 @@ __global__ __launch_bounds__(256) void conv2d_mfma_v2_kernel(const Conv2dArgs a,
         x0 = nx0;
         y0 = ny0;
     }
+}
+
+template <int KS, int NT, int MR, int EPI, int CC, bool PERSIST, bool ALIGNED = true, int S = 1>
+__global__ __launch_bounds__(256) void conv2d_mfma_v2_kernel(const Conv2dArgs a, int tiles_x, int ntiles) {
+    conv2d_mfma_v2_tile<KS, NT, MR, EPI, CC, PERSIST, ALIGNED, S>(a, tiles_x, ntiles);
+}
+
+// n_img images in one launch (ConvBatch, conv2d_x3.hpp; one tile per workgroup, never z-batched): grid (ntiles, n_img), the XCD remap
+// runs over images x tiles so that an XCD's run of tiles stays inside (mostly) one image.
+template <int KS, int NT, int MR, int EPI, int CC, bool ALIGNED = true, int S = 1>
+__global__ __launch_bounds__(256) void conv2d_mfma_v2_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    const int t = effi_xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    const int img = t / ntiles;
+    conv2d_mfma_v2_tile<KS, NT, MR, EPI, CC, false, ALIGNED, S, true>(conv_batch_image(a, b, img), tiles_x, ntiles, t - img * ntiles);
 }
 
 
@@ -1704,6 +1732,49 @@ int launch2d(const Conv2dArgs& a, hipStream_t st) {
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
+// Batched forms (ConvBatch): launch2d's rows-per-wave rule on the tile count of ALL images.  A pixel's accumulation order is (k-group,
+// tap) whatever the rows per wave, the chunk size or the kernel (v2 / the 16 x 16 kernel of unaligned rows), so image i has the bits
+// of the single-image launch whichever shape either rule picks.
+template <int KS, int NT, int MR, int EPI>
+int launch2d_v2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
+    hipLaunchKernelGGL((conv2d_mfma_v2_batch_kernel<KS, NT, MR, EPI, 8>), dim3(ntiles, b.n_img), dim3(256), 0, st, a, b, tiles_x, ntiles);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+template <int KS, int NT, int EPI>
+int launch2d_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    if ((a.w & 3) == 0) {
+        const long cols = effi_cdiv(a.w, 16);
+        const long t4 = cols * effi_cdiv(a.h, 16) * b.n_img, t2 = cols * effi_cdiv(a.h, 8) * b.n_img;
+        int mr;
+        if (t4 >= 512 || (KS == 1 && t4 >= 256)) mr = 4;
+        else if (t2 >= 512 || KS == 1) mr = 2;
+        else mr = 1;
+        if (mr == 4) return launch2d_v2_batch<KS, NT, 4, EPI>(a, b, st);
+        if (mr == 2) return launch2d_v2_batch<KS, NT, 2, EPI>(a, b, st);
+        return launch2d_v2_batch<KS, NT, (KS == 3 ? 1 : 2), EPI>(a, b, st);
+    }
+    if constexpr (EPI == EFFI_EPI_PLAIN) {
+        dim3 grid(effi_cdiv(a.w, 16), effi_cdiv(a.h, 16), b.n_img);
+        hipLaunchKernelGGL((conv2d_mfma_batch_kernel<KS, NT, EPI>), grid, dim3(256), 0, st, a, b);
+        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    }
+    return EFFI_ERR_BADARG;                    // (the entry has rejected w % 4 != 0 for every other epilogue)
+}
+
+template <int KS, int EPI>
+int dispatch_nt_batch(const Conv2dArgs& a, const ConvBatch& b, int nt, hipStream_t st) {
+    switch (nt) {
+        case 1: return launch2d_batch<KS, 1, EPI>(a, b, st);
+        case 2: return launch2d_batch<KS, 2, EPI>(a, b, st);
+        case 3: return launch2d_batch<KS, 3, EPI>(a, b, st);
+        case 4: return launch2d_batch<KS, 4, EPI>(a, b, st);
+        case 6: return launch2d_batch<KS, 6, EPI>(a, b, st);
+        default: return EFFI_ERR_UNSUPPORTED;
+    }
+}
+
 template <int KS, int EPI>
 int dispatch_nt(const Conv2dArgs& a, int nt, hipStream_t st) {
     switch (nt) {
@@ -1819,11 +1890,25 @@ extern "C" int effi_conv3d_k3s2_mfma_f32(const float* in, int cin, const float* 
 }
 #endif
 
+// Fills the image strides of a *_batch entry (n_src source strides, aux0, out0).  Returns false on a bad argument.
+static bool fill_conv_batch(ConvBatch& b, int n_img, const long* src_istride, int n_src, long aux0_istride, long out0_istride) {
+    if (n_img < 1 || n_img > 65535 || !src_istride || aux0_istride < 0 || out0_istride < 0) return false;
+    b.n_img = n_img;
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
+        b.src[i] = (i < n_src) ? src_istride[i] : 0;
+        if (b.src[i] < 0) return false;
+    }
+    b.aux0 = aux0_istride;
+    b.out0 = out0_istride;
+    return true;
+}
+
 #ifndef EFFI_BF16_ONLY
-extern "C" int effi_conv2d_f32(const float* const* srcs, const int* src_channels, int n_src, const float* wpack,
-                               const float* bias, int cout, int ks, int h, int w, int epilogue, int act,
-                               const float* aux0, const float* aux1, const float* disp_range, int n_range,
-                               float* out0, float* out1, effi_stream_t stream) {
+// bt == nullptr: the single-image entry
+static int conv2d_f32_impl(const float* const* srcs, const int* src_channels, int n_src, const float* wpack,
+                           const float* bias, int cout, int ks, int h, int w, int epilogue, int act,
+                           const float* aux0, const float* aux1, const float* disp_range, int n_range,
+                           float* out0, float* out1, const ConvBatch* bt, effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack || !bias || !out0) return EFFI_ERR_BADARG;
     if (cout < 1 || h < 1 || w < 1 || (ks != 1 && ks != 3)) return EFFI_ERR_BADARG;
     Conv2dArgs a;
@@ -1855,6 +1940,26 @@ extern "C" int effi_conv2d_f32(const float* const* srcs, const int* src_channels
     a.win = w;
     const int nt = (cout + 15) / 16;
     hipStream_t st = effi_s(stream);
+    if (bt) {                                  // several images: the epilogues of the feature pyramid
+        if (cout == 1 && ks == 3 && (long)h * w >= 262144) return EFFI_ERR_UNSUPPORTED;        // (the vector-ALU kernel's territory)
+        switch (epilogue) {
+            case EFFI_EPI_PLAIN:
+                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
+                return ks == 3 ? dispatch_nt_batch<3, EFFI_EPI_PLAIN>(a, *bt, nt, st) : dispatch_nt_batch<1, EFFI_EPI_PLAIN>(a, *bt, nt, st);
+            case EFFI_EPI_ADD_UP2:
+                if (ks != 1 || !aux0 || (h & 1) || (w & 3)) return EFFI_ERR_BADARG;
+                return dispatch_nt_batch<1, EFFI_EPI_ADD_UP2>(a, *bt, nt, st);
+            case EFFI_EPI_NHWC:
+                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH || (w & 3)) return EFFI_ERR_BADARG;
+                return ks == 3 ? dispatch_nt_batch<3, EFFI_EPI_NHWC>(a, *bt, nt, st) : dispatch_nt_batch<1, EFFI_EPI_NHWC>(a, *bt, nt, st);
+            case EFFI_EPI_GRU_ZR:
+            case EFFI_EPI_GRU_Q:
+            case EFFI_EPI_HEAD:
+                return EFFI_ERR_UNSUPPORTED;
+            default:
+                return EFFI_ERR_BADARG;
+        }
+    }
     if (cout == 1 && ks == 3 && (long)h * w >= 262144 && (epilogue == EFFI_EPI_PLAIN || epilogue == EFFI_EPI_HEAD)) {
         // single output channel on a large map: vector-ALU kernel (an MFMA tile would be 15/16 padding);
         // it reads plain [cin][9] weights that the host appends behind the packed block (packing.py).
@@ -1897,6 +2002,26 @@ extern "C" int effi_conv2d_f32(const float* const* srcs, const int* src_channels
             return EFFI_ERR_BADARG;
     }
 }
+
+extern "C" int effi_conv2d_f32(const float* const* srcs, const int* src_channels, int n_src, const float* wpack,
+                               const float* bias, int cout, int ks, int h, int w, int epilogue, int act,
+                               const float* aux0, const float* aux1, const float* disp_range, int n_range,
+                               float* out0, float* out1, effi_stream_t stream) {
+    return conv2d_f32_impl(srcs, src_channels, n_src, wpack, bias, cout, ks, h, w, epilogue, act, aux0, aux1, disp_range, n_range, out0,
+                           out1, nullptr, stream);
+}
+
+extern "C" int effi_conv2d_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const float* wpack,
+                                     const float* bias, int cout, int ks, int h, int w, int epilogue, int act,
+                                     const float* aux0, const float* aux1, const float* disp_range, int n_range,
+                                     float* out0, float* out1, int n_img, const long* src_istride, long aux0_istride,
+                                     long out0_istride, effi_stream_t stream) {
+    if (n_src < 1 || n_src > EFFI_MAX_SRC) return EFFI_ERR_BADARG;
+    ConvBatch b;
+    if (!fill_conv_batch(b, n_img, src_istride, n_src, aux0_istride, out0_istride)) return EFFI_ERR_BADARG;
+    return conv2d_f32_impl(srcs, src_channels, n_src, wpack, bias, cout, ks, h, w, epilogue, act, aux0, aux1, disp_range, n_range, out0,
+                           out1, n_img > 1 ? &b : nullptr, stream);
+}
 #endif
 
 // ---- 5x5 stride-2 convolution (feature pyramid down-sampling) ---------------------------------------------------
@@ -1916,9 +2041,26 @@ static int dispatch_k5s2(const Conv2dArgs& a, hipStream_t st) {
     return al ? launch_k5s2<NT, 1, true>(a, st) : launch_k5s2<NT, 1, false>(a, st);
 }
 
+// Batched form: the same rule on the tile count of all images (bitwise the single-image result: see launch2d_batch).
+template <int NT, int MR, bool ALIGNED>
+static int launch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
+    hipLaunchKernelGGL((conv2d_mfma_v2_batch_kernel<5, NT, MR, EFFI_EPI_PLAIN, 4, ALIGNED, 2>), dim3(ntiles, b.n_img), dim3(256), 0, st, a, b,
+                       tiles_x, ntiles);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+template <int NT>
+static int dispatch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    const long cols = effi_cdiv(a.w, 16);
+    const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
+    if (cols * effi_cdiv(a.h, 8) * b.n_img >= 512) return al ? launch_k5s2_batch<NT, 2, true>(a, b, st) : launch_k5s2_batch<NT, 2, false>(a, b, st);
+    return al ? launch_k5s2_batch<NT, 1, true>(a, b, st) : launch_k5s2_batch<NT, 1, false>(a, b, st);
+}
+
 #ifndef EFFI_BF16_ONLY
-extern "C" int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int hin,
-                                    int win, int act, float* out, effi_stream_t stream) {
+static int conv2d_k5s2_f32_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int hin,
+                                int win, int act, float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack || !bias || !out || cin < 1 || cout < 1 || hin < 1 || win < 1) return EFFI_ERR_BADARG;
     if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
     Conv2dArgs a;
@@ -1945,12 +2087,33 @@ extern "C" int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack
     a.ostride = (long)a.h * a.w;
     a.zcount = 0;
     hipStream_t st = effi_s(stream);
+    if (bt) {
+        switch ((cout + 15) / 16) {
+            case 1: return dispatch_k5s2_batch<1>(a, *bt, st);
+            case 2: return dispatch_k5s2_batch<2>(a, *bt, st);
+            case 4: return dispatch_k5s2_batch<4>(a, *bt, st);
+            default: return EFFI_ERR_UNSUPPORTED;
+        }
+    }
     switch ((cout + 15) / 16) {
         case 1: return dispatch_k5s2<1>(a, st);
         case 2: return dispatch_k5s2<2>(a, st);
         case 4: return dispatch_k5s2<4>(a, st);
         default: return EFFI_ERR_UNSUPPORTED;
     }
+}
+
+extern "C" int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int hin,
+                                    int win, int act, float* out, effi_stream_t stream) {
+    return conv2d_k5s2_f32_impl(in, cin, wpack, bias, cout, hin, win, act, out, nullptr, stream);
+}
+
+extern "C" int effi_conv2d_k5s2_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int hin,
+                                          int win, int act, float* out, int n_img, long in_istride, long out_istride,
+                                          effi_stream_t stream) {
+    ConvBatch b;
+    if (!fill_conv_batch(b, n_img, &in_istride, 1, 0, out_istride)) return EFFI_ERR_BADARG;
+    return conv2d_k5s2_f32_impl(in, cin, wpack, bias, cout, hin, win, act, out, n_img > 1 ? &b : nullptr, stream);
 }
 #endif
 
@@ -1965,8 +2128,10 @@ extern "C" int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack
 namespace {
 // KS = 3 with ZB: the stride-(2,2,2) 3-D convolution of the U-Net (conv2 / conv4) as z-batched stride-2 2-D convolutions: blockIdx.z =
 // output plane z, chunk = (input plane 2z + dz - 1, octet), 9 taps = 3 K-steps per chunk; a.cin = channels per plane.
-template <int KS, int NT, int MR, bool ZB>
-__global__ __launch_bounds__(256) void conv2d_s2_bf16x3_kernel(const Conv2dArgs a, int tiles_x, int ntiles) {
+// BATCH (2-D form only): the workgroup's logical tile is ``btile`` (conv2d_s2_bf16x3_batch_kernel), else it comes from blockIdx.x.
+template <int KS, int NT, int MR, bool ZB, bool BATCH = false>
+__device__ __forceinline__ void conv2d_s2_bf16x3_tile(const Conv2dArgs a, int tiles_x, int ntiles, int btile = 0) {
+    static_assert(!(BATCH && ZB), "blockIdx.z is the plane of the z-batched form and the image of the batched one");
     constexpr int PAD = KS / 2, NTAP = KS * KS;
     constexpr int TR = 4 * MR, IR = 2 * TR + KS - 2, NQ = 10, NSLOT = 20, NKS = (NTAP + 3) / 4;
     constexpr int ROWE = 2 * NSLOT * 8;                                // bf16 elements per staged input row (both parities)
@@ -1981,7 +2146,7 @@ __global__ __launch_bounds__(256) void conv2d_s2_bf16x3_kernel(const Conv2dArgs 
     const int li = lane & 15, lk = lane >> 4;
     const int h = a.h, w = a.w, hin = a.hin, win = a.win;
     const long hw = (long)h * w;
-    const int tile = effi_xcd_remap(blockIdx.x, gridDim.x);
+    const int tile = BATCH ? btile : effi_xcd_remap(blockIdx.x, gridDim.x);
     if (tile >= ntiles) return;
     const int ty_ = tile / tiles_x;
     const int x0 = (tile - ty_ * tiles_x) * 16, y0 = ty_ * TR;
@@ -2101,6 +2266,20 @@ __global__ __launch_bounds__(256) void conv2d_s2_bf16x3_kernel(const Conv2dArgs 
     }
 }
 
+template <int KS, int NT, int MR, bool ZB>
+__global__ __launch_bounds__(256) void conv2d_s2_bf16x3_kernel(const Conv2dArgs a, int tiles_x, int ntiles) {
+    conv2d_s2_bf16x3_tile<KS, NT, MR, ZB>(a, tiles_x, ntiles);
+}
+
+// n_img images in one launch of the 2-D form (ConvBatch, conv2d_x3.hpp): grid (ntiles, ngroups, n_img) -- blockIdx.z, the plane of
+// the z-batched form, is free here.  The XCD remap runs over images x tiles.
+template <int KS, int NT, int MR>
+__global__ __launch_bounds__(256) void conv2d_s2_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    const int t = effi_xcd_remap(blockIdx.z * gridDim.x + blockIdx.x, gridDim.x * gridDim.z);
+    const int img = t / ntiles;
+    conv2d_s2_bf16x3_tile<KS, NT, MR, false, true>(conv_batch_image(a, b, img), tiles_x, ntiles, t - img * ntiles);
+}
+
 }  // namespace
 
 template <int KS, int NT, bool ZB>
@@ -2117,8 +2296,23 @@ static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st) {
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
-extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
-                                           int win, int act, float* out, effi_stream_t stream) {
+// Batched 2-D form: the rows-per-wave rule on the workgroup count of all images (bitwise the single-image result: the accumulation
+// order of a pixel is (octet, K-step, hi/lo term) for either tile height).
+template <int KS, int NT>
+static int launch_s2_x3_batch(const Conv2dArgs& a, const ConvBatch& b, int ngroups, hipStream_t st) {
+    const int cols = effi_cdiv(a.w, 16);
+    if ((long)cols * effi_cdiv(a.h, 8) * ngroups * b.n_img >= 400) {
+        const int ntiles = cols * effi_cdiv(a.h, 8);
+        hipLaunchKernelGGL((conv2d_s2_bf16x3_batch_kernel<KS, NT, 2>), dim3(ntiles, ngroups, b.n_img), dim3(256), 0, st, a, b, cols, ntiles);
+    } else {
+        const int ntiles = cols * effi_cdiv(a.h, 4);
+        hipLaunchKernelGGL((conv2d_s2_bf16x3_batch_kernel<KS, NT, 1>), dim3(ntiles, ngroups, b.n_img), dim3(256), 0, st, a, b, cols, ntiles);
+    }
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+static int conv2d_k5s2_x3_impl(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
+                               int win, int act, float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack_bf16 || !bias || !out || cin < 1 || cout < 1 || hin < 1 || win < 1) return EFFI_ERR_BADARG;
     if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
     if ((win & 3) || cout > 128) return EFFI_ERR_UNSUPPORTED;
@@ -2149,8 +2343,22 @@ extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32)(const float* in, int cin, co
     a.zcount = a.zin = 0;
     hipStream_t st = effi_s(stream);
     const int nt = (cout + 15) / 16;
+    if (bt) return nt == 1 ? launch_s2_x3_batch<5, 1>(a, *bt, 1, st) : launch_s2_x3_batch<5, 2>(a, *bt, (nt + 1) / 2, st);
     if (nt == 1) return launch_s2_x3<5, 1, false>(a, 1, st);
     return launch_s2_x3<5, 2, false>(a, (nt + 1) / 2, st);   // weights packed in groups of two N-tiles (zero-padded)
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
+                                           int win, int act, float* out, effi_stream_t stream) {
+    return conv2d_k5s2_x3_impl(in, cin, wpack_bf16, bias, cout, hin, win, act, out, nullptr, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32_batch)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout,
+                                                 int hin, int win, int act, float* out, int n_img, long in_istride,
+                                                 long out_istride, effi_stream_t stream) {
+    ConvBatch b;
+    if (!fill_conv_batch(b, n_img, &in_istride, 1, 0, out_istride)) return EFFI_ERR_BADARG;
+    return conv2d_k5s2_x3_impl(in, cin, wpack_bf16, bias, cout, hin, win, act, out, n_img > 1 ? &b : nullptr, stream);
 }
 
 extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
@@ -2242,10 +2450,11 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_pair_f32)(const float* const* srcs_
     }
 }
 
-extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
-                                         const float* bias, int cout, int h, int w, int epilogue, int act, const float* aux0,
-                                         const float* aux1, const float* disp_range, int n_range, float* out0, float* out1,
-                                         effi_stream_t stream) {
+// bt == nullptr: the single-image entry
+static int conv2d_k3_x3_impl(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                             const float* bias, int cout, int h, int w, int epilogue, int act, const float* aux0,
+                             const float* aux1, const float* disp_range, int n_range, float* out0, float* out1,
+                             const ConvBatch* bt, effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack_bf16 || !bias || !out0) return EFFI_ERR_BADARG;
     if (cout < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (w & 3) return EFFI_ERR_UNSUPPORTED;                 // rows must be float4-aligned (callers fall back to the fp32 kernel)
@@ -2278,6 +2487,26 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_f32)(const float* const* srcs, cons
     a.zcount = 0;
     const int nt = (cout + 15) / 16;
     hipStream_t st = effi_s(stream);
+    if (bt) {                                  // several images: the epilogues of the feature pyramid
+        switch (epilogue) {
+            case EFFI_EPI_PLAIN:
+                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
+                return dispatch_bf16x3_batch<EFFI_EPI_PLAIN>(a, *bt, nt, st);
+            case EFFI_EPI_NHWC:
+                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
+                return dispatch_bf16x3_batch<EFFI_EPI_NHWC>(a, *bt, nt, st);
+            case EFFI_EPI_ADD_SHUF2:
+            case EFFI_EPI_NHWC_ADD_SHUF2:
+                if (!aux0 || (h & 1) || (w & 1) || act != EFFI_ACT_NONE) return EFFI_ERR_BADARG;
+                if (nt == 1) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3_batch<1, EFFI_EPI_ADD_SHUF2>(a, *bt, st)
+                                                                   : launch_bf16x3_batch<1, EFFI_EPI_NHWC_ADD_SHUF2>(a, *bt, st);
+                if (nt == 2) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3_batch<2, EFFI_EPI_ADD_SHUF2>(a, *bt, st)
+                                                                   : launch_bf16x3_batch<2, EFFI_EPI_NHWC_ADD_SHUF2>(a, *bt, st);
+                return EFFI_ERR_UNSUPPORTED;
+            default:
+                return EFFI_ERR_UNSUPPORTED;
+        }
+    }
     switch (epilogue) {
         case EFFI_EPI_PLAIN:
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
@@ -2308,6 +2537,26 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_f32)(const float* const* srcs, cons
         default:
             return EFFI_ERR_UNSUPPORTED;
     }
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                         const float* bias, int cout, int h, int w, int epilogue, int act, const float* aux0,
+                                         const float* aux1, const float* disp_range, int n_range, float* out0, float* out1,
+                                         effi_stream_t stream) {
+    return conv2d_k3_x3_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, h, w, epilogue, act, aux0, aux1, disp_range, n_range, out0,
+                             out1, nullptr, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_f32_batch)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                               const float* bias, int cout, int h, int w, int epilogue, int act, const float* aux0,
+                                               const float* aux1, const float* disp_range, int n_range, float* out0, float* out1,
+                                               int n_img, const long* src_istride, long aux0_istride, long out0_istride,
+                                               effi_stream_t stream) {
+    if (n_src < 1 || n_src > EFFI_MAX_SRC) return EFFI_ERR_BADARG;
+    ConvBatch b;
+    if (!fill_conv_batch(b, n_img, src_istride, n_src, aux0_istride, out0_istride)) return EFFI_ERR_BADARG;
+    return conv2d_k3_x3_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, h, w, epilogue, act, aux0, aux1, disp_range, n_range, out0,
+                             out1, n_img > 1 ? &b : nullptr, stream);
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k3_k1_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
@@ -2380,7 +2629,13 @@ struct ConvTwiceArgs {
     const float* zeros;
 };
 
-__global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwiceArgs a, int tiles_x, int ntiles) {
+// BATCH: n_img images of ntiles tiles each (image i of src / out lies i * istride / i * ostride floats behind image 0): the persistent
+// walk covers the n_img * ntiles (image, tile) pairs -- a workgroup's contiguous run may cross from one image into the next, a tile
+// never spans two -- and the image's base pointers are derived per tile.  The arithmetic of a tile is untouched.
+// (A template of the KERNEL, not a body shared by two kernels: wrapped into a device function the single-image form took 160 instead of
+// 132 registers.)
+template <bool BATCH>
+__global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwiceArgs a, int tiles_x, int ntiles, int n_img, long istride, long ostride) {
     // ROW-PAIR operands (both layers have at most 8 output channels): MFMA rows 0-7 = the channels of an image row, rows 8-15 = the
     // same channels of the row below, K = (dy in 0..3, dx) over the 4 x 3 window both rows see = 12 taps = exactly 3 K-steps for TWO
     // rows (packing.pack_conv2d_bf16x3_oct: W[j][e][dy][dx] for rows j < 8, zero at dy = 3; W[j-8][e][dy-1][dx] for j >= 8, zero at dy = 0)
@@ -2403,8 +2658,9 @@ __global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwic
     const long hw = (long)h * w;
     // persistent workgroups: a contiguous run of tiles each (neighbouring tiles share their halos in the same XCD's L2); the next
     // tile's input is requested before the current tile is multiplied, the weights are fetched once
-    const int per = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = effi_xcd_remap(blockIdx.x, gridDim.x) * per, t1 = min(t0 + per, ntiles);
+    const int nall = BATCH ? n_img * ntiles : ntiles;
+    const int per = (nall + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int t0 = effi_xcd_remap(blockIdx.x, gridDim.x) * per, t1 = min(t0 + per, nall);
     if (t0 >= t1) return;
 
     {
@@ -2422,11 +2678,17 @@ __global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwic
     const int emax = a.cin - 1;
     f32x4 pa[8];
     auto prefetch = [&](int tile) {
+        const float* src = a.src;
+        if constexpr (BATCH) {
+            const int img = tile / ntiles;
+            tile -= img * ntiles;
+            src += (long)img * istride;
+        }
         const int ty_ = tile / tiles_x;
         const int x0 = (tile - ty_ * tiles_x) * TW, y0 = ty_ * TR;
         const int sgy = y0 - 2 + srow, sgx = x0 - 4 + 4 * sqx;
         const bool s_in = (sgy >= 0) & (sgy < h) & (sgx >= 0) & (sgx < w);
-        const float* q = s_in ? a.src + ((long)sgy * w + sgx) : a.zeros;
+        const float* q = s_in ? src + ((long)sgy * w + sgx) : a.zeros;
         const long step = s_in ? hw : 0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -2464,8 +2726,15 @@ __global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwic
     if (stager) prefetch(t0);
 #pragma unroll 1
     for (int tile = t0; tile < t1; ++tile) {
-        const int ty_ = tile / tiles_x;
-        const int x0 = (tile - ty_ * tiles_x) * TW, y0 = ty_ * TR;
+        int ltile = tile;
+        float* outp = a.out;
+        if constexpr (BATCH) {
+            const int img = tile / ntiles;
+            ltile -= img * ntiles;
+            outp += (long)img * ostride;
+        }
+        const int ty_ = ltile / tiles_x;
+        const int x0 = (ltile - ty_ * tiles_x) * TW, y0 = ty_ * TR;
         if (stager) {
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
@@ -2544,17 +2813,19 @@ __global__ __launch_bounds__(256) void conv2d_k3_twice_oct_kernel(const ConvTwic
                 const long pix = (long)y * w + x;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (co0 + r < a.cout) a.out[(long)(co0 + r) * hw + pix] = fmaxf(acc[m][r] + bb[r], 0.0f);
+                    if (co0 + r < a.cout) outp[(long)(co0 + r) * hw + pix] = fmaxf(acc[m][r] + bb[r], 0.0f);
             }
         }
     }
 }
 
+
 }  // namespace
 
-extern "C" int EFFI_FN(effi_conv2d_k3_twice_bf16x3_f32)(const float* in, int cin, const void* w1_bf16, const float* bias1,
-                                               const void* w2_bf16, const float* bias2, int cout, int h, int w, float* out,
-                                               effi_stream_t stream) {
+// n_img == 1: the single-image entry
+static int conv2d_k3_twice_impl(const float* in, int cin, const void* w1_bf16, const float* bias1, const void* w2_bf16,
+                                const float* bias2, int cout, int h, int w, float* out, int n_img, long in_istride, long out_istride,
+                                effi_stream_t stream) {
     if (!in || !w1_bf16 || !bias1 || !w2_bf16 || !bias2 || !out || cin < 1 || cout < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if ((w & 3) || cin > 8 || cout > 8) return EFFI_ERR_UNSUPPORTED;
     ConvTwiceArgs a;
@@ -2565,9 +2836,30 @@ extern "C" int EFFI_FN(effi_conv2d_k3_twice_bf16x3_f32)(const float* in, int cin
     a.zeros = effi_zero_page();
     if (!a.zeros) return EFFI_ERR_WORKSPACE;
     const int tiles_x = effi_cdiv(w, 16), ntiles = tiles_x * effi_cdiv(h, 16);
+    if (n_img > 1) {
+        if ((long)n_img * ntiles > 0x7fffffffL || in_istride < 0 || out_istride < 0) return EFFI_ERR_BADARG;
+        const long nall = (long)n_img * ntiles;
+        const int nwg = nall < 1024 ? (int)nall : 1024;
+        hipLaunchKernelGGL(conv2d_k3_twice_oct_kernel<true>, dim3(nwg), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles, n_img, in_istride,
+                           out_istride);
+        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    }
     const int nwg = ntiles < 1024 ? ntiles : 1024;         // 4 persistent workgroups per CU (38 KB of LDS each)
-    hipLaunchKernelGGL(conv2d_k3_twice_oct_kernel, dim3(nwg), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles);
+    hipLaunchKernelGGL(conv2d_k3_twice_oct_kernel<false>, dim3(nwg), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles, 1, 0L, 0L);
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k3_twice_bf16x3_f32)(const float* in, int cin, const void* w1_bf16, const float* bias1,
+                                               const void* w2_bf16, const float* bias2, int cout, int h, int w, float* out,
+                                               effi_stream_t stream) {
+    return conv2d_k3_twice_impl(in, cin, w1_bf16, bias1, w2_bf16, bias2, cout, h, w, out, 1, 0, 0, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv2d_k3_twice_bf16x3_f32_batch)(const float* in, int cin, const void* w1_bf16, const float* bias1,
+                                                     const void* w2_bf16, const float* bias2, int cout, int h, int w, float* out,
+                                                     int n_img, long in_istride, long out_istride, effi_stream_t stream) {
+    if (n_img < 1) return EFFI_ERR_BADARG;
+    return conv2d_k3_twice_impl(in, cin, w1_bf16, bias1, w2_bf16, bias2, cout, h, w, out, n_img, in_istride, out_istride, stream);
 }
 
 extern "C" int EFFI_FN(effi_encoder_tail_bf16x3_f32)(const float* cor1, const float* dfm1, int hd, const void* wc2_bf16, const float* bias_c2,

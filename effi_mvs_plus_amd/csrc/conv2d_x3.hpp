@@ -86,6 +86,27 @@ struct Conv2dArgs {
     int aux_q4;              // SR GRU epilogues: aux0 / aux1 / out0 are [channels/4][h][w][4] fp32 maps (EFFI_EPI_Q4)
 };
 
+// Image batch of a launch (the *_batch entries: the feature pyramid's layers over all views at once).  Image i of a tensor starts
+// i * stride floats behind image 0; a stride of 0 shares one tensor between all images (the constant "ones" plane of the pyramid's
+// split last head).  Weights, bias and the zero page are shared.  A workgroup derives its image from the grid and offsets its
+// pointers ONCE (conv_batch_image); everything behind that is the single-image kernel body, so image i of a batched launch has
+// exactly the bits of the single-image launch on image i.  Passed as its own kernel argument: Conv2dArgs and with it every
+// single-image kernel stay as they are.
+struct ConvBatch {
+    int n_img;
+    long src[EFFI_MAX_SRC];  // image stride of each source, in floats
+    long aux0;               // ... of aux0 (ADD_UP2: the coarser map, ADD_SHUF2: the pixel-shuffled map)
+    long out0;               // ... of out0
+};
+
+__device__ __forceinline__ Conv2dArgs conv_batch_image(Conv2dArgs a, const ConvBatch& b, int img) {
+#pragma unroll
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) a.src[i] += (long)img * b.src[i];
+    a.aux0 += (long)img * b.aux0;            // (never dereferenced where the entry takes no aux0: its stride is 0 then)
+    a.out0 += (long)img * b.out0;
+    return a;
+}
+
 // GENERATED inputs of the encoder's convc2 / convd2 (models/update.py:86-91): instead of reading relu(convc1(GetCost(inv_depth))) /
 // relu(convd1(inv_depth)) as maps that another launch wrote, the convolution's workgroup evaluates them for its own tile (+ halo)
 // straight into the LDS image -- from the inverse-depth map and the stage's two cached volumes (a few values per pixel).  The
@@ -299,7 +320,8 @@ __device__ __forceinline__ void split_octet(const f32x4 (&pa)[8], int px, bf16x8
 // per CU six waves per SIMD instead of four, and half the L2 -> LDS weight traffic).
 // GEN (with SR): the A image is generated (EncGenArgs); gmode (workgroup-uniform) 0 = relu(convc1(GetCost(inv_depth))), 1 =
 // relu(convd1(inv_depth)) (7x7) -- ONE instantiation for both so that the two halves of the pair kernel share their LDS.
-template <int NT, int MR, int EPI, bool ZB, bool WIDE, bool SR = false, int NW = 4, bool GEN = false>
+// REMAP = false: ``bid`` already is the logical tile (batched launches remap over images x tiles themselves).
+template <int NT, int MR, int EPI, bool ZB, bool WIDE, bool SR = false, int NW = 4, bool GEN = false, bool REMAP = true>
 __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int tiles_x, int ntiles, int bid, int nbid, int bidy,
                                                       const EncGenArgs* gp = nullptr, int gmode = 0) {
     constexpr int NTHR = NW * 64;
@@ -334,7 +356,7 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
     const int li = lane & 15, lk = lane >> 4;
     const int h = a.h, w = a.w;
     const long hw = (long)h * w;
-    const int tile = effi_xcd_remap(bid, nbid);
+    const int tile = REMAP ? effi_xcd_remap(bid, nbid) : bid;
     if (tile >= ntiles) return;
     const int ty_ = tile / tiles_x;
     const int x0 = kHead ? (tile - ty_ * tiles_x) * (TW - 2) - 1 : (tile - ty_ * tiles_x) * TW, y0 = kHead ? ty_ * (TR - 2) - 1 : ty_ * TR;
@@ -1076,6 +1098,16 @@ __global__ __launch_bounds__(NW * 64) void conv2d_k3_bf16x3_pair_kernel(const Co
     else conv2d_k3_bf16x3_tile<NT, MR, EFFI_EPI_PLAIN, false, WIDE, SR, NW>(a1, tiles_x, ntiles, blockIdx.x, gridDim.x, 0);
 }
 
+// n_img images in one launch (planar fp32 sources): grid (ntiles, n_img).  The XCD remap runs over the whole images x tiles index
+// space, so every XCD owns a contiguous run of tiles of (mostly) one image; a tile never spans two images.
+template <int NT, int MR, int EPI, bool WIDE>
+__global__ __launch_bounds__(256) void conv2d_k3_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    const int t = effi_xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    const int img = t / ntiles;
+    conv2d_k3_bf16x3_tile<NT, MR, EPI, false, WIDE, false, 4, false, false>(conv_batch_image(a, b, img), tiles_x, ntiles, t - img * ntiles,
+                                                                           ntiles, 0);
+}
+
 // convc2 | convd2 with GENERATED inputs (EncGenArgs): blockIdx.y = 0 -> relu(convc2(relu(convc1(GetCost(inv_depth))))),
 // 1 -> relu(convd2(relu(convd1(inv_depth)))); split-resident outputs.  Replaces encoder_inputs + the pair launch.
 template <int NT, int MR, bool WIDE>
@@ -1144,6 +1176,48 @@ static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
     else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
     else hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 1, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+// Batched form (conv2d_k3_bf16x3_batch_kernel): the rule of launch_bf16x3 on the tile count of ALL images -- what was an under-filled
+// one-row launch per image becomes one launch of larger tiles.  A pixel's accumulation order (chunk, K-step, hi/lo term) does not
+// depend on the tile shape, so the result is bitwise the single-image one whatever shape either rule picks.
+template <int NT, int EPI>
+static int launch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    const long cols = effi_cdiv(a.w, 16);
+    const long t4 = cols * effi_cdiv(a.h, 16) * b.n_img, t2 = cols * effi_cdiv(a.h, 8) * b.n_img;
+    int mr;
+    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
+    else if (t2 >= effi_mr2_min()) mr = 2;
+    else mr = 1;
+    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
+    if (force) mr = (int)force;
+    if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
+    const long wide_env = effi_opt_or(EFFI_OPT_WIDE_TILES, -1);
+    const bool wide = wide_env >= 0 ? wide_env != 0 : (mr == 4 && a.w >= 512);
+    const int tiles_x = wide ? effi_cdiv(a.w, 16 * mr) : (int)cols, ntiles = tiles_x * effi_cdiv(a.h, wide ? 4 : 4 * mr);
+    const dim3 grid(ntiles, (unsigned)b.n_img);
+    if (wide) {
+        if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 4, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+        else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 2, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+        else hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 1, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+    } else {
+        if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 4, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+        else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 2, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+        else hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 1, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+    }
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+template <int EPI>
+static int dispatch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, int nt, hipStream_t st) {
+    switch (nt) {
+        case 1: return launch_bf16x3_batch<1, EPI>(a, b, st);
+        case 2: return launch_bf16x3_batch<2, EPI>(a, b, st);
+        case 3: return launch_bf16x3_batch<3, EPI>(a, b, st);
+        case 4: return launch_bf16x3_batch<4, EPI>(a, b, st);
+        case 6: return launch_bf16x3_batch<6, EPI>(a, b, st);
+        default: return EFFI_ERR_UNSUPPORTED;
+    }
 }
 
 // One-launch depth head (EFFI_EPI_K1HEAD, split-resident input): workgroups of ``tile`` = 2 (8 x 16 pixels, four waves), 4 (16 x 16,

@@ -535,6 +535,17 @@ class Effi_MVS_plus(nn.Module):
             # pyramid passes is part of the result
             features = [self.feature(imgs[:, v]) for v in range(n_views)]
             return self.forward_hot(features, self.cnet_depth(imgs[:, 0]), proj_matrices, depth_values)
+        if ops.option("fpn_batch") != 0:
+            # all N views (of all B samples) are ONE batched pass of the feature pyramid (same module, same weights: the views are the
+            # batch); the context net runs once beside it -- on the side stream with branches on.  Bitwise the per-view passes below.
+            B = imgs.size(0)
+            with ops.Branch() as br:
+                cnet_depth = self.cnet_depth(imgs[:, 0])
+            flat = self.feature(imgs.flatten(0, 1))
+            br.join(*cnet_depth.values())
+            per_view = {k: t_.unflatten(0, (B, n_views)) for k, t_ in flat.items()}
+            features = [{k: t_[:, v] for k, t_ in per_view.items()} for v in range(n_views)]
+            return self.forward_hot(features, cnet_depth, proj_matrices, depth_values)
         features = [None] * n_views
         with ops.Branch() as br:
             for v in range(1, n_views, 2):

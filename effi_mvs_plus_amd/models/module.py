@@ -297,7 +297,8 @@ class P_1to8_FeatureNet_Fast(nn.Module):
         raise NotImplementedError("feature pyramid: only 3x3/s1/p1 and 5x5/s2/p2 blocks are instantiated on the HIP path")
 
     def run(self, img):
-        """img planar [3,H,W] (H, W multiples of 8, W/2 multiple of 4) -> {stageK: [C,h,w]}."""
+        """img planar [3,H,W] (H, W multiples of 8, W/2 multiple of 4) -> {stageK: [C,h,w]}, or an image batch [n,3,H,W] ->
+        {stageK: [n,C,h,w]}: the same layers, every launch covering all n images.  Image i of the batch is bitwise ``run(img[i])``."""
         _require_eval(self)
         x = img
         c0 = list(self.conv0)
@@ -317,11 +318,12 @@ class P_1to8_FeatureNet_Fast(nn.Module):
             levels.append(x)
         l1, l2, top = levels
         cl = self.channels_last_outputs and img.shape[-1] % 32 == 0
+        chw = (2, 0, 1) if img.dim() == 3 else (0, 3, 1, 2)      # a channel-last result [..,h,w,C] presented as [..,C,h,w]
 
         def head(name, conv, x, ks):
             w, b = self._pk(name, conv)
             if cl:      # [h,w,C] in memory, presented as [C,h,w]
-                return ops.conv2d([x], w, b, conv.out_channels, ks, epilogue=ops.EPI_NHWC).permute(2, 0, 1)
+                return ops.conv2d([x], w, b, conv.out_channels, ks, epilogue=ops.EPI_NHWC).permute(*chw)
             return ops.conv2d([x], w, b, conv.out_channels, ks)
 
         out = {"stage1": head("out1", self.out1, top, 1)}
@@ -329,8 +331,8 @@ class P_1to8_FeatureNet_Fast(nn.Module):
         top = ops.conv2d([l2], w, b, self.inner1.out_channels, 1, epilogue=ops.EPI_ADD_UP2, aux0=top)
         out["stage2"] = head("out2", self.out2, top, 3)
         co3 = self.out3.out_channels
-        if (ops.uses_split() and self.out3.bias is None and self.out3.kernel_size == (3, 3) and co3 <= 16 and l1.shape[0] % 8 == 0
-                and top.shape[0] % 8 == 0 and l1.shape[-1] % 4 == 0 and top.shape[-1] % 4 == 0 and l1.shape[-2] % 2 == 0
+        if (ops.uses_split() and self.out3.bias is None and self.out3.kernel_size == (3, 3) and co3 <= 16 and l1.shape[-3] % 8 == 0
+                and top.shape[-3] % 8 == 0 and l1.shape[-1] % 4 == 0 and top.shape[-1] % 4 == 0 and l1.shape[-2] % 2 == 0
                 and ops.option("fpn_split_head") != 0):
             # the last head without its 64-channel full-resolution input: the upsampled branch is evaluated at half resolution
             # (4 parity groups of output channels), the lateral branch with out3 o inner2 composed (packing.pack_fpn_head_split)
@@ -341,9 +343,10 @@ class P_1to8_FeatureNet_Fast(nn.Module):
             if ones is None:
                 ones = self._ones.setdefault((top.device, top.shape[-2], top.shape[-1]),
                                              torch.ones(1, top.shape[-2], top.shape[-1], device=top.device, dtype=torch.float32))
+            # (``ones`` stays ONE plane for every image of a batch: the stride-0 source)
             u = ops.conv2d_k3_bf16x3([top, ones], wu, bu, 4 * co3)
             o3 = ops.conv2d_k3_bf16x3([l1], wl, bl, co3, epilogue=ops.EPI_NHWC_ADD_SHUF2 if cl else ops.EPI_ADD_SHUF2, aux0=u)
-            out["stage3"] = o3.permute(2, 0, 1) if cl else o3
+            out["stage3"] = o3.permute(*chw) if cl else o3
             return out
         w, b = self._pk("inner2", self.inner2)
         top = ops.conv2d([l1], w, b, self.inner2.out_channels, 1, epilogue=ops.EPI_ADD_UP2, aux0=top)
@@ -371,6 +374,12 @@ class P_1to8_FeatureNet_Fast(nn.Module):
             # the CPU, tools/diag_fpn.py)
             from .. import train_path
             return train_path.feature_pyramid(self, x)
+        if ops.option("fpn_batch") != 0 and x.shape[0] > 1:
+            # all images in one pass of batched launches (the views of a forward are the batch); bitwise the loop below.  Option
+            # fpn_batch: 0 = the loop, 1 = the measured rule, 2 = every level batched -- the rule IS "every level" (full batching was
+            # the fastest form at both measured sizes, the full-resolution block included: profiles/fpn_batch_ab.txt), so 1 and 2
+            # coincide until a measurement says otherwise
+            return self.run(x if x[0].is_contiguous() else x.contiguous())
         outs = [self.run(x[i].contiguous()) for i in range(x.shape[0])]
         return {k: _stack([o[k] for o in outs]) for k in outs[0]}
 

@@ -104,7 +104,12 @@ _PY_OPTION_DEFAULTS = {"warp_x3": 0, "state_q4": 1, "c1k7_mfma": 1, "k5s2_split"
                        # BasicUpdateBlock.head_fused_tile finds it faster, 2 = everywhere); head_fused_tile: 0 = that rule, else the tile
                        # (2 / 4 / 8, effi_depth_head_bf16x3_sr); clear_fused: SR border clear inside the context split; setup_fused:
                        # hypotheses + relative projections in one launch; conf_fused: full-size confidence written by the soft-argmin
-                       "head_fused": 1, "head_fused_tile": 0, "clear_fused": 1, "setup_fused": 1, "conf_fused": 1}
+                       "head_fused": 1, "head_fused_tile": 0, "clear_fused": 1, "setup_fused": 1, "conf_fused": 1,
+                       # the feature pyramid over all images of a call in batched launches (module.P_1to8_FeatureNet_Fast; bitwise the same
+                       # for every value): 0 = one pass per image, 1 = the measured rule, 2 = every level batched.  Measured
+                       # (profiles/fpn_batch_ab.txt): every level batched is the fastest form at 576x800 and at 1184x1600, so the rule is
+                       # "every level" and 1 == 2 today
+                       "fpn_batch": 1}
 _PY_OPTS = {k: int(os.environ.get("EFFI_" + k.upper(), v)) for k, v in _PY_OPTION_DEFAULTS.items()}
 LIB_OPTIONS = ("warp_lds_kb", "dyn_form", "dyn_setup_exact", "dyn_xchg", "pixnet_mfma", "force_mr", "mr4_min", "mr4_nt2_max", "mr2_min",
                "wide_tiles", "roll_mr", "roll_zt", "roll_rp", "deconv_mr", "sr_waves", "enc_gen_mr3", "c3_lean", "dyn_win")
@@ -1152,8 +1157,118 @@ def conv2d_k3_bf16x3_pair(srcs_a, wpack_a, bias_a, srcs_b, wpack_b, bias_b, cout
     return out_a, out_b
 
 
+def _images(tensors, name):
+    """Image-batch form of a convolution's tensors -> (n, image strides in floats); n is None when every tensor is 3-D (the
+    single-image call).  A 4-D tensor is [n,C,h,w] with contiguous images at ANY uniform image stride (a slice of a larger batch is
+    fine); a 3-D one beside it is shared by all images (stride 0)."""
+    n, strides = None, []
+    for t in tensors:
+        _t(t, name, contiguous=False)
+        if t.dim() == 4:
+            if n is None:
+                n = t.shape[0]
+            elif t.shape[0] != n:
+                raise ValueError(f"{name}: image counts differ ({n} and {t.shape[0]})")
+            if n < 1 or not t[0].is_contiguous():
+                raise ValueError(f"{name}: every image of a batch must be contiguous (the image stride itself is free)")
+            strides.append(t.stride(0) if n > 1 else 0)
+        elif t.dim() == 3:
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: must be contiguous")
+            strides.append(0)
+        else:
+            raise ValueError(f"{name}: expected [C,h,w] or [n,C,h,w], got {tuple(t.shape)}")
+    return n, strides
+
+
+def _long_array(vals):
+    return (C.c_long * len(vals))(*[int(v) for v in vals])
+
+
+def _batch_out(out, shape, dev, name):
+    """Output of a batched convolution: allocated [n, ...], or the caller's (images contiguous, uniform image stride)."""
+    if out is None:
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    _t(out, name, contiguous=False)
+    if tuple(out.shape) != tuple(shape) or not out[0].is_contiguous() or (shape[0] > 1 and out.stride(0) < out[0].numel()):
+        raise ValueError(f"{name}: expected {tuple(shape)} with contiguous, non-overlapping images")
+    return out
+
+
+def _batch_aux(aux0, n, name):
+    """aux0 of a batched convolution, [n, ...] -> its image stride."""
+    if aux0 is None:
+        return 0
+    _t(aux0, name, contiguous=False)
+    if aux0.dim() != 4 or aux0.shape[0] != n:
+        raise ValueError(f"{name}: expected [n, ...] with n = {n}, got {tuple(aux0.shape)}")
+    if not aux0[0].is_contiguous():
+        raise ValueError(f"{name}: every image of a batch must be contiguous")
+    return aux0.stride(0) if n > 1 else 0
+
+
+def _conv2d_batch(n, istr, srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, split):
+    """``conv2d`` / ``conv2d_k3_bf16x3`` on n images in one launch (effi_conv2d_f32_batch / effi_conv2d_k3_bf16x3_f32_batch)."""
+    h, w = srcs[0].shape[-2:]
+    dev = srcs[0].device
+    for s in srcs:
+        if tuple(s.shape[-2:]) != (h, w):
+            raise ValueError(f"conv2d: every source of a batch must be {h} x {w}, got {tuple(s.shape)}")
+    if n > 1 and aux1 is not None and (aux1.dim() != 4 or aux1.shape[0] != n):
+        # (aux1 has no image stride in the library: the epilogues that read it are single-image only)
+        raise ValueError(f"conv2d: aux1 of a batch must be [n, ...] with n = {n}")
+    if epilogue == EPI_GRU_ZR:
+        shape = (n, cout // 2, h, w)
+    elif epilogue == EPI_HEAD:
+        shape = (n, 1, h, w)
+    elif epilogue in (EPI_NHWC, EPI_NHWC_ADD_SHUF2):
+        shape = (n, h, w, cout)
+    else:
+        shape = (n, cout, h, w)
+    out0 = _batch_out(out0, shape, dev, "conv2d output")
+    if out1 is None and epilogue in (EPI_GRU_ZR, EPI_HEAD):
+        out1 = torch.empty(shape, device=dev, dtype=torch.float32)
+    if epilogue in (EPI_ADD_SHUF2, EPI_NHWC_ADD_SHUF2) and (aux0 is None or tuple(aux0.shape[1:]) != (4 * cout, h // 2, w // 2) or h % 2 or w % 2):
+        raise ValueError("conv2d_k3_bf16x3: the pixel-shuffled map must be [n, 4*cout, h/2, w/2]")
+    if epilogue == EPI_ADD_UP2 and (aux0 is None or tuple(aux0.shape[1:]) != (cout, h // 2, w // 2)):
+        raise ValueError("conv2d: the coarser map must be [n, cout, h/2, w/2]")
+    aux_stride = _batch_aux(aux0, n, "conv2d aux0")
+    cin = sum(s.shape[-3] for s in srcs)
+    chans = _int_array([s.shape[-3] for s in srcs])
+    work = lambda: {"flops": 2.0 * n * h * w * cin * cout * ks * ks, "bytes": 4.0 * n * h * w * (cin + cout)}
+    n_range = 0 if disp_range is None else disp_range.numel()
+    tail = (n, _long_array(istr), aux_stride, out0.stride(0) if n > 1 else 0, _stream())
+    if split:
+        check(_call(f"conv2d_k3x3_nt{(cout + 15) // 16}_epi{epilogue}_batch", work, _x3("effi_conv2d_k3_bf16x3_f32_batch"), _ptr_array(srcs),
+                    chans, len(srcs), _p(wpack), _p(bias), cout, h, w, epilogue, act, _p(aux0), _p(aux1), None, 0, _p(out0), _p(out1),
+                    *tail), "effi_conv2d_k3_bf16x3_f32_batch")
+    else:
+        check(_call(f"conv2d_k{ks}_nt{(cout + 15) // 16}_epi{epilogue}_batch", work, _lib.lib().effi_conv2d_f32_batch, _ptr_array(srcs),
+                    chans, len(srcs), _p(wpack), _p(bias), cout, ks, h, w, epilogue, act, _p(aux0), _p(aux1), _p(disp_range), n_range,
+                    _p(out0), _p(out1), *tail), "effi_conv2d_f32_batch")
+    return (out0, out1) if out1 is not None else out0
+
+
+def _conv2d_takes_split(srcs, wpack, ks, epilogue):
+    """Whether ``conv2d`` hands this call to the split-precision 3x3 entry: ONE predicate for the single-image and the batched call, so
+    that image i of a batch always runs the arithmetic of the 3-D call on image i."""
+    return (uses_split() and wpack.wx is not None and ks == 3 and srcs[0].shape[-1] % 4 == 0
+            and epilogue in (EPI_PLAIN, EPI_NHWC, EPI_GRU_ZR, EPI_GRU_Q)
+            and all(s.shape[-3] % 8 == 0 for s in srcs[:-1]))
+
+
 def conv2d(srcs, wpack, bias, cout, ks, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=None, aux1=None, disp_range=None,
            out0=None, out1=None):
+    """2-D convolution (ks 1 or 3) of the concatenated planar sources [C,h,w].  Image batch: sources [n,C,h,w] (all the same n; a
+    3-D source beside them is shared by all images), ``aux0`` [n,...], outputs [n,...] -- ONE launch, image i bitwise the 3-D call
+    on image i (epilogues PLAIN, NHWC, ADD_UP2; the library reports UNSUPPORTED for the others when n > 1)."""
+    n, istr = _images(srcs, "conv2d input") if any(s.dim() == 4 for s in srcs) else (None, None)
+    if n is not None:
+        if hasattr(wpack, "w32"):
+            if _conv2d_takes_split(srcs, wpack, ks, epilogue):
+                return _conv2d_batch(n, istr, srcs, wpack.wx, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
+            wpack = wpack.w32
+        return _conv2d_batch(n, istr, srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, False)
     for s in srcs:
         _t(s, "conv2d input")
     h, w = srcs[0].shape[-2:]
@@ -1174,9 +1289,7 @@ def conv2d(srcs, wpack, bias, cout, ks, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=N
     n_range = 0 if disp_range is None else disp_range.numel()
     cin = sum(s.shape[0] for s in srcs)
     if hasattr(wpack, "w32"):                 # packing.Conv2dWeights: both operand orders, pick the arithmetic here
-        if (uses_split() and wpack.wx is not None and ks == 3 and w % 4 == 0
-                and epilogue in (EPI_PLAIN, EPI_NHWC, EPI_GRU_ZR, EPI_GRU_Q)
-                and all(s.shape[0] % 8 == 0 for s in srcs[:-1])):
+        if _conv2d_takes_split(srcs, wpack, ks, epilogue):
             return conv2d_k3_bf16x3(srcs, wpack.wx, bias, cout, epilogue=epilogue, act=act, aux0=aux0, aux1=aux1,
                                     out0=out0, out1=out1)
         wpack = wpack.w32
@@ -1190,7 +1303,11 @@ def conv2d(srcs, wpack, bias, cout, ks, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=N
 def conv2d_k3_bf16x3(srcs, wpack, bias, cout, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=None, aux1=None, out0=None, out1=None):
     """3x3 convolution in split precision (hi*hi + hi*lo + lo*hi on the bf16 MFMA, fp32 accumulate); ``wpack`` from
     ``packing.pack_conv2d_bf16x3``.  Same sources / epilogues as ``conv2d`` (PLAIN, NHWC, GRU_ZR, GRU_Q); w % 4 == 0 and every
-    source but the last has a multiple of 8 channels (otherwise the library reports UNSUPPORTED)."""
+    source but the last has a multiple of 8 channels (otherwise the library reports UNSUPPORTED).  Image batch as ``conv2d``
+    (epilogues PLAIN, NHWC, ADD_SHUF2, NHWC_ADD_SHUF2 for n > 1)."""
+    if any(s.dim() == 4 for s in srcs):
+        n, istr = _images(srcs, "conv2d input")
+        return _conv2d_batch(n, istr, srcs, wpack, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
     for s in srcs:
         _t(s, "conv2d input")
     h, w = srcs[0].shape[-2:]
@@ -1564,7 +1681,16 @@ def conv2d_k3_k1_x3(srcs, wpack, bias, cout1, extra, w2pack, bias2, cout2, relu=
 
 def conv2d_k3_twice(x, w1, b1, w2, b2, cout, out=None):
     """relu(conv3x3(relu(conv3x3(x)))) with at most 8 channels into each layer (8 between them) in one kernel, the intermediate map
-    in LDS (``packing.pack_conv2d_bf16x3_oct`` weights): the pyramid's full-resolution block.  x [cin<=8,h,w] -> [cout<=8,h,w]."""
+    in LDS (``packing.pack_conv2d_bf16x3_oct`` weights): the pyramid's full-resolution block.  x [cin<=8,h,w] -> [cout<=8,h,w], or
+    an image batch [n,cin,h,w] -> [n,cout,h,w] in one launch (image i bitwise the 3-D call on image i)."""
+    if x.dim() == 4:
+        n, (istr,) = _images([x], "conv input")
+        _, cin, h, w = x.shape
+        out = _batch_out(out, (n, cout, h, w), x.device, "conv output")
+        work = lambda: {"flops": 2.0 * n * h * w * 9 * (cin * 8 + 8 * cout), "bytes": 4.0 * n * h * w * (cin + cout)}
+        check(_call("conv2d_k3_twice_batch", work, _x3("effi_conv2d_k3_twice_bf16x3_f32_batch"), _p(x), cin, _p(w1), _p(b1), _p(w2), _p(b2),
+                    cout, h, w, _p(out), n, istr, out.stride(0) if n > 1 else 0, _stream()), "effi_conv2d_k3_twice_bf16x3_f32_batch")
+        return out
     _t(x, "conv input")
     cin, h, w = x.shape
     if out is None:
@@ -1612,7 +1738,24 @@ def conv2d_k3_k1_up2x(srcs, wpack, bias, cout1, w2pack, bias2, inv_depth, disp_r
 
 
 def conv2d_k5s2(x, wpack, bias, cout, act=ACT_RELU):
-    """5x5 stride-2 pad-2 convolution (+bias, activation): x planar [cin,hin,win] -> [cout,ceil(hin/2),ceil(win/2)]."""
+    """5x5 stride-2 pad-2 convolution (+bias, activation): x planar [cin,hin,win] -> [cout,ceil(hin/2),ceil(win/2)], or an image
+    batch [n,cin,hin,win] -> [n,cout,...] in one launch (image i bitwise the 3-D call on image i)."""
+    if x.dim() == 4:
+        n, (istr,) = _images([x], "conv input")
+        _, cin, hin, win = x.shape
+        ho, wo = (hin - 1) // 2 + 1, (win - 1) // 2 + 1
+        out = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
+        work = lambda: {"flops": 2.0 * n * ho * wo * cin * cout * 25, "bytes": 4.0 * n * (hin * win * cin + ho * wo * cout)}
+        tail = (cout, hin, win, act, _p(out), n, istr, out.stride(0) if n > 1 else 0, _stream())
+        if hasattr(wpack, "w32"):
+            if uses_split() and wpack.wx is not None and win % 4 == 0 and _PY_OPTS["k5s2_split"] != 0:
+                check(_call(f"conv2d_k5s2x3_nt{(cout + 15) // 16}_batch", work, _x3("effi_conv2d_k5s2_bf16x3_f32_batch"), _p(x), cin,
+                            _p(wpack.wx), _p(bias), *tail), "effi_conv2d_k5s2_bf16x3_f32_batch")
+                return out
+            wpack = wpack.w32
+        check(_call(f"conv2d_k5s2_nt{(cout + 15) // 16}_batch", work, _lib.lib().effi_conv2d_k5s2_f32_batch, _p(x), cin, _p(wpack), _p(bias),
+                    *tail), "effi_conv2d_k5s2_f32_batch")
+        return out
     _t(x, "conv input")
     cin, hin, win = x.shape
     ho, wo = (hin - 1) // 2 + 1, (win - 1) // 2 + 1

@@ -368,6 +368,38 @@ int effi_conv2d_k3_bf16x3_f32(const float* const* srcs, const int* src_channels,
  * bias [16*ceil(cout/16)]; out planar [cout][(hin-1)/2+1][(win-1)/2+1] = act(conv + bias).  cout <= 64. */
 int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack, const float* bias, int cout,
                          int hin, int win, int act, float* out, effi_stream_t stream);
+/* ---- Image batches of the feature pyramid's convolutions (suffix _batch): n_img images in ONE launch.
+ * models/module.py:346-412 takes [B,3,H,W]; here all N views of a forward are the batch.  Arguments as the entry without the
+ * suffix, followed by n_img and one image stride per tensor, in floats: image i of a tensor starts i * stride behind the pointer
+ * given (image 0).  src_istride has n_src entries; a stride may be 0 (one tensor shared by all images, e.g. the constant "ones"
+ * plane of the pyramid's split last head).  aux0_istride belongs to aux0 (EPI_ADD_UP2: the coarser map; EPI_ADD_SHUF2 /
+ * EPI_NHWC_ADD_SHUF2: the pixel-shuffled map; otherwise ignored), out0_istride to out0.  Weights and bias are shared.
+ * Image i of the result is BITWISE what the single-image entry computes on image i; the tile shape is chosen from the tile count
+ * of all images.  n_img == 1 is the single-image launch itself.  For n_img > 1: epilogues PLAIN, NHWC, ADD_UP2 (fp32 entry),
+ * ADD_SHUF2 / NHWC_ADD_SHUF2 (split entry), the channel counts of the single-image entry; everything else (GRU_ZR, GRU_Q, HEAD,
+ * the single-channel head on large maps) returns EFFI_ERR_UNSUPPORTED.  n_img <= 65535. */
+int effi_conv2d_f32_batch(const float* const* srcs, const int* src_channels, int n_src,
+                          const float* wpack, const float* bias, int cout, int ks, int h, int w,
+                          int epilogue, int act, const float* aux0, const float* aux1,
+                          const float* disp_range, int n_range, float* out0, float* out1,
+                          int n_img, const long* src_istride, long aux0_istride, long out0_istride, effi_stream_t stream);
+int effi_conv2d_k3_bf16x3_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                    const float* bias, int cout, int h, int w, int epilogue, int act,
+                                    const float* aux0, const float* aux1, const float* disp_range, int n_range,
+                                    float* out0, float* out1, int n_img, const long* src_istride, long aux0_istride,
+                                    long out0_istride, effi_stream_t stream);
+/* in [n_img] x [cin][hin][win] at in_istride, out [n_img] x [cout][ho][wo] at out_istride. */
+int effi_conv2d_k5s2_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout,
+                               int hin, int win, int act, float* out, int n_img, long in_istride, long out_istride,
+                               effi_stream_t stream);
+int effi_conv2d_k5s2_bf16x3_f32_batch(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
+                                      int win, int act, float* out, int n_img, long in_istride, long out_istride,
+                                      effi_stream_t stream);
+/* The persistent two-layer kernel over n_img images: its workgroups walk the n_img x tiles index space, a tile never spans two
+ * images. */
+int effi_conv2d_k3_twice_bf16x3_f32_batch(const float* in, int cin, const void* w1_bf16, const float* bias1, const void* w2_bf16,
+                                          const float* bias2, int cout, int h, int w, float* out, int n_img, long in_istride,
+                                          long out_istride, effi_stream_t stream);
 /* 7x7, one input channel (convd1, models/update.py:76,90): in [h][w]; weight [49][cout]
  * (host-packed), bias [cout]; out planar [cout][h][w] = relu(conv + bias).  cout in {16,32,48}. */
 int effi_conv2d_c1k7_relu_f32(const float* in, const float* weight, const float* bias, int cout,
@@ -659,6 +691,17 @@ int effi_conv2d_k5s2_bf16x3_f32_bf16(const float* in, int cin, const void* wpack
                                 int act, float* out, effi_stream_t stream);
 int effi_conv2d_k3_twice_bf16x3_f32_bf16(const float* in, int cin, const void* w1_bf16, const float* bias1, const void* w2_bf16,
                                     const float* bias2, int cout, int h, int w, float* out, effi_stream_t stream);
+int effi_conv2d_k3_bf16x3_f32_batch_bf16(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                    const float* bias, int cout, int h, int w, int epilogue, int act,
+                                    const float* aux0, const float* aux1, const float* disp_range, int n_range,
+                                    float* out0, float* out1, int n_img, const long* src_istride, long aux0_istride,
+                                    long out0_istride, effi_stream_t stream);
+int effi_conv2d_k5s2_bf16x3_f32_batch_bf16(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
+                                      int win, int act, float* out, int n_img, long in_istride, long out_istride,
+                                      effi_stream_t stream);
+int effi_conv2d_k3_twice_bf16x3_f32_batch_bf16(const float* in, int cin, const void* w1_bf16, const float* bias1, const void* w2_bf16,
+                                          const float* bias2, int cout, int h, int w, float* out, int n_img, long in_istride,
+                                          long out_istride, effi_stream_t stream);
 int effi_encoder_tail_bf16x3_f32_bf16(const float* cor1, const float* dfm1, int hd, const void* wc2_bf16, const float* bias_c2,
                                  const void* wd2_bf16, const float* bias_d2, const void* wd_bf16, const float* bias_d, int cmix,
                                  const float* extra, int c_extra, const void* w2pack_bf16, const float* bias2, int cout2, int h,
