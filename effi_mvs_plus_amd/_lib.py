@@ -94,6 +94,23 @@ SIGNATURES = {
     "effi_conv2d_k5s2_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _l, _l, _vp],
     "effi_conv2d_k5s2_bf16x3_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _l, _l, _vp],
     "effi_conv2d_k3_twice_bf16x3_f32_batch": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _l, _l, _vp],
+    # sample batches of the stage-1 cost volume: the single-sample arguments + n_smp and the sample strides
+    "effi_compose_rel_proj_f32_batch": [_vp, _i, _vp, _i, _l, _l, _vp],
+    "effi_cascade_setup_f32_batch": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _l, _l, _l, _vp, _l, _vp],
+    "effi_warpcorr_views_f32_batch": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _i, _l, _l, _l, _l, _l, _l, _vp],
+    "effi_warpcorr_views_x3_f32_batch": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _i, _i, _l, _l, _l, _l, _l, _l, _vp],
+    "effi_view_aggregate_f32_batch": [_vp, _vp, _i, _i, _i, _vp, _i, _l, _l, _l, _vp],
+    "effi_softmax_regress_conf_f32_batch": [_vp, _vp, _l, _l, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _l, _l, _l, _l, _l, _l, _vp],
+    "effi_softmax_regress_conf_up_f32_batch": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _l, _l, _l, _l, _l, _l,
+                                               _l, _vp],
+    "effi_conv3d_k3_f32_batch": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l, _l, _vp],
+    "effi_deconv3d_k3_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _l, _l, _l, _vp],
+    "effi_conv3d_k3s1_mfma_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _l, _l, _vp],
+    "effi_conv3d_k3s2_mfma_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _l, _l, _vp],
+    "effi_conv3d_k3s1_bf16x3_f32_batch": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp],
+    "effi_conv3d_k3s1_roll_bf16x3_f32_batch": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp],
+    "effi_conv3d_k3s2_bf16x3_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _l, _l, _vp],
+    "effi_deconv3d_k3s2_bf16x3_f32_batch": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _l, _l, _l, _vp],
     "effi_encoder_tail_bf16x3_f32": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp],
     # split-resident maps of the update block
     "effi_sr_geometry": [_i, _i, _vp, _vp],
@@ -136,6 +153,8 @@ BF16X3_ENTRIES = ("effi_conv2d_k3_bf16x3_pair_f32", "effi_conv2d_k3_bf16x3_f32",
                   "effi_conv3d_k3s1_roll_bf16x3_pair_f32", "effi_csp_gen_roll_bf16x3_pair_f32", "effi_deconv3d_k3s2_bf16x3_f32", "effi_encoder_tail_bf16x3_f32", "effi_conv2d_k3_twice_bf16x3_f32",
                   "effi_conv2d_k5s2_bf16x3_f32", "effi_conv3d_k3s2_bf16x3_f32",
                   "effi_conv2d_k3_bf16x3_f32_batch", "effi_conv2d_k5s2_bf16x3_f32_batch", "effi_conv2d_k3_twice_bf16x3_f32_batch",
+                  "effi_conv3d_k3s1_bf16x3_f32_batch", "effi_conv3d_k3s1_roll_bf16x3_f32_batch", "effi_conv3d_k3s2_bf16x3_f32_batch",
+                  "effi_deconv3d_k3s2_bf16x3_f32_batch",
                   "effi_conv2d_k3_bf16x3_sr", "effi_conv2d_k3_bf16x3_pair_sr", "effi_conv2d_k3_k1_bf16x3_sr", "effi_conv2d_k3_k1_up2x_bf16x3_sr",
                   "effi_encoder_pair_gen_bf16x3_sr", "effi_gru_zr_q_fused_bf16x3_sr", "effi_depth_head_bf16x3_sr")
 for _n in BF16X3_ENTRIES:

@@ -1072,6 +1072,12 @@ __global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_kernel(const Conv2d
     conv3d_roll_rp_bf16x3_body<NOCT, MR>(a, tiles_x, ntiles, zt);
 }
 
+// n_smp samples in one launch: blockIdx.z = sample (ConvBatch, conv2d_x3.hpp)
+template <int NOCT, int MR>
+__global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles, int zt) {
+    conv3d_roll_rp_bf16x3_body<NOCT, MR>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, zt);
+}
+
 template <int NOCT, int MR>
 __global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_pair_kernel(const Conv2dArgs a, const Conv2dArgs b, int tiles_x, int ntiles,
                                                                          int zt) {
@@ -1334,6 +1340,12 @@ __global__ __launch_bounds__(256) void conv3d_roll_bf16x3_kernel(const Conv2dArg
     conv3d_roll_bf16x3_body<NOCT, NT, MR>(a, tiles_x, ntiles, zt);
 }
 
+// n_smp samples in one launch: blockIdx.z = sample (ConvBatch, conv2d_x3.hpp)
+template <int NOCT, int NT, int MR>
+__global__ __launch_bounds__(256) void conv3d_roll_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles, int zt) {
+    conv3d_roll_bf16x3_body<NOCT, NT, MR>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, zt);
+}
+
 // Two independent convolutions of the same shape in one launch (blockIdx.z picks the argument set): conv1 of the two
 // cross-scale blocks of a stage.
 template <int NOCT, int NT, int MR>
@@ -1397,7 +1409,7 @@ __host__ __device__ constexpr int deconv_slot_half(int pzy, int s) {       // fr
 }
 
 template <int MR, bool ALIGNED, bool HALF>
-__global__ __launch_bounds__(256) void deconv3d_s2_bf16x3_kernel(const DeconvArgs a, int tiles_x, int tiles_xy) {
+__device__ __forceinline__ void deconv3d_s2_bf16x3_body(const DeconvArgs a, int tiles_x, int tiles_xy) {
     constexpr int TR = 4 * MR, AR = TR + 1, AW = 20, AQ = 5, APIX = AR * AW, NQ = APIX / 4;
     constexpr int NITEMS = 4 * NQ;                                     // (octet, plane, pixel quad)
     constexpr int NP = HALF ? 4 : 8;                                    // parity tiles
@@ -1583,6 +1595,20 @@ __global__ __launch_bounds__(256) void deconv3d_s2_bf16x3_kernel(const DeconvArg
             }
         }
     }
+}
+
+template <int MR, bool ALIGNED, bool HALF>
+__global__ __launch_bounds__(256) void deconv3d_s2_bf16x3_kernel(const DeconvArgs a, int tiles_x, int tiles_xy) {
+    deconv3d_s2_bf16x3_body<MR, ALIGNED, HALF>(a, tiles_x, tiles_xy);
+}
+// n_smp samples in one launch: grid (tiles, D, n_smp), blockIdx.z = sample; the body's (z, tile) order runs inside a sample
+template <int MR, bool ALIGNED, bool HALF>
+__global__ __launch_bounds__(256) void deconv3d_s2_bf16x3_batch_kernel(const DeconvArgs a, long in_ss, long skip_ss, long out_ss, int tiles_x,
+                                                                       int tiles_xy) {
+    const long smp = blockIdx.z;
+    const DeconvArgs c{a.in + smp * in_ss, a.wpack, a.bias, a.skip ? a.skip + smp * skip_ss : nullptr, a.zeros, a.out + smp * out_ss,
+                       a.cin,  a.cout, a.D, a.h, a.w, a.relu};
+    deconv3d_s2_bf16x3_body<MR, ALIGNED, HALF>(c, tiles_x, tiles_xy);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1790,27 +1816,57 @@ int dispatch_nt(const Conv2dArgs& a, int nt, hipStream_t st) {
 }  // namespace
 
 // ---- 3-D convolution (k3, stride 1, pad 1) as z-batched 2-D convolutions on the matrix cores -----------------
+// Sample batch of a z-batched launch (the 3-D *_batch entries; ConvBatch, conv2d_x3.hpp): grid (ntiles, planes, n_smp), blockIdx.z =
+// sample.  The tile body takes its tile from blockIdx.x and its plane from blockIdx.y exactly as in the single-sample launch.
+namespace {
+template <int NT, int MR, bool ALIGNED, int S>
+__global__ __launch_bounds__(256) void conv3d_planes_mfma_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    // (one tensor behind all three plane sources, no aux0: the sample offset is one product for the input and one for the output)
+    Conv2dArgs c = a;
+    const float* in = a.src[0] + (long)blockIdx.z * b.src[0];
+#pragma unroll
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) c.src[i] = in;
+    c.out0 = a.out0 + (long)blockIdx.z * b.out0;
+    conv2d_mfma_v2_tile<3, NT, MR, EFFI_EPI_PLAIN, 8, false, ALIGNED, S>(c, tiles_x, ntiles);
+}
+}  // namespace
+
 template <int NT, int MR, bool ALIGNED>
-static int launch3d_planes(const Conv2dArgs& a, hipStream_t st) {
+static int launch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
     const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
+    if (bt)
+        hipLaunchKernelGGL((conv3d_planes_mfma_batch_kernel<NT, MR, ALIGNED, 1>), dim3(ntiles, a.zcount, bt->n_img), dim3(256), 0, st, a,
+                           *bt, tiles_x, ntiles);
+    else
     hipLaunchKernelGGL((conv2d_mfma_v2_kernel<3, NT, MR, EFFI_EPI_PLAIN, 8, false, ALIGNED>), dim3(ntiles, a.zcount), dim3(256), 0, st,
                        a, tiles_x, ntiles);
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
+// (batched: the rule on the workgroups of all samples; a pixel's accumulation order does not depend on the rows per wave)
 template <int NT>
-static int dispatch3d_planes(const Conv2dArgs& a, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
+static int dispatch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * (bt ? bt->n_img : 1);
     const bool al = (a.w & 3) == 0;
     // rows per wave: keep >= 2 workgroups per CU over all planes
-    if (cols * effi_cdiv(a.h, 16) * a.zcount >= 512) return al ? launch3d_planes<NT, 4, true>(a, st) : launch3d_planes<NT, 4, false>(a, st);
-    if (cols * effi_cdiv(a.h, 8) * a.zcount >= 512) return al ? launch3d_planes<NT, 2, true>(a, st) : launch3d_planes<NT, 2, false>(a, st);
-    return al ? launch3d_planes<NT, 1, true>(a, st) : launch3d_planes<NT, 1, false>(a, st);
+    if (cols * effi_cdiv(a.h, 16) * planes >= 512) return al ? launch3d_planes<NT, 4, true>(a, st, bt) : launch3d_planes<NT, 4, false>(a, st, bt);
+    if (cols * effi_cdiv(a.h, 8) * planes >= 512) return al ? launch3d_planes<NT, 2, true>(a, st, bt) : launch3d_planes<NT, 2, false>(a, st, bt);
+    return al ? launch3d_planes<NT, 1, true>(a, st, bt) : launch3d_planes<NT, 1, false>(a, st, bt);
+}
+
+// the sample strides of a 3-D *_batch entry with ONE input tensor behind all three plane sources
+static bool fill_vol_batch(ConvBatch& b, int n_smp, long in_sstride, long out_sstride) {
+    if (n_smp < 1 || n_smp > 65535 || in_sstride < 0 || out_sstride < 0) return false;
+    b.n_img = n_smp;
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) b.src[i] = in_sstride;
+    b.aux0 = 0;
+    b.out0 = out_sstride;
+    return true;
 }
 
 #ifndef EFFI_BF16_ONLY
-extern "C" int effi_conv3d_k3s1_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
-                                         int h, int w, int relu, float* out, effi_stream_t stream) {
+static int conv3d_k3s1_mfma_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w, int relu,
+                                 float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack || !bias || !out || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (cout != 16 && cout != 32) return EFFI_ERR_UNSUPPORTED;
     Conv2dArgs a;
@@ -1836,30 +1892,45 @@ extern "C" int effi_conv3d_k3s1_mfma_f32(const float* in, int cin, const float* 
     a.zcount = a.zin = D;
     a.hin = h;
     a.win = w;
-    return cout == 16 ? dispatch3d_planes<1>(a, effi_s(stream)) : dispatch3d_planes<2>(a, effi_s(stream));
+    return cout == 16 ? dispatch3d_planes<1>(a, effi_s(stream), bt) : dispatch3d_planes<2>(a, effi_s(stream), bt);
+}
+extern "C" int effi_conv3d_k3s1_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
+                                         int h, int w, int relu, float* out, effi_stream_t stream) {
+    return conv3d_k3s1_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
+}
+extern "C" int effi_conv3d_k3s1_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h,
+                                               int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
+                                               effi_stream_t stream) {
+    ConvBatch b;
+    if (!fill_vol_batch(b, n_smp, in_sstride, out_sstride)) return EFFI_ERR_BADARG;
+    return conv3d_k3s1_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 #endif
 
 // Stride-2 form (models/module.py:442,445: conv2 8->16, conv4 16->32): output plane z reads input planes 2z-1, 2z, 2z+1.
 template <int NT, int MR, bool ALIGNED>
-static int launch3d_planes_s2(const Conv2dArgs& a, hipStream_t st) {
+static int launch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
     const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
+    if (bt)
+        hipLaunchKernelGGL((conv3d_planes_mfma_batch_kernel<NT, MR, ALIGNED, 2>), dim3(ntiles, a.zcount, bt->n_img), dim3(256), 0, st, a,
+                           *bt, tiles_x, ntiles);
+    else
     hipLaunchKernelGGL((conv2d_mfma_v2_kernel<3, NT, MR, EFFI_EPI_PLAIN, 8, false, ALIGNED, 2>), dim3(ntiles, a.zcount), dim3(256), 0,
                        st, a, tiles_x, ntiles);
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
 template <int NT>
-static int dispatch3d_planes_s2(const Conv2dArgs& a, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
+static int dispatch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * (bt ? bt->n_img : 1);
     const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (cols * effi_cdiv(a.h, 8) * a.zcount >= 512) return al ? launch3d_planes_s2<NT, 2, true>(a, st) : launch3d_planes_s2<NT, 2, false>(a, st);
-    return al ? launch3d_planes_s2<NT, 1, true>(a, st) : launch3d_planes_s2<NT, 1, false>(a, st);
+    if (cols * effi_cdiv(a.h, 8) * planes >= 512) return al ? launch3d_planes_s2<NT, 2, true>(a, st, bt) : launch3d_planes_s2<NT, 2, false>(a, st, bt);
+    return al ? launch3d_planes_s2<NT, 1, true>(a, st, bt) : launch3d_planes_s2<NT, 1, false>(a, st, bt);
 }
 
 #ifndef EFFI_BF16_ONLY
-extern "C" int effi_conv3d_k3s2_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
-                                         int h, int w, int relu, float* out, effi_stream_t stream) {
+static int conv3d_k3s2_mfma_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w, int relu,
+                                 float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack || !bias || !out || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (cout != 16 && cout != 32) return EFFI_ERR_UNSUPPORTED;
     Conv2dArgs a;
@@ -1886,7 +1957,18 @@ extern "C" int effi_conv3d_k3s2_mfma_f32(const float* in, int cin, const float* 
     a.out1 = nullptr;
     a.cstride = (long)D * h * w;
     a.ostride = (long)a.zcount * a.h * a.w;
-    return cout == 16 ? dispatch3d_planes_s2<1>(a, effi_s(stream)) : dispatch3d_planes_s2<2>(a, effi_s(stream));
+    return cout == 16 ? dispatch3d_planes_s2<1>(a, effi_s(stream), bt) : dispatch3d_planes_s2<2>(a, effi_s(stream), bt);
+}
+extern "C" int effi_conv3d_k3s2_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
+                                         int h, int w, int relu, float* out, effi_stream_t stream) {
+    return conv3d_k3s2_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
+}
+extern "C" int effi_conv3d_k3s2_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h,
+                                               int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
+                                               effi_stream_t stream) {
+    ConvBatch b;
+    if (!fill_vol_batch(b, n_smp, in_sstride, out_sstride)) return EFFI_ERR_BADARG;
+    return conv3d_k3s2_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 #endif
 
@@ -2130,7 +2212,7 @@ namespace {
 // output plane z, chunk = (input plane 2z + dz - 1, octet), 9 taps = 3 K-steps per chunk; a.cin = channels per plane.
 // BATCH (2-D form only): the workgroup's logical tile is ``btile`` (conv2d_s2_bf16x3_batch_kernel), else it comes from blockIdx.x.
 template <int KS, int NT, int MR, bool ZB, bool BATCH = false>
-__device__ __forceinline__ void conv2d_s2_bf16x3_tile(const Conv2dArgs a, int tiles_x, int ntiles, int btile = 0) {
+__device__ __forceinline__ void conv2d_s2_bf16x3_tile(const Conv2dArgs a, int tiles_x, int ntiles, int btile = 0, int zplane = -1) {
     static_assert(!(BATCH && ZB), "blockIdx.z is the plane of the z-batched form and the image of the batched one");
     constexpr int PAD = KS / 2, NTAP = KS * KS;
     constexpr int TR = 4 * MR, IR = 2 * TR + KS - 2, NQ = 10, NSLOT = 20, NKS = (NTAP + 3) / 4;
@@ -2155,7 +2237,7 @@ __device__ __forceinline__ void conv2d_s2_bf16x3_tile(const Conv2dArgs a, int ti
     const int noct = (a.cin + 7) >> 3;
     const int nchunks = ZB ? 3 * noct : noct;
     const int ngroups = gridDim.y;
-    const int zpl = ZB ? blockIdx.z : 0;
+    const int zpl = ZB ? (zplane >= 0 ? zplane : (int)blockIdx.z) : 0;   // (zplane: the sample batch of the z-batched form)
 
     f32x4 pa[NIT][8];
     auto prefetch = [&](int ch) {
@@ -2280,7 +2362,30 @@ __global__ __launch_bounds__(256) void conv2d_s2_bf16x3_batch_kernel(const Conv2
     conv2d_s2_bf16x3_tile<KS, NT, MR, false, true>(conv_batch_image(a, b, img), tiles_x, ntiles, t - img * ntiles);
 }
 
+// n_smp samples of the z-batched 3-D form in one launch: grid (ntiles, ngroups, planes * n_smp), blockIdx.z = sample * planes + plane.
+template <int NT, int MR>
+__global__ __launch_bounds__(256) void conv3d_s2_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    const int smp = (int)blockIdx.z / a.zcount;
+    conv2d_s2_bf16x3_tile<3, NT, MR, true>(conv_batch_image(a, b, smp), tiles_x, ntiles, 0, (int)blockIdx.z - smp * a.zcount);
+}
+
 }  // namespace
+
+// (the rows-per-wave rule of launch_s2_x3 on the workgroups of all samples: bitwise the single-sample result either way)
+template <int NT>
+static int launch_s2_x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, int ngroups, hipStream_t st) {
+    const int cols = effi_cdiv(a.w, 16);
+    const long planes = (long)a.zcount * b.n_img;
+    if (planes > 65535) return EFFI_ERR_UNSUPPORTED;
+    if ((long)cols * effi_cdiv(a.h, 8) * ngroups * planes >= 400) {
+        const int ntiles = cols * effi_cdiv(a.h, 8);
+        hipLaunchKernelGGL((conv3d_s2_bf16x3_batch_kernel<NT, 2>), dim3(ntiles, ngroups, (unsigned)planes), dim3(256), 0, st, a, b, cols, ntiles);
+    } else {
+        const int ntiles = cols * effi_cdiv(a.h, 4);
+        hipLaunchKernelGGL((conv3d_s2_bf16x3_batch_kernel<NT, 1>), dim3(ntiles, ngroups, (unsigned)planes), dim3(256), 0, st, a, b, cols, ntiles);
+    }
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
 
 template <int KS, int NT, bool ZB>
 static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st) {
@@ -2361,8 +2466,8 @@ extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32_batch)(const float* in, int c
     return conv2d_k5s2_x3_impl(in, cin, wpack_bf16, bias, cout, hin, win, act, out, n_img > 1 ? &b : nullptr, stream);
 }
 
-extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
-                                           int h, int w, int relu, float* out, effi_stream_t stream) {
+static int conv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h, int w, int relu,
+                               float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack_bf16 || !bias || !out || cin < 1 || cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if ((w & 3) || cout > 64) return EFFI_ERR_UNSUPPORTED;
     Conv2dArgs a;
@@ -2393,8 +2498,22 @@ extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32)(const float* in, int cin, co
     a.ostride = (long)a.zcount * a.h * a.w;
     hipStream_t st = effi_s(stream);
     const int nt = (cout + 15) / 16;
+    if (bt) return nt == 1 ? launch_s2_x3_zb_batch<1>(a, *bt, 1, st) : launch_s2_x3_zb_batch<2>(a, *bt, (nt + 1) / 2, st);
     if (nt == 1) return launch_s2_x3<3, 1, true>(a, 1, st);
     return launch_s2_x3<3, 2, true>(a, (nt + 1) / 2, st);
+}
+
+extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
+                                           int h, int w, int relu, float* out, effi_stream_t stream) {
+    return conv3d_k3s2_x3_impl(in, cin, wpack_bf16, bias, cout, D, h, w, relu, out, nullptr, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32_batch)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout,
+                                                          int D, int h, int w, int relu, float* out, int n_smp, long in_sstride,
+                                                          long out_sstride, effi_stream_t stream) {
+    ConvBatch b;
+    if (!fill_vol_batch(b, n_smp, in_sstride, out_sstride)) return EFFI_ERR_BADARG;
+    return conv3d_k3s2_x3_impl(in, cin, wpack_bf16, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 
 
@@ -2932,9 +3051,8 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_f32)(const float* const* sr
     }
 }
 
-extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
-                                           const float* bias, int cout, int D, int h, int w, int relu, float* out,
-                                           effi_stream_t stream) {
+static int conv3d_k3s1_x3_impl(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16, const float* bias,
+                               int cout, int D, int h, int w, int relu, float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack_bf16 || !bias || !out) return EFFI_ERR_BADARG;
     if (cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     Conv2dArgs a;                                          // any w: quads that straddle a row end are staged element by element
@@ -2965,14 +3083,30 @@ extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32)(const float* const* srcs, co
     a.zcount = D;
     hipStream_t st = effi_s(stream);
     switch ((cout + 15) / 16) {
-        case 1: return launch_bf16x3<1, EFFI_EPI_PLAIN, true>(a, st);
-        case 2: return launch_bf16x3<2, EFFI_EPI_PLAIN, true>(a, st);
+        case 1: return bt ? launch_bf16x3_zb_batch<1>(a, *bt, st) : launch_bf16x3<1, EFFI_EPI_PLAIN, true>(a, st);
+        case 2: return bt ? launch_bf16x3_zb_batch<2>(a, *bt, st) : launch_bf16x3<2, EFFI_EPI_PLAIN, true>(a, st);
         default: return EFFI_ERR_UNSUPPORTED;
     }
 }
 
+extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                           const float* bias, int cout, int D, int h, int w, int relu, float* out,
+                                           effi_stream_t stream) {
+    return conv3d_k3s1_x3_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, D, h, w, relu, out, nullptr, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32_batch)(const float* const* srcs, const int* src_channels, int n_src,
+                                                          const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
+                                                          int relu, float* out, int n_smp, const long* src_sstride, long out_sstride,
+                                                          effi_stream_t stream) {
+    ConvBatch b;
+    if (n_src < 1 || n_src > EFFI_MAX_SRC || !fill_conv_batch(b, n_smp, src_sstride, n_src, 0, out_sstride)) return EFFI_ERR_BADARG;
+    for (int i = n_src; i < EFFI_MAX_SRC; ++i) b.src[i] = b.src[0];          // unused sources alias source 0 (conv3d_k3s1_x3_impl)
+    return conv3d_k3s1_x3_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
+}
+
 template <int NOCT, int NT>
-static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pair = nullptr) {
+static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pair = nullptr, const ConvBatch* bt = nullptr) {
     // Rows per wave (MR) and planes per workgroup (ZT) from a small cost model fitted to sweeps at the cfg3 shapes
     // (tools/sweep_roll.sh): the chip holds 256 * occ workgroups at a time (occ from the LDS image / register count of the
     // instantiation), a launch takes ceil(workgroups / that) rounds, and a workgroup costs (ZT + 3) plane steps (3 ~ filling
@@ -2988,7 +3122,7 @@ static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pa
         const long tiles_m = (long)cols * effi_cdiv(a.h, 4 * m), slots = 256L * occ;
         for (int nz = 1; nz <= D; ++nz) {
             const int z = effi_cdiv(D, nz);
-            const long wgs = tiles_m * effi_cdiv(D, z) * (pair ? 2 : 1);
+            const long wgs = tiles_m * effi_cdiv(D, z) * (pair ? 2 : (bt ? bt->n_img : 1));     // (batched: the workgroups of all samples)
             const double cost = (double)effi_cdiv(wgs, slots) * (z + 3) * (m == 4 ? 1.3 : 1.0);
             if (cost < best - 1e-9) { best = cost; mr = m; zt = z; }
         }
@@ -2997,8 +3131,18 @@ static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pa
     if (fm != EFFI_OPT_UNSET) mr = (int)fm;
     if (fz != EFFI_OPT_UNSET) zt = (int)fz;
     const long tiles = (long)cols * effi_cdiv(a.h, 4 * mr);
-    const dim3 grid((unsigned)tiles, (unsigned)effi_cdiv(D, zt), pair ? 2 : 1);
+    const dim3 grid((unsigned)tiles, (unsigned)effi_cdiv(D, zt), pair ? 2 : (bt ? bt->n_img : 1));
     // (option roll_rp = 0, with packing.py: the one-row-per-tile operand, A/B runs)
+    if (bt) {               // a window's plane run and the rows per wave do not enter an output's accumulation order
+        if (rp) {
+            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_batch_kernel<NOCT, 4>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
+            else hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_batch_kernel<NOCT, 2>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
+        } else {
+            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_bf16x3_batch_kernel<NOCT, NT, 4>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
+            else hipLaunchKernelGGL((conv3d_roll_bf16x3_batch_kernel<NOCT, NT, 2>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
+        }
+        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    }
     if (rp) {
         if (pair) {
             if (mr == 4) hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_pair_kernel<NOCT, 4>), grid, dim3(256), 0, st, a, *pair, cols, (int)tiles, zt);
@@ -3051,16 +3195,31 @@ static int fill_roll_args(Conv2dArgs& a, const float* const* srcs, const int* sr
     return EFFI_OK;
 }
 
-extern "C" int EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src,
-                                                const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
-                                                int relu, float* out, effi_stream_t stream) {
+static int conv3d_roll_impl(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16, const float* bias,
+                            int cout, int D, int h, int w, int relu, float* out, const ConvBatch* bt, effi_stream_t stream) {
     Conv2dArgs a;
     const int rc = fill_roll_args(a, srcs, src_channels, n_src, wpack_bf16, bias, cout, D, h, w, relu, out);
     if (rc != EFFI_OK) return rc;
     hipStream_t st = effi_s(stream);
     const int nt = (cout + 15) / 16;
-    if (a.cin == 8) return nt == 1 ? launch_roll<1, 1>(a, st) : launch_roll<1, 2>(a, st);
-    return nt == 1 ? launch_roll<2, 1>(a, st) : launch_roll<2, 2>(a, st);
+    if (a.cin == 8) return nt == 1 ? launch_roll<1, 1>(a, st, nullptr, bt) : launch_roll<1, 2>(a, st, nullptr, bt);
+    return nt == 1 ? launch_roll<2, 1>(a, st, nullptr, bt) : launch_roll<2, 2>(a, st, nullptr, bt);
+}
+
+extern "C" int EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src,
+                                                const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
+                                                int relu, float* out, effi_stream_t stream) {
+    return conv3d_roll_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, D, h, w, relu, out, nullptr, stream);
+}
+
+extern "C" int EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_f32_batch)(const float* const* srcs, const int* src_channels, int n_src,
+                                                               const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
+                                                               int relu, float* out, int n_smp, const long* src_sstride,
+                                                               long out_sstride, effi_stream_t stream) {
+    ConvBatch b;
+    if (n_src < 1 || n_src > 2 || !fill_conv_batch(b, n_smp, src_sstride, n_src, 0, out_sstride)) return EFFI_ERR_BADARG;
+    if (n_src == 1) b.src[1] = b.src[0];                   // a single source is read through both pointers (fill_roll_args)
+    return conv3d_roll_impl(srcs, src_channels, n_src, wpack_bf16, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 
 extern "C" int EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_pair_f32)(const float* const* srcs_a, const void* wpack_a, const float* bias_a,
@@ -3098,8 +3257,9 @@ extern "C" int EFFI_FN(effi_csp_gen_roll_bf16x3_pair_f32)(const float* x, int D,
     return EFFI_OK;
 }
 
-extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
-                                             int h, int w, int relu, const float* skip, float* out, effi_stream_t stream) {
+static int deconv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
+                                 int relu, const float* skip, float* out, int n_smp, long in_ss, long skip_ss, long out_ss,
+                                 effi_stream_t stream) {
     if (!in || !wpack_bf16 || !bias || !out || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (cin < 16 || (cin & 15) || cout < 1 || cout > 16) return EFFI_ERR_UNSUPPORTED;
     DeconvArgs a;
@@ -3121,14 +3281,21 @@ extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32)(const float* in, int cin, 
     hipStream_t st = effi_s(stream);
     // rows per wave from the same rounds model as launch_roll: 256 * occ workgroups at a time (occ 5 / 3 with cout <= 8, 3 / 2
     // otherwise, for 1 / 2 rows per wave), a workgroup costs (rows per wave + 2); measured 16->8 into 48x148x200: 57 -> 43 us
-    const int occ1 = half ? 5 : 3, occ2 = half ? 3 : 2;
-    const long wg1 = (long)tiles_x * effi_cdiv(h, 4) * D, wg2 = (long)tiles_x * effi_cdiv(h, 8) * D;
+    // (the batched unaligned-row instantiation with cout <= 8 holds 4 workgroups per CU, not 5: 88 registers against 80)
+    const int occ1 = half ? ((n_smp > 1 && !al) ? 4 : 5) : 3, occ2 = half ? 3 : 2;
+    const long wg1 = (long)tiles_x * effi_cdiv(h, 4) * D * n_smp, wg2 = (long)tiles_x * effi_cdiv(h, 8) * D * n_smp;   // (all samples)
     bool mr2 = effi_cdiv(wg2, 256L * occ2) * 4 < effi_cdiv(wg1, 256L * occ1) * 3;
     const long fdm = effi_option(EFFI_OPT_DECONV_MR);
     if (fdm != EFFI_OPT_UNSET) mr2 = fdm == 2;
-    const dim3 grid(tiles_x * effi_cdiv(h, mr2 ? 8 : 4), D);
-#define EFFI_DC(MRV, ALV, HFV) \
-    hipLaunchKernelGGL((deconv3d_s2_bf16x3_kernel<MRV, ALV, HFV>), grid, dim3(256), 0, st, a, tiles_x, (int)grid.x)
+    const dim3 grid(tiles_x * effi_cdiv(h, mr2 ? 8 : 4), D, n_smp);
+#define EFFI_DC(MRV, ALV, HFV)                                                                                                     \
+    do {                                                                                                                           \
+        if (n_smp > 1)                                                                                                             \
+            hipLaunchKernelGGL((deconv3d_s2_bf16x3_batch_kernel<MRV, ALV, HFV>), grid, dim3(256), 0, st, a, in_ss, skip_ss, out_ss, \
+                               tiles_x, (int)grid.x);                                                                              \
+        else                                                                                                                       \
+            hipLaunchKernelGGL((deconv3d_s2_bf16x3_kernel<MRV, ALV, HFV>), grid, dim3(256), 0, st, a, tiles_x, (int)grid.x);         \
+    } while (0)
     if (mr2) {
         if (al) { if (half) EFFI_DC(2, true, true); else EFFI_DC(2, true, false); }
         else { if (half) EFFI_DC(2, false, true); else EFFI_DC(2, false, false); }
@@ -3138,6 +3305,19 @@ extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32)(const float* in, int cin, 
     }
 #undef EFFI_DC
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
+                                             int h, int w, int relu, const float* skip, float* out, effi_stream_t stream) {
+    return deconv3d_k3s2_x3_impl(in, cin, wpack_bf16, bias, cout, D, h, w, relu, skip, out, 1, 0, 0, 0, stream);
+}
+
+extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32_batch)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout,
+                                                            int D, int h, int w, int relu, const float* skip, float* out, int n_smp,
+                                                            long in_sstride, long skip_sstride, long out_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || in_sstride < 0 || skip_sstride < 0 || out_sstride < 0) return EFFI_ERR_BADARG;
+    return deconv3d_k3s2_x3_impl(in, cin, wpack_bf16, bias, cout, D, h, w, relu, skip, out, n_smp, in_sstride, skip_sstride, out_sstride,
+                                 stream);
 }
 
 #ifndef EFFI_BF16_ONLY

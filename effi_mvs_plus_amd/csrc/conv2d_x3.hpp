@@ -1208,6 +1208,33 @@ static int launch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, hipStrea
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
+// Sample batch of the z-batched form (effi_conv3d_k3s1_bf16x3_f32_batch): grid (ntiles, planes, n_smp), blockIdx.z = sample; tile and
+// plane come from blockIdx.x / blockIdx.y as in conv2d_k3_bf16x3_kernel.  Rows per wave by the rule of launch_bf16x3 on the tiles of
+// all samples (never the wide tiles: the z-batched form does not take them).
+template <int NT, int MR>
+__global__ __launch_bounds__(256) void conv3d_k3_bf16x3_zb_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
+    conv2d_k3_bf16x3_tile<NT, MR, EFFI_EPI_PLAIN, true, false, false, 4>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, blockIdx.x,
+                                                                         gridDim.x, blockIdx.y);
+}
+template <int NT>
+static int launch_bf16x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
+    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * b.n_img;
+    const long t4 = cols * effi_cdiv(a.h, 16) * planes, t2 = cols * effi_cdiv(a.h, 8) * planes;
+    int mr;
+    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
+    else if (t2 >= effi_mr2_min()) mr = 2;
+    else mr = 1;
+    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
+    if (force) mr = (int)force;
+    if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
+    const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 4 * mr);
+    const dim3 grid(ntiles, (unsigned)a.zcount, (unsigned)b.n_img);
+    if (mr == 4) hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 4>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+    else if (mr == 2) hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 2>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+    else hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 1>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
 template <int EPI>
 static int dispatch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, int nt, hipStream_t st) {
     switch (nt) {

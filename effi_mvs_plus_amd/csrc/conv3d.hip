@@ -182,6 +182,25 @@ __global__ __launch_bounds__(256) void conv3d_k3_kernel(SrcSet src, int cin, con
     conv3d_k3_body<COUT_T, SZ, SXY, ZPT, DENSE>(src, cin, wgt, bias, cout, D, h, w, Do, ho, wo, relu, skip, out);
 }
 
+// n_smp samples in one launch (the *_batch entries: the stage-1 regulariser over a batch): blockIdx.y = sample.  Sample i of a tensor
+// starts i * stride floats behind sample 0 (stride 0 = shared by all samples); weights and bias are shared.  The workgroup offsets its
+// pointers once and runs the single-sample body: sample i has the bits of the single-sample launch on sample i.
+struct C3Batch {
+    long src[EFFI_MAX_SRC];
+    long skip, out;
+};
+template <int COUT_T, int SZ, int SXY, int ZPT, bool DENSE = false>
+__global__ __launch_bounds__(256) void conv3d_k3_batch_kernel(SrcSet src, C3Batch bt, int cin, const float* __restrict__ wgt,
+                                                              const float* __restrict__ bias, int cout, int D, int h, int w, int Do,
+                                                              int ho, int wo, int relu, const float* __restrict__ skip,
+                                                              float* __restrict__ out) {
+    const long smp = blockIdx.y;
+#pragma unroll
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) src.p[i] += smp * bt.src[i];
+    conv3d_k3_body<COUT_T, SZ, SXY, ZPT, DENSE>(src, cin, wgt, bias, cout, D, h, w, Do, ho, wo, relu, skip ? skip + smp * bt.skip : nullptr,
+                                                out + smp * bt.out);
+}
+
 // Two independent convolutions of the same shape in one launch: blockIdx.y picks the argument set (the two cross-scale blocks
 // CSP_R / CSP_C of a stage, models/Effi_MVS_plus.py:520-531, which would otherwise be forked onto two streams).
 struct Conv3dCall {
@@ -224,16 +243,12 @@ struct C1Call {
     float* out;
 };
 template <int SXY, int ZPT>
-__global__ __launch_bounds__(256) void conv3d_c1to8_kernel(C1Call ca, C1Call cb, int D, int h, int w, int ho, int wo, int relu) {
+__device__ __forceinline__ void conv3d_c1to8_body(const float* __restrict__ in, const float* __restrict__ wgt, const float* __restrict__ bias,
+                                                  float* __restrict__ out, int D, int h, int w, int ho, int wo, int relu) {
     constexpr int IZ = ZPT + 2, IY = (TY - 1) * SXY + 3, IX = (TX - 1) * SXY + 3;
     constexpr int PSZ = IY * IX, NPL = (PSZ + 255) / 256, PSZP = NPL * 256;          // plane slot padded to whole passes
     __shared__ float tile[IZ * PSZP];
     __shared__ __attribute__((aligned(16))) float wl[27 * 8 + 8];
-    const bool second = blockIdx.y != 0;
-    const float* __restrict__ in = second ? cb.in : ca.in;
-    const float* __restrict__ wgt = second ? cb.wgt : ca.wgt;
-    const float* __restrict__ bias = second ? cb.bias : ca.bias;
-    float* __restrict__ out = second ? cb.out : ca.out;
 
     const int tid = threadIdx.x;
     const int tiles_x = (wo + TX - 1) / TX, tiles_xy = tiles_x * ((ho + TY - 1) / TY);
@@ -326,27 +341,52 @@ __global__ __launch_bounds__(256) void conv3d_c1to8_kernel(C1Call ca, C1Call cb,
     }
 }
 
+template <int SXY, int ZPT>
+__global__ __launch_bounds__(256) void conv3d_c1to8_kernel(C1Call ca, C1Call cb, int D, int h, int w, int ho, int wo, int relu) {
+    const bool second = blockIdx.y != 0;
+    conv3d_c1to8_body<SXY, ZPT>(second ? cb.in : ca.in, second ? cb.wgt : ca.wgt, second ? cb.bias : ca.bias, second ? cb.out : ca.out, D, h,
+                                w, ho, wo, relu);
+}
+// n_smp samples of one convolution (blockIdx.y = sample; see conv3d_k3_batch_kernel)
+template <int SXY, int ZPT>
+__global__ __launch_bounds__(256) void conv3d_c1to8_batch_kernel(C1Call c, long in_ss, long out_ss, int D, int h, int w, int ho, int wo,
+                                                                 int relu) {
+    const long smp = blockIdx.y;
+    conv3d_c1to8_body<SXY, ZPT>(c.in + smp * in_ss, c.wgt, c.bias, c.out + smp * out_ss, D, h, w, ho, wo, relu);
+}
+
 // option c3_lean: unset = both dedicated kernels; otherwise a mask, bit 0 = the 1 -> 8 kernel, bit 1 = the 8 -> 1 kernel (A/B, bisection)
 static bool c3_lean(int bit) {
     const long v = effi_option(EFFI_OPT_C3_LEAN);
     return v == EFFI_OPT_UNSET || ((v >> bit) & 1);
 }
 
-// launch rule of the cin = 1 kernel: 8 planes per thread when the grid still covers the chip twice
-int launch_c1to8(const C1Call& a, const C1Call* b, int D, int h, int w, int sxy, int relu, hipStream_t st) {
+// launch rule of the cin = 1 kernel: 8 planes per thread when the grid still covers the chip twice.  grid.y = the two calls of a pair
+// (b != nullptr) or the n_smp samples of a batch (sample strides in_ss / out_ss; a pixel's FMA order does not depend on the planes
+// per thread, so the rule may count the workgroups of all samples)
+int launch_c1to8(const C1Call& a, const C1Call* b, int D, int h, int w, int sxy, int relu, hipStream_t st, int n_smp = 1, long in_ss = 0,
+                 long out_ss = 0) {
     if ((long)D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input volume
     const int ho = (h - 1) / sxy + 1, wo = (w - 1) / sxy + 1;
-    const long tiles = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY), ncall = b ? 2 : 1;
+    const long tiles = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY), ncall = b ? 2 : n_smp;
     const bool z8 = tiles * effi_cdiv(D, 8) * ncall >= 512;
     const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
     const C1Call& bb = b ? *b : a;
+#define EFFI_C1(SXYV, ZV)                                                                                                             \
+    do {                                                                                                                              \
+        if (n_smp > 1)                                                                                                                \
+            hipLaunchKernelGGL((conv3d_c1to8_batch_kernel<SXYV, ZV>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, ho, wo, relu); \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((conv3d_c1to8_kernel<SXYV, ZV>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);                  \
+    } while (0)
     if (sxy == 1) {
-        if (z8) hipLaunchKernelGGL((conv3d_c1to8_kernel<1, 8>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);
-        else hipLaunchKernelGGL((conv3d_c1to8_kernel<1, 4>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);
+        if (z8) EFFI_C1(1, 8);
+        else EFFI_C1(1, 4);
     } else {
-        if (z8) hipLaunchKernelGGL((conv3d_c1to8_kernel<2, 8>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);
-        else hipLaunchKernelGGL((conv3d_c1to8_kernel<2, 4>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);
+        if (z8) EFFI_C1(2, 8);
+        else EFFI_C1(2, 4);
     }
+#undef EFFI_C1
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
@@ -366,7 +406,8 @@ struct C8Call {
 // DECONV = false: out[z][y][x] = sum_c sum_taps in[c][z+kd-1][y+ky-1][x+kx-1] w[c][kd][ky][kx]          (ZPT = 4 planes per thread)
 // DECONV = true : transposed, stride (1,2,2), output_padding (0,1,1): a thread owns input (y, x) and the 2 x 2 outputs it maps to
 template <bool DECONV, int ZPT>
-__global__ __launch_bounds__(256) void conv3d_c8to1_kernel(C8Call ca, C8Call cb, int D, int h, int w, int relu) {
+__device__ __forceinline__ void conv3d_c8to1_body(const float* __restrict__ in, const float* __restrict__ wgt, const float* __restrict__ bias,
+                                                  float* __restrict__ out, int D, int h, int w, int relu) {
 #ifndef EFFI_C8_CC
 #define EFFI_C8_CC 2
 #endif
@@ -378,11 +419,6 @@ __global__ __launch_bounds__(256) void conv3d_c8to1_kernel(C8Call ca, C8Call cb,
     constexpr int PSZ = IY * IX, PSZP = (PSZ + EFFI_C8_PADMASK) & ~EFFI_C8_PADMASK, NPL = (PSZP + 255) / 256, LASTN = PSZP - 256 * (NPL - 1);
     __shared__ float tile[CC * IZ * PSZP];
     __shared__ __attribute__((aligned(16))) float wl[8 * 28 + 4];          // 27 weights per channel at stride 28, then the bias
-    const bool second = blockIdx.y != 0;
-    const float* __restrict__ in = second ? cb.in : ca.in;
-    const float* __restrict__ wgt = second ? cb.wgt : ca.wgt;
-    const float* __restrict__ bias = second ? cb.bias : ca.bias;
-    float* __restrict__ out = second ? cb.out : ca.out;
 
     const int tid = threadIdx.x;
     const int tiles_x = (w + TX - 1) / TX, tiles_xy = tiles_x * ((h + TY - 1) / TY);
@@ -540,14 +576,34 @@ __global__ __launch_bounds__(256) void conv3d_c8to1_kernel(C8Call ca, C8Call cb,
     }
 }
 
+template <bool DECONV, int ZPT>
+__global__ __launch_bounds__(256) void conv3d_c8to1_kernel(C8Call ca, C8Call cb, int D, int h, int w, int relu) {
+    const bool second = blockIdx.y != 0;
+    conv3d_c8to1_body<DECONV, ZPT>(second ? cb.in : ca.in, second ? cb.wgt : ca.wgt, second ? cb.bias : ca.bias, second ? cb.out : ca.out, D,
+                                   h, w, relu);
+}
+// n_smp samples of one convolution (blockIdx.y = sample; see conv3d_k3_batch_kernel)
+template <bool DECONV, int ZPT>
+__global__ __launch_bounds__(256) void conv3d_c8to1_batch_kernel(C8Call c, long in_ss, long out_ss, int D, int h, int w, int relu) {
+    const long smp = blockIdx.y;
+    conv3d_c8to1_body<DECONV, ZPT>(c.in + smp * in_ss, c.wgt, c.bias, c.out + smp * out_ss, D, h, w, relu);
+}
+
+// (grid.y: the two calls of a pair, or the n_smp samples of a batch -- as launch_c1to8)
 template <bool DECONV>
-int launch_c8to1(const C8Call& a, const C8Call* b, int D, int h, int w, int relu, hipStream_t st) {
+int launch_c8to1(const C8Call& a, const C8Call* b, int D, int h, int w, int relu, hipStream_t st, int n_smp = 1, long in_ss = 0,
+                 long out_ss = 0) {
     if (8L * D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input tensor
-    const long tiles = (long)effi_cdiv(w, TX) * effi_cdiv(h, TY), ncall = b ? 2 : 1;
+    const long tiles = (long)effi_cdiv(w, TX) * effi_cdiv(h, TY), ncall = b ? 2 : n_smp;
     const bool z8 = tiles * effi_cdiv(D, 8) * ncall >= 512;
     const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
-    if (z8) hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
-    else hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 4>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
+    if (n_smp > 1) {
+        if (z8) hipLaunchKernelGGL((conv3d_c8to1_batch_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, relu);
+        else hipLaunchKernelGGL((conv3d_c8to1_batch_kernel<DECONV, 4>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, relu);
+    } else {
+        if (z8) hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
+        else hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 4>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
+    }
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
 }
 
@@ -720,6 +776,17 @@ __global__ __launch_bounds__(256) void deconv3d_k3_kernel(const float* __restric
     deconv3d_k3_body<COUT_T, SZ>(in, cin, wgt, bias, cout, D, h, w, relu, skip, out);
 }
 
+// n_smp samples in one launch (blockIdx.y = sample; see conv3d_k3_batch_kernel)
+template <int COUT_T, int SZ>
+__global__ __launch_bounds__(256) void deconv3d_k3_batch_kernel(const float* __restrict__ in, long in_ss, int cin,
+                                                                const float* __restrict__ wgt, const float* __restrict__ bias, int cout,
+                                                                int D, int h, int w, int relu, const float* __restrict__ skip,
+                                                                long skip_ss, float* __restrict__ out, long out_ss) {
+    const long smp = blockIdx.y;
+    deconv3d_k3_body<COUT_T, SZ>(in + smp * in_ss, cin, wgt, bias, cout, D, h, w, relu, skip ? skip + smp * skip_ss : nullptr,
+                                 out + smp * out_ss);
+}
+
 struct Deconv3dCall {
     const float* in;
     const float* wgt;
@@ -737,9 +804,19 @@ __global__ __launch_bounds__(256) void deconv3d_k3_pair_kernel(Deconv3dCall a, D
 
 template <int COUT_T, int SZ, int SXY, int ZPT>
 int launch_conv_z(const SrcSet& s, int cin, const float* wgt, const float* bias, int cout, int D, int h, int w,
-                  int relu, const float* skip, float* out, hipStream_t st) {
+                  int relu, const float* skip, float* out, hipStream_t st, const C3Batch* bt = nullptr, int n_smp = 1) {
     const int Do = (D - 1) / SZ + 1, ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
     dim3 grid(effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, ZPT) * effi_cdiv(cout, COUT_T));
+    if (bt) {
+        grid.y = (unsigned)n_smp;
+        if (cout == COUT_T)
+            hipLaunchKernelGGL((conv3d_k3_batch_kernel<COUT_T, SZ, SXY, ZPT, true>), grid, dim3(256), 0, st, s, *bt, cin, wgt, bias, cout, D,
+                               h, w, Do, ho, wo, relu, skip, out);
+        else
+            hipLaunchKernelGGL((conv3d_k3_batch_kernel<COUT_T, SZ, SXY, ZPT, false>), grid, dim3(256), 0, st, s, *bt, cin, wgt, bias, cout, D,
+                               h, w, Do, ho, wo, relu, skip, out);
+        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    }
     if (cout == COUT_T)
         hipLaunchKernelGGL((conv3d_k3_kernel<COUT_T, SZ, SXY, ZPT, true>), grid, dim3(256), 0, st, s, cin, wgt, bias, cout, D, h, w,
                            Do, ho, wo, relu, skip, out);
@@ -751,21 +828,22 @@ int launch_conv_z(const SrcSet& s, int cin, const float* wgt, const float* bias,
 
 // Output z-slices per thread: 4 (2 for stride 2) amortises the z halo of the LDS tile; low-resolution layers
 // fall back to 1 so that the grid still has >= 2 workgroups per CU.
+// (batched, bt != nullptr: the rule on the workgroups of all n_smp samples; an output's FMA order does not depend on ZPT)
 template <int COUT_T, int SZ, int SXY>
 int launch_conv(const SrcSet& s, int cin, const float* wgt, const float* bias, int cout, int D, int h, int w,
-                int relu, const float* skip, float* out, hipStream_t st) {
+                int relu, const float* skip, float* out, hipStream_t st, const C3Batch* bt = nullptr, int n_smp = 1) {
     constexpr int ZBIG = (SXY == 1) ? 4 : ((SZ == 1) ? 4 : 2);
     const int Do = (D - 1) / SZ + 1, ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
-    const long blocks = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, ZBIG) * effi_cdiv(cout, COUT_T);
-    if (blocks >= 384) return launch_conv_z<COUT_T, SZ, SXY, ZBIG>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st);
-    return launch_conv_z<COUT_T, SZ, SXY, 1>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st);
+    const long blocks = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, ZBIG) * effi_cdiv(cout, COUT_T) * n_smp;
+    if (blocks >= 384) return launch_conv_z<COUT_T, SZ, SXY, ZBIG>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
+    return launch_conv_z<COUT_T, SZ, SXY, 1>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
 }
 
 }  // namespace
 
-extern "C" int effi_conv3d_k3_f32(const float* const* srcs, const int* src_channels, int n_src, const float* weight,
-                                  const float* bias, int cout, int D, int h, int w, int sz, int sxy, int relu,
-                                  const float* skip, float* out, effi_stream_t stream) {
+static int conv3d_k3_impl(const float* const* srcs, const int* src_channels, int n_src, const float* weight, const float* bias, int cout,
+                          int D, int h, int w, int sz, int sxy, int relu, const float* skip, float* out, const C3Batch* bt, int n_smp,
+                          effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !weight || !out) return EFFI_ERR_BADARG;
     if (D < 1 || h < 1 || w < 1 || cout < 1) return EFFI_ERR_BADARG;
     SrcSet s;
@@ -779,47 +857,92 @@ extern "C" int effi_conv3d_k3_f32(const float* const* srcs, const int* src_chann
     hipStream_t st = effi_s(stream);
     if (cin == 1 && cout == 8 && sz == 1 && (sxy == 1 || sxy == 2) && !skip && c3_lean(0)) {
         const C1Call c{srcs[0], weight, bias, out};
-        return launch_c1to8(c, nullptr, D, h, w, sxy, relu, st);
+        return launch_c1to8(c, nullptr, D, h, w, sxy, relu, st, n_smp, bt ? bt->src[0] : 0, bt ? bt->out : 0);
     }
     if (cin == 8 && n_src == 1 && cout == 1 && sz == 1 && sxy == 1 && !skip && c3_lean(1)) {
         const C8Call c{srcs[0], weight, bias, out};
-        return launch_c8to1<false>(c, nullptr, D, h, w, relu, st);
+        return launch_c8to1<false>(c, nullptr, D, h, w, relu, st, n_smp, bt ? bt->src[0] : 0, bt ? bt->out : 0);
     }
     const bool c8 = (cout % 8 == 0);
     if (!c8 && cout != 1) return EFFI_ERR_UNSUPPORTED;
     if (sz == 1 && sxy == 1)
-        return c8 ? launch_conv<8, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st)
-                  : launch_conv<1, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st);
+        return c8 ? launch_conv<8, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp)
+                  : launch_conv<1, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
     if (!c8) return EFFI_ERR_UNSUPPORTED;
-    if (sz == 2 && sxy == 2) return launch_conv<8, 2, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st);
-    if (sz == 1 && sxy == 2) return launch_conv<8, 1, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st);
+    if (sz == 2 && sxy == 2) return launch_conv<8, 2, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
+    if (sz == 1 && sxy == 2) return launch_conv<8, 1, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
     return EFFI_ERR_UNSUPPORTED;
+}
+
+extern "C" int effi_conv3d_k3_f32(const float* const* srcs, const int* src_channels, int n_src, const float* weight,
+                                  const float* bias, int cout, int D, int h, int w, int sz, int sxy, int relu,
+                                  const float* skip, float* out, effi_stream_t stream) {
+    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, nullptr, 1, stream);
+}
+
+// n_smp == 1: the single-sample launch itself
+extern "C" int effi_conv3d_k3_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const float* weight,
+                                        const float* bias, int cout, int D, int h, int w, int sz, int sxy, int relu,
+                                        const float* skip, float* out, int n_smp, const long* src_sstride, long skip_sstride,
+                                        long out_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || !src_sstride || skip_sstride < 0 || out_sstride < 0 || n_src < 1 || n_src > EFFI_MAX_SRC)
+        return EFFI_ERR_BADARG;
+    C3Batch bt;
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
+        bt.src[i] = (i < n_src) ? src_sstride[i] : 0;
+        if (bt.src[i] < 0) return EFFI_ERR_BADARG;
+    }
+    bt.skip = skip_sstride;
+    bt.out = out_sstride;
+    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, n_smp > 1 ? &bt : nullptr, n_smp,
+                          stream);
+}
+
+// n_smp > 1: grid.y = sample.  The channel split of the stride-2 form follows the workgroups of all samples (an output's FMA order does
+// not depend on it).
+static int deconv3d_k3_impl(const float* in, int cin, const float* weight, const float* bias, int cout, int D, int h, int w, int sz,
+                            int relu, const float* skip, float* out, int n_smp, long in_ss, long skip_ss, long out_ss,
+                            effi_stream_t stream) {
+    if (!in || !weight || !out || cin < 1 || cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    const int tiles = effi_cdiv(w, TX) * effi_cdiv(h, TY);
+#define EFFI_DK(CT, SZV, GX)                                                                                                          \
+    do {                                                                                                                              \
+        if (n_smp > 1)                                                                                                                \
+            hipLaunchKernelGGL((deconv3d_k3_batch_kernel<CT, SZV>), dim3(GX, n_smp), dim3(256), 0, st, in, in_ss, cin, weight, bias,   \
+                               cout, D, h, w, relu, skip, skip_ss, out, out_ss);                                                      \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((deconv3d_k3_kernel<CT, SZV>), dim3(GX), dim3(256), 0, st, in, cin, weight, bias, cout, D, h, w, relu,  \
+                               skip, out);                                                                                            \
+    } while (0)
+    if (sz == 2 && cout % 8 == 0) {
+        if ((long)tiles * D * (cout / 8) * n_smp >= 512) EFFI_DK(8, 2, tiles * D * (cout / 8));
+        else EFFI_DK(4, 2, tiles * D * (cout / 4));   // low-resolution level: split the output channels finer so the grid covers the chip
+    } else if (sz == 1 && cout == 1 && cin == 8 && !skip && c3_lean(1)) {
+        const C8Call c{in, weight, bias, out};
+        return launch_c8to1<true>(c, nullptr, D, h, w, relu, st, n_smp, in_ss, out_ss);
+    } else if (sz == 1 && cout == 1) {
+        EFFI_DK(1, 1, tiles * effi_cdiv(D, 4));
+    } else {
+        return EFFI_ERR_UNSUPPORTED;
+    }
+#undef EFFI_DK
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
 }
 
 extern "C" int effi_deconv3d_k3_f32(const float* in, int cin, const float* weight, const float* bias, int cout, int D,
                                     int h, int w, int sz, int relu, const float* skip, float* out,
                                     effi_stream_t stream) {
-    if (!in || !weight || !out || cin < 1 || cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    const int tiles = effi_cdiv(w, TX) * effi_cdiv(h, TY);
-    if (sz == 2 && cout % 8 == 0) {
-        if ((long)tiles * D * (cout / 8) >= 512)
-            hipLaunchKernelGGL((deconv3d_k3_kernel<8, 2>), dim3(tiles * D * (cout / 8)), dim3(256), 0, st, in, cin, weight, bias,
-                               cout, D, h, w, relu, skip, out);
-        else   // low-resolution level: split the output channels finer so the grid covers the chip
-            hipLaunchKernelGGL((deconv3d_k3_kernel<4, 2>), dim3(tiles * D * (cout / 4)), dim3(256), 0, st, in, cin, weight, bias,
-                               cout, D, h, w, relu, skip, out);
-    } else if (sz == 1 && cout == 1 && cin == 8 && !skip && c3_lean(1)) {
-        const C8Call c{in, weight, bias, out};
-        return launch_c8to1<true>(c, nullptr, D, h, w, relu, st);
-    } else if (sz == 1 && cout == 1) {
-        hipLaunchKernelGGL((deconv3d_k3_kernel<1, 1>), dim3(tiles * effi_cdiv(D, 4)), dim3(256), 0, st, in, cin, weight,
-                           bias, cout, D, h, w, relu, skip, out);
-    } else {
-        return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, 1, 0, 0, 0, stream);
+}
+
+// n_smp == 1: the single-sample launch itself
+extern "C" int effi_deconv3d_k3_f32_batch(const float* in, int cin, const float* weight, const float* bias, int cout, int D, int h,
+                                          int w, int sz, int relu, const float* skip, float* out, int n_smp, long in_sstride,
+                                          long skip_sstride, long out_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || in_sstride < 0 || skip_sstride < 0 || out_sstride < 0) return EFFI_ERR_BADARG;
+    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, n_smp, in_sstride, skip_sstride, out_sstride, stream);
 }
 
 // ---- pair launches (see conv3d_k3_pair_kernel) ------------------------------------------------------------------------

@@ -77,6 +77,19 @@ __global__ void compose_rel_proj_kernel(const float* __restrict__ pairs, int n_v
     write_rt(S, Rinv, rt + v * 12);
 }
 
+// n_smp camera sets in one launch: blockIdx.y = sample
+__global__ void compose_rel_proj_batch_kernel(const float* __restrict__ pairs, long pairs_ss, int n_views, float* __restrict__ rt,
+                                              long rt_ss) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_views - 1) return;
+    pairs += (long)blockIdx.y * pairs_ss;
+    double R[4][4], Rinv[4][4], S[4][4];
+    compose_k_rt(pairs, R);
+    invert4x4(R, Rinv);
+    compose_k_rt(pairs + (long)(v + 1) * 32, S);
+    write_rt(S, Rinv, rt + (long)blockIdx.y * rt_ss + v * 12);
+}
+
 // all stages of the cascade in one launch: blockIdx.x = stage
 struct PairList { const float* p[4]; };
 __device__ __forceinline__ void compose_rel_proj_stage(const PairList& pl, int stage, int n_views, float* __restrict__ rt_all) {
@@ -104,6 +117,24 @@ __global__ void cascade_setup_kernel(const float* __restrict__ disp_range, int n
     else compose_rel_proj_stage(pl, (int)blockIdx.x - 1, n_views, rt_all);
 }
 
+// n_smp samples (ranges and camera sets) in one launch: blockIdx.y = sample, each tensor at its own sample stride in floats
+struct SetupBatch {
+    long range, depths, intervals, rt;
+    long pairs[4];
+};
+__global__ void cascade_setup_batch_kernel(const float* __restrict__ disp_range, int n_range, int D, float* __restrict__ depths,
+                                           float* __restrict__ intervals, PairList pl, int n_views, float* __restrict__ rt_all,
+                                           SetupBatch b) {
+    const long s = blockIdx.y;
+    if (blockIdx.x == 0) {
+        effi_stage1_hypotheses_block(disp_range + s * b.range, n_range, D, depths + s * b.depths, intervals + s * b.intervals);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pl.p[j] += s * b.pairs[j];
+    compose_rel_proj_stage(pl, (int)blockIdx.x - 1, n_views, rt_all + s * b.rt);
+}
+
 __global__ void rel_proj_kernel(const float* __restrict__ src, const float* __restrict__ ref, float* __restrict__ rt) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double R[4][4], Rinv[4][4], S[4][4];
@@ -118,6 +149,18 @@ __global__ void rel_proj_kernel(const float* __restrict__ src, const float* __re
 extern "C" int effi_compose_rel_proj_f32(const float* pairs, int n_views, float* rt_out, effi_stream_t stream) {
     if (!pairs || !rt_out || n_views < 2 || n_views > EFFI_MAX_VIEWS + 1) return EFFI_ERR_BADARG;
     hipLaunchKernelGGL(compose_rel_proj_kernel, dim3(1), dim3(64), 0, effi_s(stream), pairs, n_views, rt_out);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+// n_smp == 1: the single-sample launch itself
+extern "C" int effi_compose_rel_proj_f32_batch(const float* pairs, int n_views, float* rt_out, int n_smp, long pairs_sstride,
+                                               long rt_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || pairs_sstride < 0 || rt_sstride < 0) return EFFI_ERR_BADARG;
+    if (n_smp == 1) return effi_compose_rel_proj_f32(pairs, n_views, rt_out, stream);
+    if (!pairs || !rt_out || n_views < 2 || n_views > EFFI_MAX_VIEWS + 1) return EFFI_ERR_BADARG;
+    hipLaunchKernelGGL(compose_rel_proj_batch_kernel, dim3(1, n_smp), dim3(64), 0, effi_s(stream), pairs, pairs_sstride, n_views, rt_out,
+                       rt_sstride);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }
@@ -146,6 +189,28 @@ extern "C" int effi_cascade_setup_f32(const float* disp_range, int n_range, int 
     }
     hipLaunchKernelGGL(cascade_setup_kernel, dim3(1 + n_stages), dim3(128), 0, effi_s(stream), disp_range, n_range, D, depths, intervals, pl,
                        n_views, rt_out);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_cascade_setup_f32_batch(const float* disp_range, int n_range, int D, float* depths, float* intervals,
+                                            const float* const* pairs, int n_stages, int n_views, float* rt_out, int n_smp,
+                                            long range_sstride, long depths_sstride, long intervals_sstride, const long* pairs_sstride,
+                                            long rt_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || range_sstride < 0 || depths_sstride < 0 || intervals_sstride < 0 || !pairs_sstride || rt_sstride < 0)
+        return EFFI_ERR_BADARG;
+    if (n_smp == 1) return effi_cascade_setup_f32(disp_range, n_range, D, depths, intervals, pairs, n_stages, n_views, rt_out, stream);
+    if (!disp_range || !depths || !intervals || n_range < 2 || D < 2) return EFFI_ERR_BADARG;
+    if (!pairs || !rt_out || n_stages < 1 || n_stages > 4 || n_views < 2 || n_views > EFFI_MAX_VIEWS + 1) return EFFI_ERR_BADARG;
+    PairList pl;
+    SetupBatch b{range_sstride, depths_sstride, intervals_sstride, rt_sstride, {0, 0, 0, 0}};
+    for (int k = 0; k < 4; ++k) {
+        pl.p[k] = pairs[k < n_stages ? k : 0];
+        b.pairs[k] = pairs_sstride[k < n_stages ? k : 0];
+        if (!pl.p[k] || b.pairs[k] < 0) return EFFI_ERR_BADARG;
+    }
+    hipLaunchKernelGGL(cascade_setup_batch_kernel, dim3(1 + n_stages, n_smp), dim3(128), 0, effi_s(stream), disp_range, n_range, D, depths,
+                       intervals, pl, n_views, rt_out, b);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }

@@ -174,8 +174,8 @@ __global__ __launch_bounds__(TPB) void head_update_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------
 // K3: sim = sum_v sim_v * w_v / (sum_v w_v + 1e-6)      (models/Effi_MVS_plus.py:48-53,67)
 // ------------------------------------------------------------------------------------------------
-__global__ void view_aggregate_kernel(const float* __restrict__ sim_views, const float* __restrict__ weights,
-                                      int S, int D, int hw, float* __restrict__ out) {
+__device__ __forceinline__ void view_aggregate_body(const float* __restrict__ sim_views, const float* __restrict__ weights,
+                                                    int S, int D, int hw, float* __restrict__ out) {
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= hw) return;
     const int d0 = blockIdx.y * 8;
@@ -204,6 +204,17 @@ __global__ void view_aggregate_kernel(const float* __restrict__ sim_views, const
     }
 }
 
+__global__ void view_aggregate_kernel(const float* __restrict__ sim_views, const float* __restrict__ weights,
+                                      int S, int D, int hw, float* __restrict__ out) {
+    view_aggregate_body(sim_views, weights, S, D, hw, out);
+}
+// n_smp samples in one launch: blockIdx.z = sample, each tensor at its own sample stride in floats
+__global__ void view_aggregate_batch_kernel(const float* __restrict__ sim_views, long sim_ss, const float* __restrict__ weights, long w_ss,
+                                            int S, int D, int hw, float* __restrict__ out, long out_ss) {
+    const long smp = blockIdx.z;
+    view_aggregate_body(sim_views + smp * sim_ss, weights ? weights + smp * w_ss : nullptr, S, D, hw, out + smp * out_ss);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K7: softmax over D, depth regression, 4-window confidence (models/Effi_MVS_plus.py:79-88)
 // ------------------------------------------------------------------------------------------------
@@ -222,11 +233,11 @@ __device__ __forceinline__ void conf_store_up(float* __restrict__ out_up, float 
         for (int i = 0; i < f; ++i) dst[(long)j * w * f + i] = conf;
 }
 
-__global__ void softmax_regress_conf_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
-                                            long dds, long dps, int D, int hw,
-                                            float* __restrict__ out_depth, float* __restrict__ out_conf,
-                                            const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv,
-                                            float* __restrict__ out_conf_up, int w, int f) {
+__device__ __forceinline__ void softmax_regress_conf_body(const float* __restrict__ logits, const float* __restrict__ depth,
+                                                          long dds, long dps, int D, int hw,
+                                                          float* __restrict__ out_depth, float* __restrict__ out_conf,
+                                                          const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv,
+                                                          float* __restrict__ out_conf_up, int w, int f) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;     // launched with 64-thread blocks
     if (p >= hw) return;
     float m = -INFINITY;
@@ -253,15 +264,36 @@ __global__ void softmax_regress_conf_kernel(const float* __restrict__ logits, co
     if (out_conf_up) conf_store_up(out_conf_up, conf, p, w, f);
 }
 
+// Per-sample strides (floats) of the batched softmax launches: blockIdx.y = sample; a stride of 0 shares the tensor
+struct SoftmaxBatch {
+    long logits, depth, out_depth, out_conf, range, out_dinv, out_conf_up;
+};
+__global__ void softmax_regress_conf_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
+                                            long dds, long dps, int D, int hw,
+                                            float* __restrict__ out_depth, float* __restrict__ out_conf,
+                                            const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv,
+                                            float* __restrict__ out_conf_up, int w, int f) {
+    softmax_regress_conf_body(logits, depth, dds, dps, D, hw, out_depth, out_conf, disp_range, n_range, out_dinv, out_conf_up, w, f);
+}
+__global__ void softmax_regress_conf_batch_kernel(const float* __restrict__ logits, const float* __restrict__ depth, long dds, long dps,
+                                                  int D, int hw, float* __restrict__ out_depth, float* __restrict__ out_conf,
+                                                  const float* __restrict__ disp_range, int n_range, float* __restrict__ out_dinv,
+                                                  float* __restrict__ out_conf_up, int w, int f, SoftmaxBatch b) {
+    const long s = blockIdx.y;
+    softmax_regress_conf_body(logits + s * b.logits, depth + s * b.depth, dds, dps, D, hw, out_depth + s * b.out_depth,
+                              out_conf + s * b.out_conf, disp_range ? disp_range + s * b.range : nullptr, n_range,
+                              out_dinv ? out_dinv + s * b.out_dinv : nullptr, out_conf_up ? out_conf_up + s * b.out_conf_up : nullptr, w, f);
+}
+
 // Same arithmetic, same order, for the depth counts the cascade uses: the D logits of a pixel are loaded ONCE into registers
 // (all loads in flight together) and every exponential is evaluated once; the generic kernel walks the volume three times with
 // dependent expf / division chains (27 us at 48 x 148 x 200 for 5.7 MB).
 template <int DT>
-__global__ __launch_bounds__(64) void softmax_regress_conf_reg_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
-                                                                      long dds, long dps, int hw, float* __restrict__ out_depth,
-                                                                      float* __restrict__ out_conf, const float* __restrict__ disp_range,
-                                                                      int n_range, float* __restrict__ out_dinv,
-                                                                      float* __restrict__ out_conf_up, int w, int f) {
+__device__ __forceinline__ void softmax_regress_conf_reg_body(const float* __restrict__ logits, const float* __restrict__ depth,
+                                                              long dds, long dps, int hw, float* __restrict__ out_depth,
+                                                              float* __restrict__ out_conf, const float* __restrict__ disp_range,
+                                                              int n_range, float* __restrict__ out_dinv,
+                                                              float* __restrict__ out_conf_up, int w, int f) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= hw) return;
     float e[DT], dv[DT];
@@ -298,6 +330,28 @@ __global__ __launch_bounds__(64) void softmax_regress_conf_reg_kernel(const floa
     out_conf[p] = conf;
     if (out_dinv) out_dinv[p] = effi_depth_to_inv(dep, disp_range[0], disp_range[n_range - 1]);   // models/Effi_MVS_plus.py:538
     if (out_conf_up) conf_store_up(out_conf_up, conf, p, w, f);
+}
+
+template <int DT>
+__global__ __launch_bounds__(64) void softmax_regress_conf_reg_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
+                                                                      long dds, long dps, int hw, float* __restrict__ out_depth,
+                                                                      float* __restrict__ out_conf, const float* __restrict__ disp_range,
+                                                                      int n_range, float* __restrict__ out_dinv,
+                                                                      float* __restrict__ out_conf_up, int w, int f) {
+    softmax_regress_conf_reg_body<DT>(logits, depth, dds, dps, hw, out_depth, out_conf, disp_range, n_range, out_dinv, out_conf_up, w, f);
+}
+template <int DT>
+__global__ __launch_bounds__(64) void softmax_regress_conf_reg_batch_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
+                                                                            long dds, long dps, int hw, float* __restrict__ out_depth,
+                                                                            float* __restrict__ out_conf,
+                                                                            const float* __restrict__ disp_range, int n_range,
+                                                                            float* __restrict__ out_dinv, float* __restrict__ out_conf_up,
+                                                                            int w, int f, SoftmaxBatch b) {
+    const long s = blockIdx.y;
+    softmax_regress_conf_reg_body<DT>(logits + s * b.logits, depth + s * b.depth, dds, dps, hw, out_depth + s * b.out_depth,
+                                      out_conf + s * b.out_conf, disp_range ? disp_range + s * b.range : nullptr, n_range,
+                                      out_dinv ? out_dinv + s * b.out_dinv : nullptr, out_conf_up ? out_conf_up + s * b.out_conf_up : nullptr,
+                                      w, f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -608,15 +662,49 @@ extern "C" int effi_view_aggregate_f32(const float* sim_views, const float* weig
     return EFFI_OK;
 }
 
+extern "C" int effi_view_aggregate_f32_batch(const float* sim_views, const float* weights, int S, int D, int hw, float* out, int n_smp,
+                                             long sim_sstride, long weights_sstride, long out_sstride, effi_stream_t stream) {
+    if (n_smp < 1 || n_smp > 65535 || sim_sstride < 0 || weights_sstride < 0 || out_sstride < 0) return EFFI_ERR_BADARG;
+    if (n_smp == 1) return effi_view_aggregate_f32(sim_views, weights, S, D, hw, out, stream);
+    if (!sim_views || !out || S < 1 || S > EFFI_MAX_VIEWS || D < 1 || hw < 1) return EFFI_ERR_BADARG;
+    hipLaunchKernelGGL(view_aggregate_batch_kernel, dim3(effi_cdiv(hw, TPB), effi_cdiv(D, 8), n_smp), dim3(TPB), 0, effi_s(stream),
+                       sim_views, sim_sstride, weights, weights_sstride, S, D, hw, out, out_sstride);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+// bt == nullptr: the single-sample launch
 static int softmax_regress_conf_launch(const float* logits, const float* depth, long dds, long dps, int D, int hw, float* out_depth,
                                        float* out_conf, const float* disp_range, int n_range, float* out_depth_inv,
-                                       float* out_conf_up, int w, int f, effi_stream_t stream) {
+                                       float* out_conf_up, int w, int f, effi_stream_t stream, const SoftmaxBatch* bt = nullptr,
+                                       int n_smp = 1) {
     if (!logits || !depth || !out_depth || !out_conf || D < 1 || hw < 1) return EFFI_ERR_BADARG;
     if (out_depth_inv && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
     if (out_conf_up && (w < 1 || f < 1 || hw % w != 0)) return EFFI_ERR_BADARG;
     if (out_conf_up && f == 4 && (reinterpret_cast<uintptr_t>(out_conf_up) & 15)) return EFFI_ERR_BADARG;
-    const dim3 grid(effi_cdiv(hw, 64));
     hipStream_t st = effi_s(stream);
+    if (bt) {
+        if (out_conf_up && f == 4 && (bt->out_conf_up & 3)) return EFFI_ERR_BADARG;           // 16-byte stores in every sample
+        const dim3 bgrid(effi_cdiv(hw, 64), n_smp);
+#define EFFI_SMB(DT)                                                                                                              \
+    hipLaunchKernelGGL(softmax_regress_conf_reg_batch_kernel<DT>, bgrid, dim3(64), 0, st, logits, depth, dds, dps, hw, out_depth, \
+                       out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f, *bt)
+        switch (D) {
+            case 8: EFFI_SMB(8); break;
+            case 16: EFFI_SMB(16); break;
+            case 32: EFFI_SMB(32); break;
+            case 48: EFFI_SMB(48); break;
+            case 64: EFFI_SMB(64); break;
+            case 96: EFFI_SMB(96); break;
+            default:
+                hipLaunchKernelGGL(softmax_regress_conf_batch_kernel, bgrid, dim3(64), 0, st, logits, depth, dds, dps, D, hw, out_depth,
+                                   out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f, *bt);
+        }
+#undef EFFI_SMB
+        EFFI_LAUNCH_CHECK();
+        return EFFI_OK;
+    }
+    const dim3 grid(effi_cdiv(hw, 64));
 #define EFFI_SM(DT)                                                                                                      \
     hipLaunchKernelGGL(softmax_regress_conf_reg_kernel<DT>, grid, dim3(64), 0, st, logits, depth, dds, dps, hw, out_depth, \
                        out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f)
@@ -649,6 +737,42 @@ extern "C" int effi_softmax_regress_conf_up_f32(const float* logits, const float
     if (h < 1 || w < 1 || !out_conf_up) return EFFI_ERR_BADARG;
     return softmax_regress_conf_launch(logits, depth, dds, dps, D, h * w, out_depth, out_conf, disp_range, n_range, out_depth_inv,
                                        out_conf_up, w, f, stream);
+}
+
+static bool fill_softmax_batch(SoftmaxBatch& b, int n_smp, long logits_ss, long depth_ss, long od_ss, long oc_ss, long range_ss,
+                               long oi_ss, long ou_ss) {
+    if (n_smp < 1 || n_smp > 65535 || logits_ss < 0 || depth_ss < 0 || od_ss < 0 || oc_ss < 0 || range_ss < 0 || oi_ss < 0 || ou_ss < 0)
+        return false;
+    b = SoftmaxBatch{logits_ss, depth_ss, od_ss, oc_ss, range_ss, oi_ss, ou_ss};
+    return true;
+}
+
+extern "C" int effi_softmax_regress_conf_f32_batch(const float* logits, const float* depth, long dds, long dps, int D, int hw,
+                                                   float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                                   float* out_depth_inv, int n_smp, long logits_sstride, long depth_sstride,
+                                                   long out_depth_sstride, long out_conf_sstride, long range_sstride,
+                                                   long out_depth_inv_sstride, effi_stream_t stream) {
+    SoftmaxBatch b;
+    if (!fill_softmax_batch(b, n_smp, logits_sstride, depth_sstride, out_depth_sstride, out_conf_sstride, range_sstride,
+                            out_depth_inv_sstride, 0))
+        return EFFI_ERR_BADARG;
+    return softmax_regress_conf_launch(logits, depth, dds, dps, D, hw, out_depth, out_conf, disp_range, n_range, out_depth_inv, nullptr, 0,
+                                       0, stream, n_smp > 1 ? &b : nullptr, n_smp);
+}
+
+extern "C" int effi_softmax_regress_conf_up_f32_batch(const float* logits, const float* depth, long dds, long dps, int D, int h, int w,
+                                                      float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                                      float* out_depth_inv, float* out_conf_up, int f, int n_smp, long logits_sstride,
+                                                      long depth_sstride, long out_depth_sstride, long out_conf_sstride,
+                                                      long range_sstride, long out_depth_inv_sstride, long out_conf_up_sstride,
+                                                      effi_stream_t stream) {
+    SoftmaxBatch b;
+    if (h < 1 || w < 1 || !out_conf_up) return EFFI_ERR_BADARG;
+    if (!fill_softmax_batch(b, n_smp, logits_sstride, depth_sstride, out_depth_sstride, out_conf_sstride, range_sstride,
+                            out_depth_inv_sstride, out_conf_up_sstride))
+        return EFFI_ERR_BADARG;
+    return softmax_regress_conf_launch(logits, depth, dds, dps, D, h * w, out_depth, out_conf, disp_range, n_range, out_depth_inv,
+                                       out_conf_up, w, f, stream, n_smp > 1 ? &b : nullptr, n_smp);
 }
 
 extern "C" int effi_vol_lookup1d_f32(const float* vol, long vds, long vps, int Dp, const float* query, long qds,

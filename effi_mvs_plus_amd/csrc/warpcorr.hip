@@ -146,18 +146,22 @@ __device__ __forceinline__ bool tile_pixel(int bid, int nblk, int h, int w, int&
 // ------------------------------------------------------------------------------------------------
 // stage 1: per-view similarity volume + softmax entropy over D   (grid.y = source view)
 // ------------------------------------------------------------------------------------------------
+// Sample batch of the stage-1 launches (the *_batch entries): blockIdx.z = sample; sample i of a tensor starts i * stride floats
+// behind sample 0, `src` is the ONE stride every pointer of the source list shares, a depth stride of 0 shares the hypotheses.
+struct WarpBatch {
+    long ref, src, rt, depth, sim, ent;
+};
+
 template <int C>
-__global__ __launch_bounds__(256) void warpcorr_views_kernel(const float* ref_arg, EffiPtrList srcs,
-                                                             const float* __restrict__ rt_all,
-                                                             const float* __restrict__ depth, long dds, long dps,
-                                                             int h, int w, int D, float* sim_views,
-                                                             float* __restrict__ entropy) {
+__device__ __forceinline__ void warpcorr_views_body(const float* __restrict__ ref, const float* __restrict__ src,
+                                                    const float* __restrict__ rt_all,
+                                                    const float* __restrict__ depth, long dds, long dps,
+                                                    int h, int w, int D, float* sim_views,
+                                                    float* __restrict__ entropy) {
     using G = WarpGeom<C>;
-    const float* __restrict__ ref = effi_resolve_views(ref_arg, srcs);
     int x, y, sub;
     if (!tile_pixel<C>(blockIdx.x, gridDim.x, h, w, x, y, sub)) return;
     const int view = blockIdx.y;
-    const float* __restrict__ src = pick_view(srcs, view);
     const float* __restrict__ rt = rt_all + view * 12;
     const int hw = h * w, pix = y * w + x, sub4 = 4 * sub;
     const float4 r4 = *reinterpret_cast<const float4*>(ref + (long)pix * C + sub4);
@@ -190,6 +194,26 @@ __global__ __launch_bounds__(256) void warpcorr_views_kernel(const float* ref_ar
     }
     e = effi_group_sum<G::LPP>(e);
     if (sub == 0) entropy[(long)view * hw + pix] = e;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void warpcorr_views_kernel(const float* ref_arg, EffiPtrList srcs,
+                                                             const float* __restrict__ rt_all,
+                                                             const float* __restrict__ depth, long dds, long dps,
+                                                             int h, int w, int D, float* sim_views,
+                                                             float* __restrict__ entropy) {
+    warpcorr_views_body<C>(effi_resolve_views(ref_arg, srcs), pick_view(srcs, blockIdx.y), rt_all, depth, dds, dps, h, w, D, sim_views,
+                           entropy);
+}
+template <int C>
+__global__ __launch_bounds__(256) void warpcorr_views_batch_kernel(const float* ref_arg, EffiPtrList srcs,
+                                                                   const float* __restrict__ rt_all,
+                                                                   const float* __restrict__ depth, long dds, long dps,
+                                                                   int h, int w, int D, float* sim_views,
+                                                                   float* __restrict__ entropy, WarpBatch b) {
+    const long smp = blockIdx.z;
+    warpcorr_views_body<C>(ref_arg + smp * b.ref, pick_view_list(srcs, blockIdx.y) + smp * b.src, rt_all + smp * b.rt, depth + smp * b.depth,
+                           dds, dps, h, w, D, sim_views + smp * b.sim, entropy + smp * b.ent);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -545,6 +569,15 @@ __global__ __launch_bounds__(WIN_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
                                    h, w, D, sim_views, entropy, lds_px);
 }
 
+template <int MAXPX>
+__global__ __launch_bounds__(WIN_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void warpcorr_views_win_batch_kernel(
+    const float* __restrict__ ref_arg, EffiPtrList srcs, const float* __restrict__ rt_all, const float* __restrict__ depth, long dds,
+    int h, int w, int D, float* sim_views, float* __restrict__ entropy, int lds_px, WarpBatch b) {
+    const long smp = blockIdx.z;
+    warpcorr_views_win_body<MAXPX>(ref_arg + smp * b.ref, pick_view_list(srcs, blockIdx.y) + smp * b.src, rt_all + smp * b.rt,
+                                   depth + smp * b.depth, dds, h, w, D, sim_views + smp * b.sim, entropy + smp * b.ent, lds_px);
+}
+
 // ------------------------------------------------------------------------------------------------
 // stage 1 in SPLIT precision, CORRELATE FIRST (round 4; C = 32, hypotheses shared by all pixels, precision "split" / "bf16" only --
 // the exact-fp32 mode and training keep the kernel above).  BUILT, CORRECT (tests/test_gpu_kernels.py::test_warpcorr_views_matrix_core_form),
@@ -799,6 +832,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int view = blockIdx.y;
     warpcorr_views_mm_body<HI_ONLY>(TBL ? srcs.tbl[0] : ref_arg, TBL ? srcs.tbl[1 + view] : pick_view_list(srcs, view), rt_all, depth, dds,
                                     h, w, D, sim_views, entropy);
+}
+
+template <bool HI_ONLY>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void warpcorr_views_mm_batch_kernel(
+    const float* __restrict__ ref_arg, EffiPtrList srcs, const float* __restrict__ rt_all, const float* __restrict__ depth, long dds, int h,
+    int w, int D, float* sim_views, float* __restrict__ entropy, WarpBatch b) {
+    const long smp = blockIdx.z;
+    warpcorr_views_mm_body<HI_ONLY>(ref_arg + smp * b.ref, pick_view_list(srcs, blockIdx.y) + smp * b.src, rt_all + smp * b.rt,
+                                    depth + smp * b.depth, dds, h, w, D, sim_views + smp * b.sim, entropy + smp * b.ent);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1754,12 +1796,32 @@ static bool fill_table(const float* const* table_dev, int S, EffiPtrList& l) {
     return true;
 }
 
+// bt != nullptr: n_smp samples in one launch (pointer form only), the kernel form chosen by the same rules
 static int launch_warpcorr_views(const float* ref_nhwc, const EffiPtrList& l, int S, const float* rt, const float* depth, long dds,
-                                 long dps, int C, int h, int w, int D, float* sim_views, float* entropy, effi_stream_t stream) {
+                                 long dps, int C, int h, int w, int D, float* sim_views, float* entropy, effi_stream_t stream,
+                                 const WarpBatch* bt = nullptr, int n_smp = 1) {
     if (!rt || !depth || !sim_views || !entropy) return EFFI_ERR_BADARG;
     if (h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
     hipStream_t s = effi_s(stream);
     const int lds_px = warp_lds_px();
+    if (bt) {
+        if (l.tbl) return EFFI_ERR_UNSUPPORTED;
+        if (C == 32 && dps == 0 && lds_px >= 0 && D <= 256) {
+            const int tiles = ((w + WIN_TW - 1) / WIN_TW) * ((h + WIN_TH - 1) / WIN_TH);
+            hipLaunchKernelGGL((warpcorr_views_win_batch_kernel<WIN_MAXPX>), dim3(tiles, S, n_smp), dim3(WIN_THREADS), 0, s, ref_nhwc, l, rt,
+                               depth, dds, h, w, D, sim_views, entropy, lds_px, *bt);
+            EFFI_LAUNCH_CHECK();
+            return EFFI_OK;
+        }
+        switch (C) {
+            case 32: hipLaunchKernelGGL(warpcorr_views_batch_kernel<32>, dim3(grid_blocks<32>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
+            case 16: hipLaunchKernelGGL(warpcorr_views_batch_kernel<16>, dim3(grid_blocks<16>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
+            case 8:  hipLaunchKernelGGL(warpcorr_views_batch_kernel<8>, dim3(grid_blocks<8>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
+            default: return EFFI_ERR_UNSUPPORTED;
+        }
+        EFFI_LAUNCH_CHECK();
+        return EFFI_OK;
+    }
     if (C == 32 && dps == 0 && lds_px >= 0 && D <= 256) {
         // hypotheses shared by all pixels (the cascade's stage 1): taps served from an LDS window
         const int tiles = ((w + WIN_TW - 1) / WIN_TW) * ((h + WIN_TH - 1) / WIN_TH);
@@ -1794,12 +1856,24 @@ extern "C" int effi_warpcorr_views_f32(const float* ref_nhwc, const float* const
 // hi_only: bf16 operands (precision "bf16").
 static int launch_warpcorr_views_x3(const float* ref_nhwc, const EffiPtrList& l, int S, const float* rt, const float* depth, long dds,
                                     long dps, int C, int h, int w, int D, float* sim_views, float* entropy, int hi_only,
-                                    effi_stream_t stream) {
+                                    effi_stream_t stream, const WarpBatch* bt = nullptr, int n_smp = 1) {
     if (!rt || !depth || !sim_views || !entropy) return EFFI_ERR_BADARG;
     if (h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
     if (!(C == 32 && dps == 0 && D <= 256 && h < 32000 && w < 32000))
-        return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream);
+        return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream, bt, n_smp);
     hipStream_t s = effi_s(stream);
+    if (bt) {
+        if (l.tbl) return EFFI_ERR_UNSUPPORTED;
+        const dim3 bgrid(((w + 15) / 16) * ((h + 3) / 4), S, n_smp);
+        if (hi_only)
+            hipLaunchKernelGGL((warpcorr_views_mm_batch_kernel<true>), bgrid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views,
+                               entropy, *bt);
+        else
+            hipLaunchKernelGGL((warpcorr_views_mm_batch_kernel<false>), bgrid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views,
+                               entropy, *bt);
+        EFFI_LAUNCH_CHECK();
+        return EFFI_OK;
+    }
     const dim3 grid(((w + 15) / 16) * ((h + 3) / 4), S);
 #define EFFI_MM(TBL, HO) hipLaunchKernelGGL((warpcorr_views_mm_kernel<TBL, HO>), grid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views, entropy)
     if (l.tbl) { if (hi_only) EFFI_MM(true, true); else EFFI_MM(true, false); }
@@ -1815,6 +1889,36 @@ extern "C" int effi_warpcorr_views_x3_f32(const float* ref_nhwc, const float* co
     EffiPtrList l;
     if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
     return launch_warpcorr_views_x3(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, hi_only, stream);
+}
+
+static bool fill_warp_batch(WarpBatch& b, int n_smp, long ref_ss, long src_ss, long rt_ss, long depth_ss, long sim_ss, long ent_ss) {
+    if (n_smp < 1 || n_smp > 65535 || ref_ss < 0 || src_ss < 0 || rt_ss < 0 || depth_ss < 0 || sim_ss < 0 || ent_ss < 0) return false;
+    b = WarpBatch{ref_ss, src_ss, rt_ss, depth_ss, sim_ss, ent_ss};
+    return true;
+}
+
+extern "C" int effi_warpcorr_views_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
+                                             const float* depth, long dds, long dps, int C, int h, int w, int D, float* sim_views,
+                                             float* entropy, int n_smp, long ref_sstride, long src_sstride, long rt_sstride,
+                                             long depth_sstride, long sim_sstride, long entropy_sstride, effi_stream_t stream) {
+    EffiPtrList l;
+    WarpBatch b;
+    if (!fill_warp_batch(b, n_smp, ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride)) return EFFI_ERR_BADARG;
+    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
+    return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream, n_smp > 1 ? &b : nullptr, n_smp);
+}
+
+extern "C" int effi_warpcorr_views_x3_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
+                                                const float* depth, long dds, long dps, int C, int h, int w, int D, float* sim_views,
+                                                float* entropy, int hi_only, int n_smp, long ref_sstride, long src_sstride,
+                                                long rt_sstride, long depth_sstride, long sim_sstride, long entropy_sstride,
+                                                effi_stream_t stream) {
+    EffiPtrList l;
+    WarpBatch b;
+    if (!fill_warp_batch(b, n_smp, ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride)) return EFFI_ERR_BADARG;
+    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
+    return launch_warpcorr_views_x3(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, hi_only, stream,
+                                    n_smp > 1 ? &b : nullptr, n_smp);
 }
 
 extern "C" int effi_warpcorr_views_x3_tbl_f32(const float* const* view_table_dev, int S, const float* rt, const float* depth, long dds,

@@ -90,7 +90,7 @@ class PixelwiseNet2d(nn.Sequential):
         self._cache = packing.PackCache()
 
     def run(self, entropy):
-        """entropy [n,h,w] -> weights [n,h,w]."""
+        """entropy [n,h,w] -> weights [n,h,w] (a sample batch [b,S,h,w] is b * S planes of the same launch)."""
         _require_eval(self)
         t = []
         for i in range(3):
@@ -129,6 +129,27 @@ class DepthNet(nn.Module):
         return {"depth": d, "photometric_confidence": conf, **({"view_weights": weights} if weights is not None else {}),
                 "reg_volume": reg[0], "volume": volume.unsqueeze(0)}
 
+    @staticmethod
+    def run_batch(feats, pairs, depth, num_depth, cost_regularization, pixel_wise_net):
+        """``run`` for B samples in one pass of batched launches: feats list of [B,C,h,w]; pairs [B,N,2,4,4]; depth [B,D] or
+        [B,D,h,w] -> the dictionary of ``run`` with a leading B on every tensor, sample b bitwise ``run`` on sample b."""
+        B = feats[0].shape[0]
+        nhwc = ops.to_nhwc(feats)
+        rt = ops.compose_rel_proj(pairs if pairs[0].is_contiguous() else pairs.contiguous())
+        sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rt, depth, num_depth)
+        if pixel_wise_net is None:
+            weights = None
+        elif hasattr(pixel_wise_net, "run"):
+            weights = pixel_wise_net.run(entropy)
+        else:
+            S = entropy.shape[1]
+            weights = pixel_wise_net(entropy.flatten(0, 1).unsqueeze(1)).squeeze(1).contiguous().unflatten(0, (B, S))
+        volume = ops.view_aggregate(sim_views, weights)
+        reg, _ = cost_regularization.run(volume.unsqueeze(1))
+        d, conf = ops.softmax_regress_conf(reg[:, 0], depth)
+        return {"depth": d, "photometric_confidence": conf, **({"view_weights": weights} if weights is not None else {}),
+                "reg_volume": reg[:, 0], "volume": volume.unsqueeze(1)}
+
     @ops.on_tensor_device
 
     def forward(self, features, proj_matrices, depth_values, num_depth, cost_regularization, pixel_wise_net, G=8):
@@ -143,6 +164,11 @@ class DepthNet(nn.Module):
                                           "HIP path; the shipped model always passes its PixelwiseNet")
             from .. import train_path
             return train_path.depthnet(pixel_wise_net, cost_regularization, features, proj_matrices, depth_values)
+        if features[0].shape[0] > 1 and hasattr(cost_regularization, "run"):
+            res = self.run_batch(list(features), proj_matrices, depth_values, num_depth, cost_regularization, pixel_wise_net)
+            if pixel_wise_net is None:
+                res["view_weights"] = []
+            return res
         outs = []
         for b in range(features[0].shape[0]):
             outs.append(self.run([f[b] for f in features], proj_matrices[b].contiguous(), depth_values[b], num_depth,
@@ -322,16 +348,49 @@ class Effi_MVS_plus(nn.Module):
         self.cost_regularization = CostRegNet_2_sample_FPN3D_Fast(in_channels=self.G, base_channels=8)
 
     # -----------------------------------------------------------------------------------------
-    def _hot_single(self, feats, ctx, pairs, disp_range, want_intermediates=False):
+    def _stage1_batch(self, features, proj_matrices, depth_values):
+        """Set-up and stage-1 cost volume of ALL B samples in one pass of batched launches (what ``_hot_single`` does up to its
+        first update block): -> one dictionary per sample, views of the batched results, for ``_hot_single(stage1=...)``."""
+        D1 = self.depth_stage_nums[0]
+        B = depth_values.shape[0]
+        keys = ["stage{}".format(s + 1) for s in range(self.num_stage)]
+        disp_range = depth_values if depth_values[0].is_contiguous() else depth_values.contiguous()
+        pairs = [proj_matrices[k] if proj_matrices[k][0].is_contiguous() else proj_matrices[k].contiguous() for k in keys]
+        if self.num_stage <= 4 and ops.option("setup_fused"):
+            (hyp, misc), rts = ops.cascade_setup(disp_range, D1, pairs)
+        else:                                   # the separate set-up launches have no sample index: per sample, stacked
+            hm = [ops.stage1_hypotheses(disp_range[b], D1) for b in range(B)]
+            hyp, misc = torch.stack([x[0] for x in hm]), torch.stack([x[1] for x in hm])
+            per = [ops.compose_rel_proj_stages([p_[b] for p_ in pairs]) if self.num_stage <= 4 else
+                   [ops.compose_rel_proj(p_[b]) for p_ in pairs] for b in range(B)]
+            rts = [torch.stack([per[b][s] for b in range(B)]) for s in range(self.num_stage)]
+        nhwc = ops.to_nhwc([f[keys[0]] for f in features])
+        sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rts[0], hyp, D1, x3=bool(ops.option("warp_x3")))
+        weights = self.PixelwiseNet.run(entropy)
+        cur_vol = ops.view_aggregate(sim_views, weights)
+        reg_vol = self.cost_regularization.run(cur_vol.unsqueeze(1))[0][:, 0]
+        if ops.option("conf_fused"):
+            depth, c, inv_next, conf = ops.softmax_regress_conf(reg_vol, hyp, disp_range, conf_up=4)
+        else:
+            depth, c, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)
+            conf = None
+        return [{"hyp": hyp[b], "misc": misc[b], "rts": [r[b] for r in rts], "weights": weights[b], "cur_vol": cur_vol[b],
+                 "reg_vol": reg_vol[b], "depth": depth[b], "c": c[b], "inv_next": inv_next[b], "conf": None if conf is None else conf[b]}
+                for b in range(B)]
+
+    def _hot_single(self, feats, ctx, pairs, disp_range, want_intermediates=False, stage1=None):
         """One sample, unbatched.  feats: per view {stageK: [C,h,w]}; ctx {stageK: [hd+cd,h,w]};
-        pairs {stageK: [N,2,4,4]}; disp_range [384] ascending inverse depths."""
+        pairs {stageK: [N,2,4,4]}; disp_range [384] ascending inverse depths.  ``stage1``: this sample's slice of
+        ``_stage1_batch`` -- the set-up and the stage-1 cost volume are then taken from it instead of being launched."""
         D1 = self.depth_stage_nums[0]
         ops.mark("begin")
         keys = ["stage{}".format(s + 1) for s in range(self.num_stage)]
         # per-stage inputs that depend on nothing but the features / cameras / context pyramid: relative projections of all
         # stages in one launch -- the launch that also makes the stage-1 hypotheses (option setup_fused) --, tanh / relu halves of all
         # context maps (hidden state and context input of the update blocks) in one launch
-        if self.num_stage <= 4 and ops.option("setup_fused"):
+        if stage1 is not None:
+            hyp, misc, rts = stage1["hyp"], stage1["misc"], stage1["rts"]
+        elif self.num_stage <= 4 and ops.option("setup_fused"):
             (hyp, misc), rts = ops.cascade_setup(disp_range, D1, [pairs[k].contiguous() for k in keys])
         else:
             hyp, misc = ops.stage1_hypotheses(disp_range, D1)      # misc: 3 intervals, depth_min_, depth_max_
@@ -384,7 +443,7 @@ class Effi_MVS_plus(nn.Module):
                 return dict(enumerate(ops.split_tanh_relu_stages(cs, self.hdim_stage[:self.num_stage], self.cdim_stage[:self.num_stage])))
             return {s: ops.split_tanh_relu(cs[s], self.hdim_stage[s], self.cdim_stage[s]) for s in range(self.num_stage)}
 
-        geo = {0: geometry(0)}
+        geo = {0: geometry(0) if stage1 is None else ((), rts[0], feats[0][keys[0]].shape)}
         with ops.Branch() as prep_branch:        # what the stage-1 cost volume does not need (side stream when branches are on)
             st = all_states()
             for s in range(1, self.num_stage):
@@ -396,7 +455,15 @@ class Effi_MVS_plus(nn.Module):
             if s > 0:
                 ops.mark("stage{}".format(s))              # end of the previous stage
             nhwc, rt, (_, h, w) = geo[s]
-            if s == 0:
+            if s == 0 and stage1 is not None:
+                weights, cur_vol, reg_vol = stage1["weights"], stage1["cur_vol"], stage1["reg_vol"]
+                depth, c, inv_next, conf = stage1["depth"], stage1["c"], stage1["inv_next"], stage1["conf"]
+                if conf is None:
+                    with ops.Branch() as tail_branch:
+                        conf = ops.upsample_nearest(c.unsqueeze(0), 4)[0]
+                preds.append(depth)
+                lo_cur, hi_cur = g_min, g_max
+            elif s == 0:
                 if table is not None:
                     sim_views, entropy = ops.warpcorr_views_tbl(table, 0, rt, hyp, D1, x3=bool(ops.option("warp_x3")))
                 else:
@@ -507,12 +574,18 @@ class Effi_MVS_plus(nn.Module):
         B = depth_values.shape[0]
         if isinstance(features, ops.ViewTable) and B != 1:
             raise ValueError("forward_hot: a ViewTable describes ONE sample (B = 1)")
+        # B > 1 (tensor features): the set-up and the stage-1 cost volume of all samples run ONCE in batched launches; the update
+        # blocks and stages 2-3 then run per sample on slices of those results.  Bitwise the per-sample loop.
+        stage1 = None
+        if B > 1 and not isinstance(features, ops.ViewTable):
+            stage1 = self._stage1_batch(features, proj_matrices, depth_values)
         outs = []
         for b in range(B):
             feats = features if isinstance(features, ops.ViewTable) else [{k: v[b] for k, v in f.items()} for f in features]
             ctx = {k: v[b] for k, v in cnet_depth.items()}
             pairs = {k: v[b].contiguous() for k, v in proj_matrices.items()}
-            outs.append(self._hot_single(feats, ctx, pairs, depth_values[b].contiguous(), want_intermediates))
+            outs.append(self._hot_single(feats, ctx, pairs, depth_values[b].contiguous(), want_intermediates,
+                                         stage1=None if stage1 is None else stage1[b]))
         res = {"depth": [_stack([o["depth"][i] for o in outs]) for i in range(len(outs[0]["depth"]))],
                "photometric_confidence": _stack([o["photometric_confidence"] for o in outs])}
         if want_intermediates:

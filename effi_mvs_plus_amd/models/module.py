@@ -66,14 +66,16 @@ class Conv3d(nn.Module):
         return self._cache.get(t, lambda: packing.pack_conv3d(self.conv, self.bn))
 
     def run(self, srcs, skip=None):
-        """srcs: list of unbatched planar [Ci,D,h,w] tensors (channel concatenation) -> [cout,Do,ho,wo]."""
+        """srcs: list of planar [Ci,D,h,w] tensors (channel concatenation) -> [cout,Do,ho,wo]; or a sample batch, every tensor
+        [n,Ci,D,h,w] -> [n,cout,Do,ho,wo]: the same kernel form (chosen by the same rules) over all samples in ONE launch, sample i
+        bitwise ``run`` on sample i."""
         _require_eval(self)
         if _triple(self.conv.kernel_size) != (3, 3, 3) or _triple(self.conv.padding) != (1, 1, 1):
             raise NotImplementedError("Conv3d: only kernel 3 / padding 1 is instantiated on the HIP path")
         t = None
-        cin_total = sum(x.shape[0] for x in srcs)
+        cin_total = sum(x.shape[-4] for x in srcs)
         if (skip is None and _triple(self.conv.stride) == (1, 1, 1) and 1 < self.out_channels <= 32 and len(srcs) <= 2
-                and cin_total in (8, 16) and srcs[0].shape[0] % 8 == 0 and srcs[0].shape[-1] % 4 == 0
+                and cin_total in (8, 16) and srcs[0].shape[-4] % 8 == 0 and srcs[0].shape[-1] % 4 == 0
                 and ops.uses_split() and ops.option("roll") != 0):
             # 8 / 16 input channels: rolling window of input planes in LDS, each plane fetched once
             t = [self.conv.weight, self.conv.bias]
@@ -125,6 +127,8 @@ class Conv3d(nn.Module):
         if self.training:                      # BatchNorm on batch statistics, differentiable: forward AND backward on HIP kernels
             from .. import train_path
             return train_path.conv3d_block(self, [x])
+        if x.shape[0] > 1:                     # all samples in one launch
+            return self.run([x if x[0].is_contiguous() else x.contiguous()])
         return _stack([self.run([x[i].contiguous()]) for i in range(x.shape[0])])
 
 
@@ -154,7 +158,7 @@ class Deconv3d(nn.Module):
         if _triple(self.conv.kernel_size) != (3, 3, 3) or pad != (1, 1, 1) or st[1:] != (2, 2) or \
                 op != (st[0] - 1, 1, 1) or st[0] not in (1, 2):
             raise NotImplementedError("Deconv3d: only k3 / p1 / stride (s,2,2) / output_padding (s-1,1,1) is instantiated")
-        if st == (2, 2, 2) and x.shape[0] % 16 == 0 and self.out_channels <= 16 and ops.uses_split():
+        if st == (2, 2, 2) and x.shape[-4] % 16 == 0 and self.out_channels <= 16 and ops.uses_split():    # (x may be a sample batch [n,C,D,h,w])
             t = [self.conv.weight, self.conv.bias]
             if self.bn is not None:
                 t += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
@@ -169,6 +173,8 @@ class Deconv3d(nn.Module):
         if self.training:
             from .. import train_path
             return train_path.deconv3d_block(self, x)
+        if x.shape[0] > 1:                     # all samples in one launch
+            return self.run(x if x[0].is_contiguous() else x.contiguous())
         return _stack([self.run(x[i].contiguous()) for i in range(x.shape[0])])
 
 
@@ -404,9 +410,10 @@ class CostRegNet_2_sample_FPN3D_Fast(nn.Module):
 
     def run(self, vol):
         """vol planar [cin,D,h,w] -> (prob [1,D,h,w], pro [b,D,h,w]); skip adds are fused into the
-        transposed-conv epilogues (added after their ReLU, models/module.py:460-461)."""
+        transposed-conv epilogues (added after their ReLU, models/module.py:460-461).  A sample batch [n,cin,D,h,w] goes through the
+        same nine launches -> ([n,1,D,h,w], [n,b,D,h,w])."""
         _require_eval(self)
-        _, D, h, w = vol.shape
+        D, h, w = vol.shape[-3:]
         if D % 4 or h % 4 or w % 4:
             raise ValueError(f"cost volume dims {D}x{h}x{w} must be multiples of 4 (two stride-2 levels)")
         c1 = self.conv1.run([self.conv0.run([vol])])
@@ -424,6 +431,8 @@ class CostRegNet_2_sample_FPN3D_Fast(nn.Module):
         if self.training:
             from .. import train_path
             return train_path.cost_regnet(self, x)
+        if x.shape[0] > 1:                     # one launch per layer for all samples
+            return self.run(x if x[0].is_contiguous() else x.contiguous())
         outs = [self.run(x[i].contiguous()) for i in range(x.shape[0])]
         return _stack([o[0] for o in outs]), _stack([o[1] for o in outs])
 

@@ -1,7 +1,9 @@
 """Tensor-level wrappers over the C ABI.  PyTorch is used for device memory and the current stream only.
 
 All functions take fp32 CUDA (ROCm) tensors without a batch dimension and enqueue on the current
-stream.  CPU tensors raise: there is no fallback path.
+stream.  CPU tensors raise: there is no fallback path.  The feature pyramid's convolutions (image batches) and the wrappers of the
+stage-1 cost volume (sample batches, ``_smp`` below) also take a leading batch dimension: ONE launch, element i bitwise the
+unbatched call on element i.
 """
 from __future__ import annotations
 
@@ -354,7 +356,14 @@ def _int_array(vals):
 
 # ---------------------------------------------------------------------------------------------
 def compose_rel_proj(pairs: torch.Tensor) -> torch.Tensor:
-    """pairs [N,2,4,4] -> rt [N-1,12]  (K.[R|t] then P_src . P_ref^-1)."""
+    """pairs [N,2,4,4] -> rt [N-1,12]  (K.[R|t] then P_src . P_ref^-1).  Sample batch: [n,N,2,4,4] -> [n,N-1,12], one launch."""
+    pairs = _samples(pairs)
+    if pairs.dim() == 5:
+        n, ps = _smp(pairs, 4, "pairs")
+        rt = torch.empty(n, pairs.shape[1] - 1, 12, device=pairs.device, dtype=torch.float32)
+        check(_lib.lib().effi_compose_rel_proj_f32_batch(_p(pairs), pairs.shape[1], _p(rt), n, ps, rt.stride(0), _stream()),
+              "effi_compose_rel_proj_f32_batch")
+        return rt
     _t(pairs, "pairs")
     n = pairs.shape[0]
     rt = torch.empty(n - 1, 12, device=pairs.device, dtype=torch.float32)
@@ -375,8 +384,84 @@ def compose_rel_proj_stages(pairs_list):
     return [rt[k] for k in range(len(pairs_list))]
 
 
+# ---- sample batches of the stage-1 cost volume ----------------------------------------------------------------------------------
+def _smp(x, nd, name):
+    """Sample form of one tensor argument: ``nd`` dims = ONE tensor (in a batched call: shared by all samples, stride 0), ``nd + 1``
+    dims = [n, ...] with contiguous samples at ANY uniform sample stride (a slice of a larger allocation is fine; an expanded
+    leading dimension is stride 0) -> (n or None, sample stride in floats)."""
+    _t(x, name, contiguous=False)
+    if x.dim() == nd:
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        return None, 0
+    if x.dim() != nd + 1 or x.shape[0] < 1:
+        raise ValueError(f"{name}: expected {nd} dimensions, or {nd + 1} with a leading sample dimension, got {tuple(x.shape)}")
+    if not x[0].is_contiguous():
+        raise ValueError(f"{name}: every sample of a batch must be contiguous (the sample stride itself is free)")
+    return x.shape[0], (x.stride(0) if x.shape[0] > 1 else 0)
+
+
+def _smp_count(counts, what):
+    """The one sample count of a call's tensors (None entries = unbatched tensors); ValueError when they disagree."""
+    ns = {c for c in counts if c is not None}
+    if len(ns) > 1:
+        raise ValueError(f"{what}: sample counts differ ({sorted(ns)})")
+    return ns.pop() if ns else None
+
+
+def as_samples(tensors):
+    """n per-sample tensors of one shape -> ONE [n, ...] view over them when they sit at a uniform sample stride inside one
+    allocation (no copy), else None.  The batched wrappers pass list arguments through it (``_samples``)."""
+    t0 = tensors[0]
+    if len(tensors) == 1:
+        return t0.unsqueeze(0)
+    if any(t.shape != t0.shape or t.stride() != t0.stride() or t.dtype != t0.dtype or t.device != t0.device
+           or t.untyped_storage().data_ptr() != t0.untyped_storage().data_ptr() for t in tensors):
+        return None
+    step = tensors[1].storage_offset() - t0.storage_offset()
+    if step < 0 or any(t.storage_offset() - t0.storage_offset() != i * step for i, t in enumerate(tensors)):
+        return None
+    return t0.as_strided((len(tensors),) + tuple(t0.shape), (step,) + tuple(t0.stride()), t0.storage_offset())
+
+
+def _samples(x):
+    """A wrapper's tensor argument given as a list of per-sample tensors -> [n, ...]: ``as_samples``' view when the samples sit at a
+    uniform stride in one allocation, else one gathered copy (``torch.stack``).  Tensors (and None) pass through."""
+    if not isinstance(x, (list, tuple)):
+        return x
+    if not x:
+        raise ValueError("an empty list of samples")
+    v = as_samples(x)
+    return torch.stack(list(x)) if v is None else v
+
+
+def _cascade_setup_batch(disp_range, D, pairs_list):
+    n, rs = _smp(disp_range, 1, "disp_range")
+    strides = []
+    for p_ in pairs_list:
+        m, ps = _smp(p_, 4, "pairs")
+        if m != n:
+            raise ValueError(f"cascade_setup: sample counts differ ({n} ranges, {m} camera sets)")
+        strides.append(ps)
+    nv = pairs_list[0].shape[1]
+    if len(pairs_list) > 4 or any(p_.shape[1] != nv for p_ in pairs_list):
+        raise ValueError("cascade_setup: up to 4 stages with the same number of views")
+    dev = disp_range.device
+    depths = torch.empty(n, D, device=dev, dtype=torch.float32)
+    intervals = torch.empty(n, 5, device=dev, dtype=torch.float32)
+    rt = torch.empty(n, len(pairs_list), nv - 1, 12, device=dev, dtype=torch.float32)
+    check(_lib.lib().effi_cascade_setup_f32_batch(_p(disp_range), disp_range.shape[1], D, _p(depths), _p(intervals), _ptr_array(pairs_list),
+                                                  len(pairs_list), nv, _p(rt), n, rs, D, 5, _long_array(strides), rt.stride(0), _stream()),
+          "effi_cascade_setup_f32_batch")
+    return (depths, intervals), [rt[:, k] for k in range(len(pairs_list))]
+
+
 def cascade_setup(disp_range, D, pairs_list):
-    """``stage1_hypotheses`` and ``compose_rel_proj_stages`` in one launch -> ((depths [D], intervals [5]), [rt [N-1,12], ...])."""
+    """``stage1_hypotheses`` and ``compose_rel_proj_stages`` in one launch -> ((depths [D], intervals [5]), [rt [N-1,12], ...]).
+    Sample batch: disp_range [n,R] and pairs [n,N,2,4,4] -> ((depths [n,D], intervals [n,5]), [rt [n,N-1,12], ...]), one launch."""
+    disp_range, pairs_list = _samples(disp_range), [_samples(p_) for p_ in pairs_list]
+    if disp_range.dim() == 2:
+        return _cascade_setup_batch(disp_range, D, pairs_list)
     _t(disp_range, "disp_range")
     for p_ in pairs_list:
         _t(p_, "pairs")
@@ -399,9 +484,35 @@ def rel_proj(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch.Tensor:
     return rt
 
 
+def _to_nhwc_batch(feats):
+    """``to_nhwc`` of [n,C,h,w] maps -> [n,h,w,C] maps: passed through when every sample is channel-last in memory, else ALL of
+    them are transposed into one [n,N,h,w,C] allocation (one uniform sample stride for the batched warp)."""
+    n, C_, h, w = feats[0].shape
+    for f in feats:
+        _t(f, "feature", contiguous=False)
+        if tuple(f.shape) != (n, C_, h, w):
+            raise ValueError("to_nhwc: feature maps of a batch must share one shape")
+    if C_ > 1 and all(f[0].permute(1, 2, 0).is_contiguous() for f in feats):
+        return [f.permute(0, 2, 3, 1) for f in feats]
+    dst = torch.empty(n, len(feats), h, w, C_, device=feats[0].device, dtype=torch.float32)
+    src_l, dst_l = [], []
+    for v, f in enumerate(feats):
+        for b in range(n):
+            if not f[b].is_contiguous():
+                raise ValueError("feature map must be planar-contiguous or channels-last")
+            src_l.append(f[b])
+            dst_l.append(dst[b, v])
+    for k in range(0, len(src_l), MAX_VIEWS + 1):
+        s_, d_ = src_l[k:k + MAX_VIEWS + 1], dst_l[k:k + MAX_VIEWS + 1]
+        check(_lib.lib().effi_planar_to_nhwc_f32(_ptr_array(s_), _ptr_array(d_), len(s_), C_, h * w, _stream()), "effi_planar_to_nhwc_f32")
+    return [dst[:, v] for v in range(len(feats))]
+
+
 def to_nhwc(feats):
     """list of planar [C,h,w] maps -> list of channel-last [h,w,C] maps.  A map that is already
-    channel-last in memory (torch.channels_last) is passed through without a copy."""
+    channel-last in memory (torch.channels_last) is passed through without a copy.  Sample batch: [n,C,h,w] maps -> [n,h,w,C]."""
+    if feats[0].dim() == 4:
+        return _to_nhwc_batch(feats)
     out, todo_src, todo_dst = [None] * len(feats), [], []
     for i, f in enumerate(feats):
         _t(f, "feature", contiguous=False)
@@ -456,10 +567,74 @@ def homo_warp_bwd(rt, depth, D, grad_out, h, w):
     return g_src
 
 
+def _depth_strides_batch(depth, n, D, h, w):
+    """Hypotheses of a batched call -> (tensor, dstride, pstride, sample stride): [D] shared by all samples, [n,D], or [n,D,h,w]
+    (contiguous, or expanded over the map as the reference passes them)."""
+    _t(depth, "depth", contiguous=False)
+    if depth.dim() not in (1, 2, 4):
+        raise ValueError(f"depth hypotheses: expected [D], [n,D] or [n,D,h,w], got {tuple(depth.shape)}")
+    if depth.shape[min(1, depth.dim() - 1)] != D or (depth.dim() == 4 and tuple(depth.shape[2:]) != (h, w)):
+        raise ValueError(f"depth hypotheses: {tuple(depth.shape)} do not hold D = {D} hypotheses" + (f" on a {h} x {w} map" if depth.dim() == 4 else ""))
+    if depth.dim() == 1:
+        return (depth if depth.is_contiguous() else depth.contiguous()), 1, 0, 0
+    if depth.shape[0] != n:
+        raise ValueError(f"depth hypotheses: sample counts differ ({n} and {depth.shape[0]})")
+    if depth.dim() == 2:
+        if depth.stride(1) != 1 or depth.stride(0) < 0:
+            depth = depth.contiguous()
+        return depth, 1, 0, (depth.stride(0) if n > 1 else 0)
+    if depth.stride(2) == 0 and depth.stride(3) == 0 and depth.stride(1) >= 0 and depth.stride(0) >= 0:
+        return depth, depth.stride(1), 0, (depth.stride(0) if n > 1 else 0)
+    if not depth.is_contiguous():
+        depth = depth.contiguous()
+    return depth, h * w, 1, (depth.stride(0) if n > 1 else 0)
+
+
+def _warpcorr_views_batch(ref_nhwc, srcs_nhwc, rt, depth, D, x3):
+    n, rs = _smp(ref_nhwc, 3, "ref_nhwc")
+    _, h, w, Cc = ref_nhwc.shape
+    S = len(srcs_nhwc)
+    sstr = set()
+    for s_ in srcs_nhwc:
+        m, ss = _smp(s_, 3, "src_nhwc")
+        if tuple(s_.shape[1:]) != (h, w, Cc):
+            raise ValueError("source / reference feature shapes differ")
+        if m != n:
+            raise ValueError(f"warpcorr_views: sample counts differ ({n} and {m})")
+        sstr.add(ss)
+    m, rts = _smp(rt, 2, "rt")
+    if m != n:
+        raise ValueError(f"warpcorr_views: sample counts differ ({n} maps, {m} projection sets)")
+    if rt.shape[1] != S:
+        raise ValueError("Different number of images and projection matrices")
+    if len(sstr) > 1:               # sources at different sample strides: not expressible as pointer list + ONE stride -> per sample
+        outs = [warpcorr_views(ref_nhwc[b], [s_[b] for s_ in srcs_nhwc], rt[b], depth if depth.dim() == 1 else depth[b], D, x3=x3)
+                for b in range(n)]
+        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+    depth, dds, dps, dss = _depth_strides_batch(depth, n, D, h, w)
+    sim = torch.empty(n, S, D, h, w, device=ref_nhwc.device, dtype=torch.float32)
+    ent = torch.empty(n, S, h, w, device=ref_nhwc.device, dtype=torch.float32)
+    work = lambda: {"flops": n * S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * n * h * w * (S * Cc + Cc + S * D + S)}
+    tail = (n, rs, sstr.pop(), rts, dss, sim.stride(0), ent.stride(0), _stream())
+    if x3 and uses_split():
+        check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_x3_f32_batch, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
+                    _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), int(_PRECISION == "bf16"), *tail),
+              "effi_warpcorr_views_x3_f32_batch")
+        return sim, ent
+    check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_f32_batch, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
+                _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), *tail), "effi_warpcorr_views_f32_batch")
+    return sim, ent
+
+
 def warpcorr_views(ref_nhwc, srcs_nhwc, rt, depth, D, x3=False):
-    """-> (sim_views [S,D,h,w], entropy [S,h,w]).  ``x3``: in "split" / "bf16" precision use the matrix-core form
+    """-> (sim_views [S,D,h,w], entropy [S,h,w]).  Sample batch: ref [n,h,w,C], sources [n,h,w,C] each, rt [n,S,12], depth [D]
+    (shared), [n,D] or [n,D,h,w] -> (sim_views [n,S,D,h,w], entropy [n,S,h,w]) in ONE launch when the sources share one sample
+    stride (else one launch per sample).  ``x3``: in "split" / "bf16" precision use the matrix-core form
     (``effi_warpcorr_views_x3_f32``: correlations of the tap pixels as split-precision MFMAs, then interpolated) -- inference only;
     the default is the exact fp32 kernel (what training and the exact-fp32 precision use)."""
+    ref_nhwc, srcs_nhwc, rt, depth = _samples(ref_nhwc), [_samples(s_) for s_ in srcs_nhwc], _samples(rt), _samples(depth)
+    if ref_nhwc.dim() == 4:
+        return _warpcorr_views_batch(ref_nhwc, srcs_nhwc, rt, depth, D, x3)
     h, w, Cc = ref_nhwc.shape
     S = len(srcs_nhwc)
     _t(ref_nhwc, "ref_nhwc"), _t(rt, "rt"), _t(depth, "depth", contiguous=False)
@@ -586,6 +761,10 @@ def warpcorr_dyn_tbl(table, stage, rt, cur_depth, interval, view_w, D):
 
 
 def pixelwise_net(entropy, params):
+    """entropy [n,h,w] -> weights [n,h,w]; a sample batch [b,S,h,w] is the same launch on b * S planes."""
+    if entropy.dim() == 4:
+        _t(entropy, "entropy")
+        return pixelwise_net(entropy.flatten(0, 1), params).view(entropy.shape)
     n, h, w = entropy.shape
     _t(entropy, "entropy"), _t(params, "params")
     out = torch.empty_like(entropy)
@@ -596,6 +775,19 @@ def pixelwise_net(entropy, params):
 
 def view_aggregate(sim_views, weights):
     """sum_v sim_v w_v / (sum_v w_v + 1e-6); ``weights`` None = the plain mean over the views (pixel_wise_net = None)."""
+    sim_views, weights = _samples(sim_views), _samples(weights)
+    if sim_views.dim() == 5:            # sample batch: sim_views [n,S,D,h,w], weights [n,S,h,w] or None -> [n,D,h,w], one launch
+        n, ss = _smp(sim_views, 4, "sim_views")
+        _, S, D, h, w = sim_views.shape
+        ws = 0
+        if weights is not None:
+            m, ws = _smp(weights, 3, "weights")
+            if m != n or weights.shape[1] != S:
+                raise ValueError(f"view_aggregate: sample / view counts differ ({n} x {S} volumes, weights {tuple(weights.shape)})")
+        out = torch.empty(n, D, h, w, device=sim_views.device, dtype=torch.float32)
+        check(_lib.lib().effi_view_aggregate_f32_batch(_p(sim_views), _p(weights), S, D, h * w, _p(out), n, ss, ws, out.stride(0),
+                                                       _stream()), "effi_view_aggregate_f32_batch")
+        return out
     S, D, h, w = sim_views.shape
     _t(sim_views, "sim_views")
     if weights is not None:
@@ -630,8 +822,44 @@ def warpcorr_dyn(ref_nhwc, srcs_nhwc, rt, cur_depth, interval, view_w, D):
     return sim, samples
 
 
-def conv3d_k3(srcs, weight, bias, cout, stride=(1, 1, 1), relu=True, skip=None):
-    """srcs: list of planar [Ci,D,h,w]; weight packed [cin,27,cout]; -> [cout,Do,ho,wo]."""
+def _vol_samples(srcs, skip, what):
+    """(n, source strides, skip stride) of a batched 3-D convolution's tensors [n,C,D,h,w]."""
+    forms = [_smp(s_, 4, what + " input") for s_ in srcs]
+    n = _smp_count([f[0] for f in forms] + ([skip.shape[0]] if skip is not None and skip.dim() == 5 else []), what)
+    if any(f[0] is None for f in forms):
+        raise ValueError(f"{what}: every source of a batched call must be [n,C,D,h,w]")
+    if any(tuple(s_.shape[-3:]) != tuple(srcs[0].shape[-3:]) for s_ in srcs):
+        raise ValueError(f"{what}: the sources must share one (D, h, w), got {[tuple(s_.shape) for s_ in srcs]}")
+    ks = 0
+    if skip is not None:
+        m, ks = _smp(skip, 4, "skip")
+        if m != n:
+            raise ValueError(f"{what}: skip must be [n, ...] with n = {n}")
+    return n, [f[1] for f in forms], ks
+
+
+def conv3d_k3(srcs, weight, bias, cout, stride=(1, 1, 1), relu=True, skip=None, out=None):
+    """srcs: list of planar [Ci,D,h,w]; weight packed [cin,27,cout]; -> [cout,Do,ho,wo].  Sample batch (here and in the other 3-D
+    convolution wrappers): sources / skip [n,...] -> [n,cout,Do,ho,wo] in one launch; ``out`` may be [n,...] slices of a larger
+    allocation."""
+    srcs, skip = [_samples(s_) for s_ in srcs], _samples(skip)
+    if srcs[0].dim() == 5:
+        n, sstr, ks = _vol_samples(srcs, skip, "conv3d")
+        D, h, w = srcs[0].shape[-3:]
+        sz, sxy = int(stride[0]), int(stride[1])
+        Do, ho, wo = (D - 1) // sz + 1, (h - 1) // sxy + 1, (w - 1) // sxy + 1
+        out = _batch_out(out, (n, cout, Do, ho, wo), srcs[0].device, "conv3d output")
+        if skip is not None:
+            assert skip.shape == out.shape
+        cin = sum(s_.shape[1] for s_ in srcs)
+        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * Do * ho * wo,
+                        "bytes": 4.0 * n * (cin * D * h * w + cout * Do * ho * wo * (2 if skip is not None else 1))}
+        check(_call(f"conv3d_c{'8' if cout % 8 == 0 else '1'}_s{sz}{sxy}", work, _lib.lib().effi_conv3d_k3_f32_batch, _ptr_array(srcs),
+                    _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(weight), _p(bias), cout, D, h, w, sz, sxy, int(relu),
+                    _p(skip), _p(out), n, _long_array(sstr), ks, out.stride(0) if n > 1 else 0, _stream()), "effi_conv3d_k3_f32_batch")
+        return out
+    if out is not None:
+        raise ValueError("conv3d_k3: out= belongs to the batched call")
     for s in srcs:
         _t(s, "conv3d input")
     _, D, h, w = srcs[0].shape
@@ -652,6 +880,15 @@ def conv3d_k3(srcs, weight, bias, cout, stride=(1, 1, 1), relu=True, skip=None):
 
 def conv3d_k3s1_mfma(x, wpack, bias, cout, relu=True):
     """x planar [cin,D,h,w]; stride-1 3-D conv as z-batched 2-D MFMA convs -> [cout,D,h,w]."""
+    x = _samples(x)
+    if x.dim() == 5:
+        n, xs = _smp(x, 4, "conv3d input")
+        _, cin, D, h, w = x.shape
+        out = torch.empty(n, cout, D, h, w, device=x.device, dtype=torch.float32)
+        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
+        check(_call(f"conv3d_mfma_nt{cout // 16}", work, _lib.lib().effi_conv3d_k3s1_mfma_f32_batch, _p(x), cin, _p(wpack), _p(bias), cout,
+                    D, h, w, int(relu), _p(out), n, xs, out.stride(0), _stream()), "effi_conv3d_k3s1_mfma_f32_batch")
+        return out
     _t(x, "conv3d input")
     cin, D, h, w = x.shape
     out = torch.empty(cout, D, h, w, device=x.device, dtype=torch.float32)
@@ -664,6 +901,17 @@ def conv3d_k3s1_mfma(x, wpack, bias, cout, relu=True):
 def conv3d_k3s1_bf16x3(srcs, wpack, bias, cout, relu=True):
     """srcs: planar [Ci,D,h,w] tensors (channel concatenation); stride-1 3-D conv as z-batched 2-D convs in split precision
     (``packing.pack_conv3d_planes_bf16x3``) -> [cout,D,h,w].  w % 4 == 0, cout <= 32."""
+    srcs = [_samples(s_) for s_ in srcs]
+    if srcs[0].dim() == 5:
+        n, sstr, _ = _vol_samples(srcs, None, "conv3d")
+        D, h, w = srcs[0].shape[-3:]
+        cin = sum(s_.shape[1] for s_ in srcs)
+        out = torch.empty(n, cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
+        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
+        check(_call(f"conv3d_x3_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_bf16x3_f32_batch"), _ptr_array(srcs), _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(wpack),
+                    _p(bias), cout, D, h, w, int(relu), _p(out), n, _long_array(sstr), out.stride(0), _stream()),
+              "effi_conv3d_k3s1_bf16x3_f32_batch")
+        return out
     for s in srcs:
         _t(s, "conv3d input")
     _, D, h, w = srcs[0].shape
@@ -679,6 +927,17 @@ def conv3d_k3s1_bf16x3(srcs, wpack, bias, cout, relu=True):
 def conv3d_k3s1_roll(srcs, wpack, bias, cout, relu=True):
     """srcs: one or two planar [Ci,D,h,w] tensors, 8 or 16 channels in total; stride-1 3-D conv with a rolling window of
     input planes in split precision (``packing.pack_conv3d_roll_bf16x3``) -> [cout,D,h,w].  w % 4 == 0, cout <= 32."""
+    srcs = [_samples(s_) for s_ in srcs]
+    if srcs[0].dim() == 5:
+        n, sstr, _ = _vol_samples(srcs, None, "conv3d")
+        D, h, w = srcs[0].shape[-3:]
+        cin = sum(s_.shape[1] for s_ in srcs)
+        out = torch.empty(n, cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
+        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
+        check(_call(f"conv3d_roll_oct{cin // 8}_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_roll_bf16x3_f32_batch"), _ptr_array(srcs), _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(wpack),
+                    _p(bias), cout, D, h, w, int(relu), _p(out), n, _long_array(sstr), out.stride(0), _stream()),
+              "effi_conv3d_k3s1_roll_bf16x3_f32_batch")
+        return out
     for s in srcs:
         _t(s, "conv3d input")
     _, D, h, w = srcs[0].shape
@@ -691,9 +950,24 @@ def conv3d_k3s1_roll(srcs, wpack, bias, cout, relu=True):
     return out
 
 
+def _conv3d_s2_batch(x, wpack, bias, cout, relu, key, fn, what):
+    """The stride-(2,2,2) forms on [n,cin,D,h,w] in one launch."""
+    n, xs = _smp(x, 4, "conv3d input")
+    _, cin, D, h, w = x.shape
+    Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    out = torch.empty(n, cout, Do, ho, wo, device=x.device, dtype=torch.float32)
+    work = lambda: {"flops": 2.0 * 27 * n * cin * cout * Do * ho * wo, "bytes": 4.0 * n * (cin * D * h * w + cout * Do * ho * wo)}
+    check(_call(key, work, fn, _p(x), cin, _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out), n, xs, out.stride(0), _stream()), what)
+    return out
+
+
 def conv3d_k3s2_x3(x, wpack, bias, cout, relu=True):
     """x planar [cin,D,h,w] (w % 4 == 0); stride-(2,2,2) 3-D conv in split precision (``packing.pack_conv3d_s2_bf16x3``) ->
     [cout,Do,ho,wo]."""
+    x = _samples(x)
+    if x.dim() == 5:
+        return _conv3d_s2_batch(x, wpack, bias, cout, relu, f"conv3d_s2x3_nt{(cout + 15) // 16}", _x3("effi_conv3d_k3s2_bf16x3_f32_batch"),
+                                "effi_conv3d_k3s2_bf16x3_f32_batch")
     _t(x, "conv3d input")
     cin, D, h, w = x.shape
     Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -706,6 +980,10 @@ def conv3d_k3s2_x3(x, wpack, bias, cout, relu=True):
 
 def conv3d_k3s2_mfma(x, wpack, bias, cout, relu=True):
     """x planar [cin,D,h,w]; stride-(2,2,2) 3-D conv as z-batched stride-2 2-D MFMA convs -> [cout,Do,ho,wo]."""
+    x = _samples(x)
+    if x.dim() == 5:
+        return _conv3d_s2_batch(x, wpack, bias, cout, relu, f"conv3d_mfma_s2_nt{cout // 16}", _lib.lib().effi_conv3d_k3s2_mfma_f32_batch,
+                                "effi_conv3d_k3s2_mfma_f32_batch")
     _t(x, "conv3d input")
     cin, D, h, w = x.shape
     Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -716,7 +994,26 @@ def conv3d_k3s2_mfma(x, wpack, bias, cout, relu=True):
     return out
 
 
+def _deconv3d_batch(x, wp, bias, cout, sz, relu, skip, key, fn, what, with_sz):
+    """The transposed forms on [n,cin,D,h,w] (+ skip [n,...]) in one launch."""
+    n, (xs,), ks = _vol_samples([x], skip, "deconv3d")
+    _, cin, D, h, w = x.shape
+    out = torch.empty(n, cout, sz * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
+    if skip is not None:
+        assert skip.shape == out.shape, f"skip {tuple(skip.shape)} vs out {tuple(out.shape)}"
+    work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w,
+                    "bytes": 4.0 * n * (cin * D * h * w + cout * sz * D * 4 * h * w * (2 if skip is not None else 1))}
+    args = (_p(x), cin, _p(wp), _p(bias), cout, D, h, w) + ((sz,) if with_sz else ()) + (int(relu), _p(skip), _p(out), n, xs, ks,
+                                                                                      out.stride(0) if n > 1 else 0, _stream())
+    check(_call(key, work, fn, *args), what)
+    return out
+
+
 def deconv3d_k3(x, weight, bias, cout, sz=2, relu=True, skip=None):
+    x, skip = _samples(x), _samples(skip)
+    if x.dim() == 5:
+        return _deconv3d_batch(x, weight, bias, cout, sz, relu, skip, f"deconv3d_c{cout if cout == 1 else 8}_s{sz}",
+                               _lib.lib().effi_deconv3d_k3_f32_batch, "effi_deconv3d_k3_f32_batch", True)
     _t(x, "deconv3d input")
     cin, D, h, w = x.shape
     out = torch.empty(cout, sz * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
@@ -733,6 +1030,10 @@ def deconv3d_k3(x, weight, bias, cout, sz=2, relu=True, skip=None):
 def deconv3d_k3s2_x3(x, wpack, bias, cout, relu=True, skip=None):
     """Transposed 3-D conv, stride (2,2,2), on the bf16 matrix cores in split precision
     (``packing.pack_deconv3d_s2_bf16x3``): x [cin,D,h,w] -> [cout,2D,2h,2w] (+ skip after the ReLU)."""
+    x, skip = _samples(x), _samples(skip)
+    if x.dim() == 5:
+        return _deconv3d_batch(x, wpack, bias, cout, 2, relu, skip, "deconv3d_x3", _x3("effi_deconv3d_k3s2_bf16x3_f32_batch"),
+                               "effi_deconv3d_k3s2_bf16x3_f32_batch", False)
     _t(x, "deconv3d input")
     cin, D, h, w = x.shape
     out = torch.empty(cout, 2 * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
@@ -895,10 +1196,40 @@ def resize_planar(x, dst_h, dst_w, out=None):
     return out
 
 
+def _softmax_regress_conf_batch(logits, depth, disp_range, conf_up):
+    """``softmax_regress_conf`` on logits [n,D,h,w] with hypotheses [D] / [n,D] / [n,D,h,w] and per-sample disp_range [n,R] (or one
+    [R] for all): every result with a leading n, one launch."""
+    n, ls = _smp(logits, 3, "logits")
+    _, D, h, w = logits.shape
+    depth, dds, dps, dss = _depth_strides_batch(depth, n, D, h, w)
+    dev = logits.device
+    od = torch.empty(n, h, w, device=dev, dtype=torch.float32)
+    oc = torch.empty(n, h, w, device=dev, dtype=torch.float32)
+    oi, n_range, rs = None, 0, 0
+    if disp_range is not None:
+        m, rs = _smp(disp_range, 1, "disp_range")
+        if m is not None and m != n:
+            raise ValueError(f"softmax_regress_conf: sample counts differ ({n} volumes, {m} ranges)")
+        oi, n_range = torch.empty(n, h, w, device=dev, dtype=torch.float32), disp_range.shape[-1]
+    if conf_up:
+        ou = torch.empty(n, h * conf_up, w * conf_up, device=dev, dtype=torch.float32)
+        check(_lib.lib().effi_softmax_regress_conf_up_f32_batch(_p(logits), _p(depth), dds, dps, D, h, w, _p(od), _p(oc), _p(disp_range),
+                                                                 n_range, _p(oi), _p(ou), conf_up, n, ls, dss, h * w, h * w, rs, h * w,
+                                                                 ou.stride(0), _stream()), "effi_softmax_regress_conf_up_f32_batch")
+        return (od, oc, ou) if disp_range is None else (od, oc, oi, ou)
+    check(_lib.lib().effi_softmax_regress_conf_f32_batch(_p(logits), _p(depth), dds, dps, D, h * w, _p(od), _p(oc), _p(disp_range), n_range,
+                                                          _p(oi), n, ls, dss, h * w, h * w, rs, h * w, _stream()),
+          "effi_softmax_regress_conf_f32_batch")
+    return (od, oc) if disp_range is None else (od, oc, oi)
+
+
 def softmax_regress_conf(logits, depth, disp_range=None, conf_up=0):
     """logits [D,h,w]; depth [D] / [D,h,w] -> (depth [h,w], confidence [h,w]) and, with ``disp_range``, also the regressed
     depth as normalised inverse depth (``depth_to_inv`` of it, written by the same kernel).  ``conf_up`` = f > 0: the result
     tuple ends with the confidence replicated f x f ([h*f,w*f], ``upsample_nearest`` of it) written by the same kernel."""
+    logits, depth, disp_range = _samples(logits), _samples(depth), _samples(disp_range)
+    if logits.dim() == 4:
+        return _softmax_regress_conf_batch(logits, depth, disp_range, conf_up)
     D, h, w = logits.shape
     _t(logits, "logits"), _t(depth, "depth", contiguous=False)
     depth, dds, dps = _depth_strides(depth, D, h, w)

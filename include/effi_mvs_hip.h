@@ -11,8 +11,9 @@
  *   - every pointer is a DEVICE pointer owned by the caller unless the comment says "host".
  *   - returns 0 (EFFI_OK) or a negative error code; never throws, allocates, frees or synchronises.
  *   - re-entrant; work is enqueued on `stream` of the current device; graph-capture safe.
- *   - tensors are fp32, batch size 1 per call (the host loops over the batch); layouts are spelled
- *     out per argument.  "planar" = [C][H][W] (torch NCHW with N=1), "nhwc" = [H][W][C].
+ *   - tensors are fp32, batch size 1 per call (the host loops over the batch) EXCEPT the entries with the suffix _batch: the
+ *     feature pyramid's convolutions over n_img images and the stage-1 cost volume over n_smp samples, one launch each (their
+ *     blocks below).  Layouts are spelled out per argument.  "planar" = [C][H][W] (torch NCHW with N=1), "nhwc" = [H][W][C].
  */
 #ifndef EFFI_MVS_HIP_H
 #define EFFI_MVS_HIP_H
@@ -400,6 +401,83 @@ int effi_conv2d_k5s2_bf16x3_f32_batch(const float* in, int cin, const void* wpac
 int effi_conv2d_k3_twice_bf16x3_f32_batch(const float* in, int cin, const void* w1_bf16, const float* bias1, const void* w2_bf16,
                                           const float* bias2, int cout, int h, int w, float* out, int n_img, long in_istride,
                                           long out_istride, effi_stream_t stream);
+/* ---- Sample batches of the stage-1 cost volume (suffix _batch): n_smp samples in ONE launch.
+ * The reference's operators take [B, ...] tensors end to end (models/Effi_MVS_plus.py:14-89 DepthNet.forward, models/module.py:435-463
+ * the regulariser); these are the entries DepthNet.run launches plus the set-up in front of it.  Same convention as the image
+ * batches above: the arguments of the entry without the suffix, then n_smp (<= 65535), then one sample stride per tensor in floats
+ * (sample i of a tensor starts i * stride behind the pointer given); a stride of 0 shares the tensor between all samples; weights
+ * and bias are always shared.  A workgroup derives (sample, tile) from the grid, offsets its pointers once and runs the single-
+ * sample body: sample i of the result is BITWISE what the entry without the suffix computes on sample i.  Tile shapes that do not
+ * enter an output's accumulation order (rows per wave, planes per thread / per window run) follow the workgroup count of all
+ * samples.  n_smp == 1 is the single-sample launch itself.
+ *
+ * effi_cascade_setup_f32 (models/Effi_MVS_plus.py:34-37,413-424,464-474) for n_smp depth ranges and camera sets: disp_range
+ * [n_smp][n_range] -> depths [n_smp][D], intervals [n_smp][5]; pairs = HOST array of n_stages device pointers (sample 0 of each
+ * stage), pairs_sstride = HOST array of their n_stages sample strides; rt_out [n_smp][n_stages][n_views-1][12] at rt_sstride. */
+int effi_cascade_setup_f32_batch(const float* disp_range, int n_range, int D, float* depths, float* intervals,
+                                 const float* const* pairs, int n_stages, int n_views, float* rt_out, int n_smp,
+                                 long range_sstride, long depths_sstride, long intervals_sstride, const long* pairs_sstride,
+                                 long rt_sstride, effi_stream_t stream);
+/* effi_compose_rel_proj_f32 (models/Effi_MVS_plus.py:34-37, models/module.py:314-316) for n_smp camera sets: pairs
+ * [n_smp][n_views][2][4][4] at pairs_sstride -> rt_out [n_smp][n_views-1][12] at rt_sstride (DepthNet.forward on a batch, which is
+ * handed its hypotheses and needs the projections alone). */
+int effi_compose_rel_proj_f32_batch(const float* pairs, int n_views, float* rt_out, int n_smp, long pairs_sstride, long rt_sstride,
+                                    effi_stream_t stream);
+/* effi_warpcorr_views_f32 / effi_warpcorr_views_x3_f32 (models/Effi_MVS_plus.py:38-44, models/module.py:303-344) with the sample as
+ * the grid's third index, in all three kernel forms (LDS window, direct gather, matrix cores), chosen by the rules of the
+ * single-sample entries.  src_nhwc: HOST array of S device pointers = the S source maps of sample 0; src_sstride is the ONE sample
+ * stride every source shares (the maps of a batched pyramid pass sit at a uniform stride).  depth_sstride 0 = the hypotheses of
+ * sample 0 for every sample.  sim_views [n_smp][S][D][h][w] at sim_sstride, entropy [n_smp][S][h][w] at entropy_sstride. */
+int effi_warpcorr_views_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
+                                  const float* depth, long depth_dstride, long depth_pstride, int C, int h, int w, int D,
+                                  float* sim_views, float* entropy, int n_smp, long ref_sstride, long src_sstride, long rt_sstride,
+                                  long depth_sstride, long sim_sstride, long entropy_sstride, effi_stream_t stream);
+int effi_warpcorr_views_x3_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
+                                     const float* depth, long depth_dstride, long depth_pstride, int C, int h, int w, int D,
+                                     float* sim_views, float* entropy, int hi_only, int n_smp, long ref_sstride, long src_sstride,
+                                     long rt_sstride, long depth_sstride, long sim_sstride, long entropy_sstride,
+                                     effi_stream_t stream);
+/* effi_view_aggregate_f32 (models/Effi_MVS_plus.py:48-58,67-70); weights == NULL: the unweighted branch for every sample. */
+int effi_view_aggregate_f32_batch(const float* sim_views, const float* weights, int S, int D, int hw, float* out, int n_smp,
+                                  long sim_sstride, long weights_sstride, long out_sstride, effi_stream_t stream);
+/* effi_softmax_regress_conf_f32 / effi_softmax_regress_conf_up_f32 (models/Effi_MVS_plus.py:79-88,479,538) with per-sample
+ * hypotheses (depth_sstride; 0 = shared) and per-sample disp_range (range_sstride).  f == 4: out_conf_up_sstride % 4 == 0. */
+int effi_softmax_regress_conf_f32_batch(const float* logits, const float* depth, long depth_dstride, long depth_pstride, int D,
+                                        int hw, float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                        float* out_depth_inv, int n_smp, long logits_sstride, long depth_sstride,
+                                        long out_depth_sstride, long out_conf_sstride, long range_sstride,
+                                        long out_depth_inv_sstride, effi_stream_t stream);
+int effi_softmax_regress_conf_up_f32_batch(const float* logits, const float* depth, long depth_dstride, long depth_pstride, int D,
+                                           int h, int w, float* out_depth, float* out_conf, const float* disp_range, int n_range,
+                                           float* out_depth_inv, float* out_conf_up, int f, int n_smp, long logits_sstride,
+                                           long depth_sstride, long out_depth_sstride, long out_conf_sstride, long range_sstride,
+                                           long out_depth_inv_sstride, long out_conf_up_sstride, effi_stream_t stream);
+/* The 3-D convolutions of the regulariser (models/module.py:124-160,168-203,435-463) in every form Conv3d / Deconv3d select.
+ * src_sstride has n_src entries; skip_sstride belongs to skip (ignored when skip is NULL), out_sstride to out (it may exceed a
+ * sample: the outputs may be slices of a larger allocation). */
+int effi_conv3d_k3_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const float* weight, const float* bias,
+                             int cout, int D, int h, int w, int sz, int sxy, int relu, const float* skip, float* out, int n_smp,
+                             const long* src_sstride, long skip_sstride, long out_sstride, effi_stream_t stream);
+int effi_deconv3d_k3_f32_batch(const float* in, int cin, const float* weight, const float* bias, int cout, int D, int h, int w,
+                               int sz, int relu, const float* skip, float* out, int n_smp, long in_sstride, long skip_sstride,
+                               long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s1_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w,
+                                    int relu, float* out, int n_smp, long in_sstride, long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s2_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w,
+                                    int relu, float* out, int n_smp, long in_sstride, long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s1_bf16x3_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                      const float* bias, int cout, int D, int h, int w, int relu, float* out, int n_smp,
+                                      const long* src_sstride, long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s1_roll_bf16x3_f32_batch(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                           const float* bias, int cout, int D, int h, int w, int relu, float* out, int n_smp,
+                                           const long* src_sstride, long out_sstride, effi_stream_t stream);
+/* (planes * n_smp <= 65535 for the stride-2 form: sample and plane share one grid index) */
+int effi_conv3d_k3s2_bf16x3_f32_batch(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h,
+                                      int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
+                                      effi_stream_t stream);
+int effi_deconv3d_k3s2_bf16x3_f32_batch(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h,
+                                        int w, int relu, const float* skip, float* out, int n_smp, long in_sstride,
+                                        long skip_sstride, long out_sstride, effi_stream_t stream);
 /* 7x7, one input channel (convd1, models/update.py:76,90): in [h][w]; weight [49][cout]
  * (host-packed), bias [cout]; out planar [cout][h][w] = relu(conv + bias).  cout in {16,32,48}. */
 int effi_conv2d_c1k7_relu_f32(const float* in, const float* weight, const float* bias, int cout,
@@ -726,6 +804,19 @@ int effi_csp_gen_roll_bf16x3_pair_f32_bf16(const float* x, int D, int H, int W, 
                                       const void* w1_b, const float* b1_b, float* out_b, effi_stream_t stream);
 int effi_deconv3d_k3s2_bf16x3_f32_bf16(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout,
                                   int D, int h, int w, int relu, const float* skip, float* out, effi_stream_t stream);
+/* ... and of the regulariser's split-precision sample batches */
+int effi_conv3d_k3s1_bf16x3_f32_batch_bf16(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                           const float* bias, int cout, int D, int h, int w, int relu, float* out, int n_smp,
+                                           const long* src_sstride, long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s1_roll_bf16x3_f32_batch_bf16(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
+                                                const float* bias, int cout, int D, int h, int w, int relu, float* out, int n_smp,
+                                                const long* src_sstride, long out_sstride, effi_stream_t stream);
+int effi_conv3d_k3s2_bf16x3_f32_batch_bf16(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h,
+                                           int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
+                                           effi_stream_t stream);
+int effi_deconv3d_k3s2_bf16x3_f32_batch_bf16(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
+                                             int h, int w, int relu, const float* skip, float* out, int n_smp, long in_sstride,
+                                             long skip_sstride, long out_sstride, effi_stream_t stream);
 
 /* ---- scope row n3, DTU branch: reproject_with_depth + check_geometric_consistency + the array part of filter_depth,
  * test_dtu_dypcd.py:164-333 (the reference runs it with numpy / cv2 on the host, one scan per pool worker).  PARITY UNPINNED: cv2
