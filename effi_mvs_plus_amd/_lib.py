@@ -23,6 +23,13 @@ SIGNATURES = {
     "effi_fusion_dynamic_filter_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp],
     "effi_fusion_dtu_filter_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "effi_fusion_dtu_filter_scan_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "effi_fusion_dynamic_filter_scan_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp],
+    "effi_fusion_compact_blocks": [_i, _i, _i],
+    "effi_fusion_compact_scan_tile": [],
+    "effi_fusion_compact_count_u8": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "effi_fusion_compact_scatter_f32": [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
     "effi_fusion_vis_filter_f32": [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp],
     "effi_fusion_points_f32": [_i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_dtu_reproject_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],

@@ -39,21 +39,43 @@ __device__ void fus_invert(const double* A, int n, double* inv) {           // G
         for (int c = 0; c < n; ++c) inv[r * n + c] = M[r][c + n];
 }
 
-// cams: view 0 = reference ([2][4][4]: extrinsic, intrinsic in the top-left 3x3), views 1..V = sources
-__global__ void fusion_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
-                                      float* __restrict__ mats) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > V) return;
-    const float* cam = (v == 0) ? ref_cam : src_cams + (long)(v - 1) * 32;
+// one view's K[9] Kinv[9] E[16] Einv[16] from its camera [2][4][4] (extrinsic, intrinsic in the top-left 3x3)
+__device__ void fus_prepare_view(const float* __restrict__ cam, float* __restrict__ m) {
     double K[9], Ki[9], E[16], Ei[16];
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) K[r * 3 + c] = (double)cam[16 + r * 4 + c];
     for (int i = 0; i < 16; ++i) E[i] = (double)cam[i];
     fus_invert(K, 3, Ki);
     fus_invert(E, 4, Ei);
-    float* m = mats + (long)v * MAT_STRIDE;
     for (int i = 0; i < 9; ++i) { m[i] = (float)K[i]; m[9 + i] = (float)Ki[i]; }
     for (int i = 0; i < 16; ++i) { m[18 + i] = (float)E[i]; m[34 + i] = (float)Ei[i]; }
+}
+
+// cams: view 0 = reference ([2][4][4]: extrinsic, intrinsic in the top-left 3x3), views 1..V = sources
+__global__ void fusion_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
+                                      float* __restrict__ mats) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v > V) return;
+    fus_prepare_view((v == 0) ? ref_cam : src_cams + (long)(v - 1) * 32, mats + (long)v * MAT_STRIDE);
+}
+
+// Pair table of a scan launch: row r = [reference id, source ids ..., -1 padding], 1 + v_max ints.  The entry points validate the
+// HOST copy of the table (ids inside the scan, source counts, padding only at the end) before any kernel reads the device copy.
+__device__ __forceinline__ int fus_row_sources(const int* __restrict__ row, int v_max) {
+    int n = 0;
+    while (n < v_max && row[1 + n] >= 0) ++n;
+    return n;
+}
+
+// scan variant: mats [n_ref][v_max+1][52], one thread per (reference view, slot); slots past a row's source count stay unwritten
+__global__ void fusion_prepare_scan_kernel(const float* __restrict__ cams, const int* __restrict__ table, int n_ref, int v_max,
+                                           float* __restrict__ mats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_ref * (v_max + 1)) return;
+    const int r = i / (v_max + 1), v = i - r * (v_max + 1);
+    const int id = table[(long)r * (v_max + 1) + v];
+    if (id < 0) return;
+    fus_prepare_view(cams + (long)id * 32, mats + (long)i * MAT_STRIDE);
 }
 
 struct V3 { float x, y, z; };
@@ -115,15 +137,16 @@ __device__ __forceinline__ float sample_bilinear_zero(const float* __restrict__ 
     return at(y0, x0) * nw + at(y0, x0 + 1) * ne + at(y0 + 1, x0) * sw + at(y0 + 1, x0 + 1) * se;
 }
 
-__global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
-    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w,
+// The filter of ONE reference pixel p, shared by the single-view kernel and the scan kernel: every pointer is already the reference
+// view's own (``src_of(s)`` = depth map of its s-th source), so both launches run one arithmetic.
+template <class SrcOf>
+__device__ __forceinline__ void fusion_dynamic_filter_pixel(
+    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
     const float* __restrict__ mats, const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base,
     float rel_base, int relative, float* __restrict__ out_depth, unsigned char* __restrict__ out_geo,
     unsigned char* __restrict__ out_prob, unsigned char* __restrict__ out_mask, float* __restrict__ out_points,
     float* __restrict__ out_xyd) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const long hw = (long)h * w;
-    if (p >= hw) return;
     const int y = p / w, x = p - y * w;
     const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
     const float* Mr = mats;
@@ -140,7 +163,7 @@ __global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
         const float* Ms = mats + (long)(s + 1) * MAT_STRIDE;
         const V4 c = xform<true>(Ms + 18, world);
         const V3 im = cam2img<true>(Ms, c);
-        const float ds = sample_bilinear_zero(src_depths + (long)s * hw, h, w, im.x, im.y);
+        const float ds = sample_bilinear_zero(src_of(s), h, w, im.x, im.y);
         const V4 sc = img2cam<false>(Ms + 9, im.x, im.y, ds);
         const V4 sw = xform<false>(Ms + 34, sc);
         const V4 rc = xform<false>(Mr + 18, sw);
@@ -192,6 +215,39 @@ __global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
     }
 }
 
+__global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
+    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w,
+    const float* __restrict__ mats, const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base,
+    float rel_base, int relative, float* __restrict__ out_depth, unsigned char* __restrict__ out_geo,
+    unsigned char* __restrict__ out_prob, unsigned char* __restrict__ out_mask, float* __restrict__ out_points,
+    float* __restrict__ out_xyd) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    fusion_dynamic_filter_pixel(p, ref_depth, [=](int s) { return src_depths + (long)s * hw; }, V, h, w, mats, conf, ch, cw, prob_thr,
+                                dh, dist_base, rel_base, relative, out_depth, out_geo, out_prob, out_mask, out_points, out_xyd);
+}
+
+// Scan launch: blockIdx.y = row r of the pair table, so no workgroup straddles two reference views.  depths [n_views][h][w] is read
+// in place through the table's ids; conf [n_ref][ch][cw]; outputs [n_ref][h][w] / points [n_ref][3][h][w].
+__global__ __launch_bounds__(256) void fusion_dynamic_filter_scan_kernel(
+    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base, float rel_base, int relative,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
+    unsigned char* __restrict__ out_mask, float* __restrict__ out_points) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    const int r = blockIdx.y;
+    const int* row = table + (long)r * (v_max + 1);
+    const int V = fus_row_sources(row, v_max);
+    fusion_dynamic_filter_pixel(p, depths + (long)row[0] * hw, [=](int s) { return depths + (long)row[1 + s] * hw; }, V, h, w,
+                                mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + (long)r * ch * cw : nullptr, ch, cw, prob_thr,
+                                dh, dist_base, rel_base, relative, out_depth + r * hw, out_geo ? out_geo + r * hw : nullptr,
+                                out_prob ? out_prob + r * hw : nullptr, out_mask ? out_mask + r * hw : nullptr,
+                                out_points ? out_points + 3 * r * hw : nullptr, nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // DTU branch of row n3: reproject_with_depth + check_geometric_consistency + the array part of filter_depth of the reference's
 // test_dtu_dypcd.py:164-333 (the numpy / cv2 filter its DTU driver runs per scan on the host, in a multiprocessing pool), one thread
@@ -204,10 +260,7 @@ __global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
 // their dtypes, OpenCV's published remap algorithm restated).  Matrix inverses / products are formed once per view in double and
 // rounded to float32 (the reference: single-precision LAPACK / float32 matmul; ~1e-7 relative apart).
 // per view: ref: K[9] Kinv[9] E[16] Einv[16]; source s: K[9] Kinv[9] T_ref->src[16] = E_s . E_ref^-1, T_src->ref[16] = E_ref . E_s^-1
-__global__ void fusion_dtu_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
-                                          float* __restrict__ mats) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > V) return;
+__device__ void fus_dtu_prepare_view(const float* __restrict__ ref_cam, const float* __restrict__ src_cam, float* __restrict__ m) {
     auto load = [](const float* cam, double* K, double* E) {
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) K[r * 3 + c] = (double)cam[16 + r * 4 + c];
@@ -216,14 +269,13 @@ __global__ void fusion_dtu_prepare_kernel(const float* __restrict__ ref_cam, con
     double K[9], Ki[9], E[16], Ei[16], Kr[9], Er[16], Eri[16];
     load(ref_cam, Kr, Er);
     fus_invert(Er, 4, Eri);
-    float* m = mats + (long)v * MAT_STRIDE;
-    if (v == 0) {
+    if (!src_cam) {                                                         // the reference view's own slot
         fus_invert(Kr, 3, Ki);
         for (int i = 0; i < 9; ++i) { m[i] = (float)Kr[i]; m[9 + i] = (float)Ki[i]; }
         for (int i = 0; i < 16; ++i) { m[18 + i] = (float)Er[i]; m[34 + i] = (float)Eri[i]; }
         return;
     }
-    load(src_cams + (long)(v - 1) * 32, K, E);
+    load(src_cam, K, E);
     fus_invert(K, 3, Ki);
     fus_invert(E, 4, Ei);
     for (int i = 0; i < 9; ++i) { m[i] = (float)K[i]; m[9 + i] = (float)Ki[i]; }
@@ -237,6 +289,24 @@ __global__ void fusion_dtu_prepare_kernel(const float* __restrict__ ref_cam, con
             m[18 + r * 4 + c] = (float)a;
             m[34 + r * 4 + c] = (float)b;
         }
+}
+
+__global__ void fusion_dtu_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
+                                          float* __restrict__ mats) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v > V) return;
+    fus_dtu_prepare_view(ref_cam, v == 0 ? nullptr : src_cams + (long)(v - 1) * 32, mats + (long)v * MAT_STRIDE);
+}
+
+// scan variant (layout and table as fusion_prepare_scan_kernel): the per-pair products of every (reference, source) pair in one launch
+__global__ void fusion_dtu_prepare_scan_kernel(const float* __restrict__ cams, const int* __restrict__ table, int n_ref, int v_max,
+                                               float* __restrict__ mats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_ref * (v_max + 1)) return;
+    const int r = i / (v_max + 1), v = i - r * (v_max + 1);
+    const int* row = table + (long)r * (v_max + 1);
+    if (row[v] < 0) return;
+    fus_dtu_prepare_view(cams + (long)row[0] * 32, v == 0 ? nullptr : cams + (long)row[v] * 32, mats + (long)i * MAT_STRIDE);
 }
 
 struct D3 { double x, y, z; };
@@ -296,14 +366,15 @@ __device__ __forceinline__ DtuReproj dtu_reproject_pixel(const float* __restrict
     return r;
 }
 
-__global__ __launch_bounds__(256) void fusion_dtu_filter_kernel(
-    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w, const float* __restrict__ mats,
+// The DTU filter of ONE reference pixel p, shared by the single-view kernel and the scan kernel (pointers already the reference
+// view's own, ``src_of(sv)`` = depth map of its sv-th source).
+template <class SrcOf>
+__device__ __forceinline__ void fusion_dtu_filter_pixel(
+    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w, const float* __restrict__ mats,
     const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
     float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
     unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const long hw = (long)h * w;
-    if (p >= hw) return;
     const int y = p / w, x = p - y * w;
     const double xd = (double)x, yd = (double)y;
     const float* Mr = mats;
@@ -323,7 +394,7 @@ __global__ __launch_bounds__(256) void fusion_dtu_filter_kernel(
     int nlast = 0;
     for (int sv = 0; sv < V; ++sv) {
         const float* Ms = mats + (long)(sv + 1) * MAT_STRIDE;
-        const DtuReproj rr = dtu_reproject_pixel(Mr, Ms, src_depths + (long)sv * hw, h, w, xd, yd, dref);     // (:164-205)
+        const DtuReproj rr = dtu_reproject_pixel(Mr, Ms, src_of(sv), h, w, xd, yd, dref);     // (:164-205)
         const float depth_rep = rr.depth_rep, xr = rr.x_rep, yr = rr.y_rep;
         const double dxr = (double)xr - xd, dyr = (double)yr - yd;
         const double dist = sqrt(dxr * dxr + dyr * dyr);                                                       // (:218) float32 - int64 -> float64
@@ -361,6 +432,37 @@ __global__ __launch_bounds__(256) void fusion_dtu_filter_kernel(
         out_points[hw + p] = (float)pw.y;
         out_points[2 * hw + p] = (float)pw.z;
     }
+}
+
+__global__ __launch_bounds__(256) void fusion_dtu_filter_kernel(
+    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
+    unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    fusion_dtu_filter_pixel(p, ref_depth, [=](int sv) { return src_depths + (long)sv * hw; }, V, h, w, mats, conf, conf_thr, conf_keep,
+                            s_lo, e_hi, dist_base, diff_base, out_depth, out_photo, out_geo, out_final, out_points);
+}
+
+// Scan launch (grid and layouts as fusion_dynamic_filter_scan_kernel); conf [n_ref][h][w], already at the depth size.
+__global__ __launch_bounds__(256) void fusion_dtu_filter_scan_kernel(
+    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
+    unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    const int r = blockIdx.y;
+    const int* row = table + (long)r * (v_max + 1);
+    const int V = fus_row_sources(row, v_max);
+    fusion_dtu_filter_pixel(p, depths + (long)row[0] * hw, [=](int sv) { return depths + (long)row[1 + sv] * hw; }, V, h, w,
+                            mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + r * hw : nullptr, conf_thr, conf_keep, s_lo, e_hi,
+                            dist_base, diff_base, out_depth + r * hw, out_photo ? out_photo + r * hw : nullptr,
+                            out_geo ? out_geo + r * hw : nullptr, out_final ? out_final + r * hw : nullptr,
+                            out_points ? out_points + 3 * r * hw : nullptr);
 }
 
 // reproject_with_depth (test_dtu_dypcd.py:164-205) and, with ``masks``, check_geometric_consistency (:208-233) for one
@@ -469,7 +571,207 @@ __global__ __launch_bounds__(256) void fusion_points_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Ordered compaction of a scan's survivors (the host side of test_dtu_dypcd.py:327-333 and test_tank.py:517-533: boolean indexing of
+// the points and the reference image, view after view, then np.concatenate).  Vertex order = reference views in table order, row-major
+// survivors within a view.  Three kernels and no atomics, so the arrays are bitwise reproducible: (1) survivors per workgroup
+// (64-bit ballot popcount per wave, the waves combined through LDS), (2) one exclusive scan over the n_ref * blocks_per_view counts,
+// which also leaves the per-view vertex ranges, (3) scatter: rank inside the wave from the ballot bits below the lane, plus the bases
+// of the wave and of the workgroup.  A workgroup covers 256 consecutive pixels of ONE view (blockIdx.y = view).
+constexpr int CMP_THREADS = 256, CMP_WAVES = CMP_THREADS / 64;
+constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 4, SCAN_WAVES = SCAN_THREADS / 64;
+constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;          // counts per pass of the scan kernel's loop
+
+__global__ __launch_bounds__(CMP_THREADS) void fusion_compact_count_kernel(const unsigned char* __restrict__ mask, int hw,
+                                                                           int* __restrict__ counts) {
+    __shared__ int wave_n[CMP_WAVES];
+    const int p = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const bool m = p < hw && mask[(long)blockIdx.y * hw + p] != 0;
+    const unsigned long long b = __ballot(m);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int i = 0; i < CMP_WAVES; ++i) n += wave_n[i];
+        counts[(long)blockIdx.y * gridDim.x + blockIdx.x] = n;
+    }
+}
+
+// In place: counts[i] -> number of survivors before workgroup i.  One workgroup walks the array in tiles of SCAN_TILE and carries the
+// running total; offsets[v] = survivors before view v (v = 0 .. n_views, the last entry the total M).
+__global__ __launch_bounds__(SCAN_THREADS) void fusion_compact_scan_kernel(int* __restrict__ counts, int n, int blocks_per_view,
+                                                                           int* __restrict__ offsets) {
+    __shared__ int wave_sum[SCAN_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += SCAN_TILE) {
+        const int i0 = base + tid * SCAN_ITEMS;
+        int v[SCAN_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            v[k] = (i0 + k < n) ? counts[i0 + k] : 0;
+            sum += v[k];
+        }
+        int inc = sum;                                          // inclusive scan of the threads' sums inside the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wave_sum[wv] = inc;
+        __syncthreads();
+        int before = 0, tile = 0;
+#pragma unroll
+        for (int j = 0; j < SCAN_WAVES; ++j) {
+            const int ws = wave_sum[j];
+            if (j < wv) before += ws;
+            tile += ws;
+        }
+        int run = carry + before + inc - sum;
+#pragma unroll
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            const int i = i0 + k;
+            if (i < n) {
+                counts[i] = run;
+                if (i % blocks_per_view == 0) offsets[i / blocks_per_view] = run;
+                run += v[k];
+            }
+        }
+        carry += tile;
+        __syncthreads();                                        // wave_sum is rewritten by the next tile
+    }
+    if (tid == 0) offsets[n / blocks_per_view] = carry;
+}
+
+// points [n_ref][3][h][w]; image of row r = images + view * img_view_stride with view = table ? table[r * table_stride] : r, channel c of
+// pixel p at p * pix_stride + c * ch_stride ([h][w][3]: 3, 1; [3][h][w]: 1, h*w).  Colour = (uint8)(c * 255.0f): one multiply, truncation.
+__global__ __launch_bounds__(CMP_THREADS) void fusion_compact_scatter_kernel(
+    const unsigned char* __restrict__ mask, const float* __restrict__ points, const float* __restrict__ images, const int* __restrict__ table,
+    int table_stride, long img_view_stride, long pix_stride, long ch_stride, int hw, const int* __restrict__ block_base,
+    float* __restrict__ xyz, unsigned char* __restrict__ rgb) {
+    __shared__ int wave_n[CMP_WAVES];
+    const int p = blockIdx.x * CMP_THREADS + threadIdx.x, r = blockIdx.y;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool m = p < hw && mask[(long)r * hw + p] != 0;
+    const unsigned long long b = __ballot(m);
+    if (lane == 0) wave_n[wv] = __popcll(b);
+    __syncthreads();
+    if (!m) return;
+    long dst = block_base[(long)r * gridDim.x + blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+    for (int j = 0; j < wv; ++j) dst += wave_n[j];
+    const float* pt = points + (long)r * 3 * hw + p;
+    const int view = table ? table[(long)r * table_stride] : r;
+    const float* px = images + (long)view * img_view_stride + (long)p * pix_stride;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        xyz[dst * 3 + c] = pt[(long)c * hw];
+        rgb[dst * 3 + c] = (unsigned char)(int)(px[c * ch_stride] * 255.0f);
+    }
+}
+
 }  // namespace
+
+// Host-side check of a pair table [n_ref][1 + v_max] (row = reference id, source ids, -1 padding at the end only): every id inside
+// [0, n_views), at least min_src and at most FUS_MAX_VIEWS sources per row.
+static int fus_check_table(const int* table, int n_ref, int v_max, int n_views, int min_src) {
+    if (!table || n_ref < 1 || n_ref > 65535 || v_max < 1 || v_max > FUS_MAX_VIEWS || n_views < 1) return EFFI_ERR_BADARG;
+    for (int r = 0; r < n_ref; ++r) {
+        const int* row = table + (long)r * (v_max + 1);
+        if (row[0] < 0 || row[0] >= n_views) return EFFI_ERR_BADARG;
+        int n = 0;
+        while (n < v_max && row[1 + n] >= 0) ++n;
+        for (int k = 0; k < v_max; ++k)
+            if (k < n ? row[1 + k] >= n_views : row[1 + k] != -1) return EFFI_ERR_BADARG;
+        if (n < min_src) return EFFI_ERR_BADARG;
+    }
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_dtu_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                               const int* pair_table, int n_ref, int v_max, int h, int w, const float* confidence,
+                                               float conf_threshold, float conf_keep, int s, int e, float dist_base, float diff_base,
+                                               float* mats_scratch, float* out_depth, unsigned char* out_photo_mask,
+                                               unsigned char* out_geo_mask, unsigned char* out_final_mask, float* out_points,
+                                               effi_stream_t stream) {
+    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
+    if (h < 2 || w < 2 || s < 1 || e <= s || dist_base <= 0.0f || diff_base <= 0.0f) return EFFI_ERR_BADARG;
+    if (e - s > DTU_MAX_THR) return EFFI_ERR_UNSUPPORTED;
+    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, 1) != EFFI_OK) return EFFI_ERR_BADARG;
+    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_dtu_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table,
+                       n_ref, v_max, mats_scratch);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_dtu_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table, v_max,
+                       h, w, mats_scratch, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, out_depth, out_photo_mask,
+                       out_geo_mask, out_final_mask, out_points);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_dynamic_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                                   const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf,
+                                                   int conf_h, int conf_w, float prob_threshold, int dh_view_num, float dist_base,
+                                                   float rel_diff_base, int relative, float* mats_scratch, float* out_depth,
+                                                   unsigned char* out_geo_mask, unsigned char* out_prob_mask, unsigned char* out_mask,
+                                                   float* out_points, effi_stream_t stream) {
+    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
+    if (h < 2 || w < 2 || dh_view_num < 1 || dist_base <= 0.0f || rel_diff_base <= 0.0f) return EFFI_ERR_BADARG;
+    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
+    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, dh_view_num) != EFFI_OK) return EFFI_ERR_BADARG;
+    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table, n_ref,
+                       v_max, mats_scratch);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_dynamic_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table,
+                       v_max, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dh_view_num, dist_base, rel_diff_base, relative,
+                       out_depth, out_geo_mask, out_prob_mask, out_mask, out_points);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_compact_blocks(int n_ref, int h, int w) {
+    if (n_ref < 1 || n_ref > 65535 || h < 1 || w < 1 || (long)n_ref * h * w >= (1L << 31)) return 0;
+    return n_ref * effi_cdiv((long)h * w, CMP_THREADS);
+}
+
+extern "C" int effi_fusion_compact_scan_tile(void) { return SCAN_TILE; }
+
+extern "C" int effi_fusion_compact_count_u8(const unsigned char* mask, int n_ref, int h, int w, int* block_base, int* offsets,
+                                            effi_stream_t stream) {
+    if (!mask || !block_base || !offsets || n_ref < 1 || n_ref > 65535 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    const int hw = h * w, bpv = effi_cdiv(hw, CMP_THREADS);
+    hipLaunchKernelGGL(fusion_compact_count_kernel, dim3(bpv, n_ref), dim3(CMP_THREADS), 0, st, mask, hw, block_base);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_compact_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_base, n_ref * bpv, bpv, offsets);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_compact_scatter_f32(const unsigned char* mask, const float* points, const float* images, int n_images,
+                                               const int* pair_table_host, const int* pair_table, int table_stride, long img_view_stride,
+                                               long pix_stride, long ch_stride, int n_ref, int h, int w, const int* block_base,
+                                               float* xyz, unsigned char* rgb, effi_stream_t stream) {
+    if (!mask || !points || !images || !block_base || !xyz || !rgb || n_ref < 1 || n_ref > 65535 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    if ((long)n_ref * h * w >= (1L << 31) || n_images < 1 || img_view_stride < 0 || pix_stride < 1 || ch_stride < 1) return EFFI_ERR_BADARG;
+    if ((pair_table == nullptr) != (pair_table_host == nullptr)) return EFFI_ERR_BADARG;
+    if (pair_table_host) {
+        if (table_stride < 1) return EFFI_ERR_BADARG;
+        for (int r = 0; r < n_ref; ++r)
+            if (pair_table_host[(long)r * table_stride] < 0 || pair_table_host[(long)r * table_stride] >= n_images) return EFFI_ERR_BADARG;
+    } else if (n_images < n_ref) {
+        return EFFI_ERR_BADARG;
+    }
+    hipStream_t st = effi_s(stream);
+    const int hw = h * w;
+    hipLaunchKernelGGL(fusion_compact_scatter_kernel, dim3(effi_cdiv(hw, CMP_THREADS), n_ref), dim3(CMP_THREADS), 0, st, mask, points, images,
+                       pair_table, table_stride, img_view_stride, pix_stride, ch_stride, hw, block_base, xyz, rgb);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
 
 extern "C" int effi_fusion_vis_filter_f32(const float* ref_depth, const float* reproj_xyd, int n, int n_src, int h, int w,
                                           float dist_base, float rel_diff_base, int thres_view, int relative, unsigned char* masks,

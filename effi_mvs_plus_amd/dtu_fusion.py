@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from .datasets.data_io import read_pfm
+from .fusion import fuse_chunks, pair_table  # noqa: F401  (pair_table: the host-only table builder, re-exported)
 
 # module constants of the reference (test_dtu_dypcd.py:33-37)
 s, e = 1, 11
@@ -119,6 +120,30 @@ def filter_view(ref_depth_est, ref_intrinsics, ref_extrinsics, src_depth_ests, s
                               conf_keep=0.75, s=s, e=e, dist_base=dist_base, diff_base=diff_base)
     return {"depth_est_averaged": r["depth"], "photo_mask": r["photo_mask"].bool(), "geo_mask": r["geo_mask"].bool(),
             "final_mask": r["mask"].bool(), "xyz_world": r["points"]}
+
+
+@ops.on_tensor_device
+def fuse_scan(depths, confidences, cams, images, pair_data, conf=0.5, chunk=None):
+    """The array part of ``filter_depth`` (test_dtu_dypcd.py:250-333) for a WHOLE scan, from the maps its forward pass left on the
+    device to the fused point cloud: depths [n_views,h,w]; confidences [n_views,ch,cw] (any size); cams [n_views,2,4,4] (extrinsic,
+    intrinsic in the top-left 3x3); images [n_views,h,w,3] fp32 in [0,1] (``read_img``); ``pair_data`` the ``read_pair_file`` list ->
+    dict(xyz [M,3] float32, rgb [M,3] uint8 -- the vertices ``filter_depth`` writes, in its order: reference views in list order,
+    row-major survivors --, offsets [n_ref+1] int32 (view r owns vertices offsets[r]:offsets[r+1]), depth_est_averaged [n_ref,h,w],
+    photo_mask / geo_mask / final_mask [n_ref,h,w] bool).  Scan-batched launches: no source map is stacked or copied, and the
+    survivors are compacted on the device; the reference views are worked through ``chunk`` at a time (None: sized so that a chunk's
+    dense points stay below 400 MB) and the result is the same for every ``chunk``.  ``write_ply`` takes xyz / rgb after
+    ``.cpu().numpy()``."""
+    table = pair_table(pair_data)
+    dev = depths.device
+    depths, cams, images = depths.contiguous(), cams.contiguous(), images.contiguous()
+
+    def filter_chunk(t_, r0, r1):
+        return ops.fusion_dtu_filter_scan(depths, cams, t_, confidences[t_[:, 0].long().to(dev)].contiguous(), conf_threshold=conf,
+                                          conf_keep=0.75, s=s, e=e, dist_base=dist_base, diff_base=diff_base)
+
+    out = fuse_chunks(table, filter_chunk, images, "hwc", chunk, ("depth", "photo_mask", "geo_mask", "mask"))
+    return {"xyz": out["xyz"], "rgb": out["rgb"], "offsets": out["offsets"], "depth_est_averaged": out["depth"],
+            "photo_mask": out["photo_mask"].bool(), "geo_mask": out["geo_mask"].bool(), "final_mask": out["mask"].bool()}
 
 
 def write_ply(filename, vertexs, vertex_colors):

@@ -3,8 +3,9 @@
 ``get_pixel_grids``, ``bin_op_reduce``, ``idx_img2cam``, ``idx_cam2world``, ``idx_world2cam``, ``idx_cam2img``,
 ``get_reproj_dynamic``, ``vis_filter_dynamic`` -- so that ``import effi_mvs_plus_amd.fusion as fusion`` lets the driver's lines
 486-509 run unchanged; each is one kernel of csrc/fusion.hip behind the C ABI.  ``dynamic_filter`` is the same block of the driver
-as ONE fused kernel per reference view (no ``[n,v,3,h,w]`` intermediates), what bench.py times.  CUDA (ROCm) fp32 tensors only; no
-CPU fallback.
+as ONE fused kernel per reference view (no ``[n,v,3,h,w]`` intermediates), what bench.py times.  ``dynamic_filter_scan`` is the
+driver's whole loop over a scan's reference views -- depth maps of a scan in, point cloud out -- in scan-batched launches with the
+survivors compacted on the device.  CUDA (ROCm) fp32 tensors only; no CPU fallback.
 """
 from __future__ import annotations
 
@@ -103,4 +104,67 @@ def dynamic_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_thre
     out = {"depth": torch.stack([r["depth"] for r in res]).unsqueeze(1), "points": torch.stack([r["points"] for r in res])}
     for k in ("geo_mask", "prob_mask", "mask"):
         out[k] = torch.stack([r[k] for r in res]).unsqueeze(1).bool()
+    return out
+
+
+def pair_table(pair_data):
+    """Host only: the ``read_pair_file`` list [(ref_view, [src_views...]), ...] -> int32 CPU tensor [n_ref, 1 + v_max] (reference id,
+    source ids, -1 padding), the table the scan launches index a scan's depth maps and cameras with."""
+    return ops.fusion_pair_table(pair_data)
+
+
+def fuse_chunks(table, filter_chunk, images, layout, chunk, mask_keys):
+    """The chunk loop both scan drivers share.  ``filter_chunk(rows, r0, r1)`` runs the scan-batched filter on table rows r0:r1 and
+    returns its dict (``mask`` = the final mask, ``points``); every chunk's survivors are compacted in order, so the dense points of
+    only one chunk exist at a time and the result does not depend on ``chunk``."""
+    n_ref = table.shape[0]
+    h, w = images.shape[1:3] if layout == "hwc" else images.shape[2:4]
+    if chunk is None:
+        chunk = max(1, (1 << 25) // (h * w))                    # <= 400 MB of dense points per chunk
+    chunk = max(1, min(int(chunk), n_ref))
+    xyz, rgb, offs, kept, total = [], [], [], {k: [] for k in mask_keys}, 0
+    for r0 in range(0, n_ref, chunk):
+        rows = table[r0:r0 + chunk].contiguous()
+        r = filter_chunk(rows, r0, r0 + rows.shape[0])
+        x, c, o = ops.fusion_compact(r["mask"], r["points"], images, layout, rows)
+        xyz.append(x), rgb.append(c), offs.append(o[:-1] + total)
+        total += x.shape[0]
+        for k in mask_keys:
+            kept[k].append(r[k])
+    offs.append(torch.tensor([total], dtype=torch.int32, device=images.device))
+    out = {"xyz": torch.cat(xyz), "rgb": torch.cat(rgb), "offsets": torch.cat(offs)}
+    for k in mask_keys:
+        out[k] = torch.cat(kept[k])
+    return out
+
+
+@ops.on_tensor_device
+def dynamic_filter_scan(depths, confidences, cams, images, pair_data, prob_threshold=0.3, dh_view_num=2, dist_filter=4.0,
+                        depth_filter=1300.0, relative=False, chunk=None):
+    """``dynamic_filter_depth`` (test_tank.py:455-570) from the maps a scan's forward pass left on the device to the fused point
+    cloud, ``filter_dixt``'s fields as keywords.  depths [n_views,h,w]; confidences [n_views,ch,cw] or None; cams [n_views,2,4,4];
+    images [n_views,3,h,w] fp32 in [0,1]; ``pair_data`` the ``read_pair_file`` list.  A reference view with fewer than
+    ``dh_view_num + 1`` sources contributes nothing (:478) -> dict(xyz [M,3] float32, rgb [M,3] uint8 -- vertices in the reference's
+    order: retained reference views in list order, row-major survivors --, offsets [n_kept+1] int32, ref_ids: the retained reference
+    ids, depth [n_kept,h,w], prob_mask / geo_mask / mask [n_kept,h,w] bool).  Works through the reference views ``chunk`` at a time
+    (None: sized so that a chunk's dense points stay below 400 MB); the result is the same for every ``chunk``."""
+    rows = [(ref, srcs) for ref, srcs in pair_data if len(srcs) >= dh_view_num + 1]
+    dev = depths.device
+    if not rows:
+        h, w = depths.shape[-2:]
+        z = lambda *sh, dt=torch.float32: torch.empty(*sh, device=dev, dtype=dt)
+        return {"xyz": z(0, 3), "rgb": z(0, 3, dt=torch.uint8), "offsets": torch.zeros(1, dtype=torch.int32, device=dev), "ref_ids": [],
+                "depth": z(0, h, w), "prob_mask": z(0, h, w, dt=torch.bool), "geo_mask": z(0, h, w, dt=torch.bool),
+                "mask": z(0, h, w, dt=torch.bool)}
+    table = pair_table(rows)
+    depths, cams, images = depths.contiguous(), cams.contiguous(), images.contiguous()
+
+    def filter_chunk(t_, r0, r1):
+        conf = None if confidences is None else confidences[t_[:, 0].long().to(dev)].contiguous()
+        return ops.fusion_dynamic_filter_scan(depths, cams, t_, conf, prob_threshold, dh_view_num, dist_filter, depth_filter, relative)
+
+    out = fuse_chunks(table, filter_chunk, images, "chw", chunk, ("depth", "prob_mask", "geo_mask", "mask"))
+    for k in ("prob_mask", "geo_mask", "mask"):
+        out[k] = out[k].bool()
+    out["ref_ids"] = [ref for ref, _ in rows]
     return out

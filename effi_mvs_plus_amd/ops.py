@@ -1168,6 +1168,141 @@ def fusion_dtu_filter(ref_depth, src_depths, ref_cam, src_cams, confidence=None,
     return out
 
 
+def fusion_pair_table(pair_data):
+    """Host only (no GPU, no library): the ``read_pair_file`` list [(ref_view, [src_views...]), ...] (test_dtu_dypcd.py:150-160) ->
+    the pair table of the scan launches, int32 CPU tensor [n_ref, 1 + v_max]: row = reference id, its source ids in order, -1 padding."""
+    rows = [(int(ref), [int(v) for v in srcs]) for ref, srcs in pair_data]
+    if not rows:
+        raise ValueError("fusion_pair_table: no reference view")
+    for ref, srcs in rows:
+        if ref < 0 or not srcs or min(srcs) < 0:
+            raise ValueError(f"fusion_pair_table: reference view {ref} needs a non-negative id and at least one non-negative source id")
+    v_max = max(len(srcs) for _, srcs in rows)
+    table = torch.full((len(rows), 1 + v_max), -1, dtype=torch.int32)
+    for r, (ref, srcs) in enumerate(rows):
+        table[r, 0] = ref
+        table[r, 1:1 + len(srcs)] = torch.tensor(srcs, dtype=torch.int32)
+    return table
+
+
+def _scan_inputs(what, depths, cams, pairs):
+    _t(depths, "depths"), _t(cams, "cams")
+    if depths.dim() != 3 or tuple(cams.shape) != (depths.shape[0], 2, 4, 4):
+        raise ValueError(f"{what}: depths [n_views,h,w] and cams [n_views,2,4,4] expected, got {tuple(depths.shape)} / {tuple(cams.shape)}")
+    if not isinstance(pairs, torch.Tensor) or pairs.is_cuda or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] < 2 \
+            or pairs.shape[0] < 1:
+        raise ValueError(f"{what}: pairs must be the int32 CPU table [n_ref, 1 + v_max] of ops.fusion_pair_table")
+    pairs = pairs.contiguous()
+    return pairs, pairs.to(depths.device)
+
+
+def fusion_dtu_filter_scan(depths, cams, pairs, confidence=None, conf_threshold=0.5, conf_keep=0.75, s=1, e=11, dist_base=0.5,
+                           diff_base=0.25, want_points=True):
+    """``fusion_dtu_filter`` for every reference view of a scan in ONE launch (test_dtu_dypcd.py:250-333).  depths [n_views,h,w] and
+    cams [n_views,2,4,4] are read in place through ``pairs`` (``fusion_pair_table``: each reference view its own source count, at most
+    16); confidence [n_ref,ch,cw] in table order (any size) or None -> dict(depth [n_ref,h,w], photo_mask / geo_mask / mask
+    [n_ref,h,w] uint8, points [n_ref,3,h,w] or None); row r is bitwise ``fusion_dtu_filter`` on reference view r and its stacked sources."""
+    pairs, pairs_dev = _scan_inputs("fusion_dtu_filter_scan", depths, cams, pairs)
+    n_views, h, w = depths.shape
+    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
+    dev = depths.device
+    conf = None
+    if confidence is not None:
+        _t(confidence, "confidence")
+        if confidence.dim() != 3 or confidence.shape[0] != n_ref:
+            raise ValueError(f"fusion_dtu_filter_scan: confidence [n_ref,ch,cw] expected, got {tuple(confidence.shape)}")
+        conf = confidence if tuple(confidence.shape[1:]) == (h, w) else resize_planar(confidence, h, w)
+    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
+           "photo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
+    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
+    n_src = int((pairs[:, 1:] >= 0).sum())
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (3 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
+    check(_call("fusion_dtu_filter_scan", work, _lib.lib().effi_fusion_dtu_filter_scan_f32, _p(depths), _p(cams), n_views, _p(pairs),
+                _p(pairs_dev), n_ref, v_max, h, w, _p(conf), float(conf_threshold), float(conf_keep), int(s), int(e), float(dist_base),
+                float(diff_base), _p(scratch), _p(out["depth"]), _p(out["photo_mask"]), _p(out["geo_mask"]), _p(out["mask"]),
+                _p(out["points"]), _stream()), "effi_fusion_dtu_filter_scan_f32")
+    return out
+
+
+def fusion_dynamic_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshold=0.0, dh_view_num=2, dist_base=4.0,
+                               rel_diff_base=1300.0, relative=False, want_points=True):
+    """``fusion_dynamic_filter`` for every reference view of a scan in ONE launch (test_tank.py:466-512); arguments as
+    ``fusion_dtu_filter_scan``, ref_conf [n_ref,ch,cw] in table order or None -> dict(depth [n_ref,h,w], geo_mask / prob_mask / mask
+    [n_ref,h,w] uint8, points [n_ref,3,h,w] or None).  Every row needs at least ``dh_view_num`` sources."""
+    pairs, pairs_dev = _scan_inputs("fusion_dynamic_filter_scan", depths, cams, pairs)
+    n_views, h, w = depths.shape
+    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
+    dev = depths.device
+    ch = cw = 0
+    if ref_conf is not None:
+        _t(ref_conf, "ref_conf")
+        if ref_conf.dim() != 3 or ref_conf.shape[0] != n_ref:
+            raise ValueError(f"fusion_dynamic_filter_scan: ref_conf [n_ref,ch,cw] expected, got {tuple(ref_conf.shape)}")
+        ch, cw = ref_conf.shape[1:]
+    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
+           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "prob_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
+    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
+    n_src = int((pairs[:, 1:] >= 0).sum())
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (2 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
+    check(_call("fusion_dynamic_filter_scan", work, _lib.lib().effi_fusion_dynamic_filter_scan_f32, _p(depths), _p(cams), n_views,
+                _p(pairs), _p(pairs_dev), n_ref, v_max, h, w, _p(ref_conf), ch, cw, float(prob_threshold), int(dh_view_num),
+                float(dist_base), float(rel_diff_base), int(bool(relative)), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]),
+                _p(out["prob_mask"]), _p(out["mask"]), _p(out["points"]), _stream()), "effi_fusion_dynamic_filter_scan_f32")
+    return out
+
+
+def fusion_compact(mask, points, images, layout="hwc", pairs=None):
+    """The survivors of a scan as vertex arrays in the reference's order (test_dtu_dypcd.py:327-333, test_tank.py:517-533: boolean
+    indexing view by view, then np.concatenate) without leaving the device and without atomics.  mask [n_ref,h,w] uint8; points
+    [n_ref,3,h,w]; images fp32 in [0,1], ``layout`` "hwc" = [n,h,w,3] (the DTU driver's) or "chw" = [n,3,h,w] (the T&T driver's); row r
+    takes image r, or image ``pairs[r,0]`` when the pair table is given -> (xyz [M,3] float32, rgb [M,3] uint8 = (uint8)(c * 255),
+    offsets [n_ref+1] int32: the vertices of row r are offsets[r]:offsets[r+1]).  Reading M is the only host synchronisation."""
+    _t(points, "points"), _t(images, "images")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.dim() != 3 \
+            or mask.device != points.device:
+        raise TypeError("fusion_compact: mask must be a contiguous uint8 tensor [n_ref,h,w] on the points' device")
+    n_ref, h, w = mask.shape
+    if layout not in ("hwc", "chw"):
+        raise ValueError("fusion_compact: layout is 'hwc' or 'chw'")
+    if tuple(points.shape) != (n_ref, 3, h, w) or tuple(images.shape[1:]) != ((h, w, 3) if layout == "hwc" else (3, h, w)):
+        raise ValueError(f"fusion_compact: points [n_ref,3,h,w] and images {'[n,h,w,3]' if layout == 'hwc' else '[n,3,h,w]'} expected, "
+                         f"got {tuple(points.shape)} / {tuple(images.shape)} for mask {tuple(mask.shape)}")
+    pairs_dev, stride = None, 0
+    if pairs is not None:
+        if not isinstance(pairs, torch.Tensor) or pairs.is_cuda or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[0] != n_ref:
+            raise ValueError("fusion_compact: pairs must be the int32 CPU table [n_ref, 1 + v_max] of ops.fusion_pair_table")
+        pairs = pairs.contiguous()
+        pairs_dev, stride = pairs.to(mask.device), pairs.shape[1]
+    elif images.shape[0] != n_ref:
+        raise ValueError(f"fusion_compact: {images.shape[0]} images for {n_ref} reference views (pass pairs to pick them by id)")
+    L = _lib.lib()
+    dev = mask.device
+    n_blocks = L.effi_fusion_compact_blocks(n_ref, h, w)
+    if n_blocks <= 0:
+        raise EffiLibraryError(f"fusion_compact: n_ref*h*w = {n_ref * h * w} must stay below 2^31 and n_ref below 65536")
+    base = torch.empty(n_blocks, device=dev, dtype=torch.int32)
+    offsets = torch.empty(n_ref + 1, device=dev, dtype=torch.int32)
+    work = lambda: {"flops": 0.0, "bytes": 1.0 * n_ref * h * w + 8.0 * n_blocks}
+    check(_call("fusion_compact_count", work, L.effi_fusion_compact_count_u8, C.c_void_p(mask.data_ptr()), n_ref, h, w, _p(base),
+                _p(offsets), _stream()), "effi_fusion_compact_count_u8")
+    m = int(offsets[n_ref].item())                              # the path's one host synchronisation: sizes the output
+    xyz = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    rgb = torch.empty(m, 3, device=dev, dtype=torch.uint8)
+    if m:
+        pix, chs = (3, 1) if layout == "hwc" else (1, h * w)
+        work = lambda: {"flops": 0.0, "bytes": 1.0 * n_ref * h * w + 39.0 * m}
+        check(_call("fusion_compact_scatter", work, L.effi_fusion_compact_scatter_f32, C.c_void_p(mask.data_ptr()), _p(points), _p(images),
+                    images.shape[0], _p(pairs), _p(pairs_dev), stride, 3 * h * w, pix, chs, n_ref, h, w, _p(base), _p(xyz), _p(rgb),
+                    _stream()), "effi_fusion_compact_scatter_f32")
+    return xyz, rgb, offsets
+
+
 def image_prepare(img_u8, dst_h, dst_w, out=None):
     """Scope row n4: decoded image [h,w,3] (or [h,w]) uint8 on the device -> [3,dst_h,dst_w] fp32 = cv2-style bilinear resize of
     img / 255, channel-first (datasets/general_eval.py:83-117,189)."""

@@ -833,6 +833,47 @@ int effi_fusion_dtu_filter_f32(const float* ref_depth, const float* src_depths, 
                                float dist_base, float diff_base, float* mats_scratch, float* out_depth, unsigned char* out_photo_mask,
                                unsigned char* out_geo_mask, unsigned char* out_final_mask, float* out_points, effi_stream_t stream);
 
+/* ---- n3, a whole scan per launch: the loops over reference views of test_dtu_dypcd.py:250-333 (filter_depth) and
+ * test_tank.py:466-533 (dynamic_filter_depth) with the reference-view index in the grid.  depths [n_views][h][w] and cams
+ * [n_views][2][4][4] hold every view of the scan ONCE and are read in place; the pair table [n_ref][1 + v_max] (int32) holds per row
+ * the reference id and its source ids, padded with -1 at the end, so every reference view has its own source count (pair.txt,
+ * test_dtu_dypcd.py:150-160).  pair_table_host is the table in HOST memory: it is checked before anything is launched (ids in
+ * [0, n_views), 1 .. 16 sources per row -- for the T&T entry at least dh_view_num --, v_max <= 16, n_ref <= 65535, n_ref*h*w < 2^31;
+ * otherwise EFFI_ERR_BADARG); pair_table is the same table in device memory.  Row r of every output is bitwise what the single-view
+ * entry gives for that reference view and its sources.  mats_scratch: 52 * n_ref * (v_max + 1) floats.
+ * DTU: confidence [n_ref][h][w] (already at the depth size: effi_resize_linear_f32 with n_ref planes) or NULL; outputs
+ * [n_ref][h][w], out_points [n_ref][3][h][w] (any but out_depth may be NULL). */
+int effi_fusion_dtu_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                    const int* pair_table, int n_ref, int v_max, int h, int w, const float* confidence,
+                                    float conf_threshold, float conf_keep, int s, int e, float dist_base, float diff_base,
+                                    float* mats_scratch, float* out_depth, unsigned char* out_photo_mask, unsigned char* out_geo_mask,
+                                    unsigned char* out_final_mask, float* out_points, effi_stream_t stream);
+/* Tanks-and-Temples (test_tank.py:466-512 per row): ref_conf [n_ref][conf_h][conf_w] (nearest look-up in the kernel, :473) or NULL.
+ * The caller leaves out reference views with fewer than dh_view_num + 1 sources (:478). */
+int effi_fusion_dynamic_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                        const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf, int conf_h,
+                                        int conf_w, float prob_threshold, int dh_view_num, float dist_base, float rel_diff_base,
+                                        int relative, float* mats_scratch, float* out_depth, unsigned char* out_geo_mask,
+                                        unsigned char* out_prob_mask, unsigned char* out_mask, float* out_points, effi_stream_t stream);
+
+/* Ordered compaction of the survivors into vertex arrays, what test_dtu_dypcd.py:327-333 and test_tank.py:517-533 do on the host with
+ * boolean indexing and np.concatenate: vertices in reference-view order, row-major inside a view.  No atomics (bitwise reproducible).
+ * effi_fusion_compact_count_u8: mask [n_ref][h][w] bytes -> block_base [effi_fusion_compact_blocks(n_ref, h, w)] (survivors before each
+ * workgroup of 256 pixels) and offsets [n_ref + 1] (survivors before each view; the last entry is the vertex count M, which the caller
+ * reads to size xyz / rgb).  effi_fusion_compact_scatter_f32: points [n_ref][3][h][w] -> xyz [M][3]; rgb [M][3] bytes =
+ * (uint8)(c * 255.0f) of the reference image's fp32 channels in [0, 1] (test_dtu_dypcd.py:333, test_tank.py:529-533).  The image of
+ * row r is images + view * img_view_stride floats with view = r, or = pair_table[r * table_stride] when a table is given (host and
+ * device copy as above; ids in [0, n_images)); channel c of pixel p lies at p * pix_stride + c * ch_stride ([h][w][3]: 3 and 1,
+ * [3][h][w]: 1 and h*w).  n_ref*h*w >= 2^31 is EFFI_ERR_BADARG.  effi_fusion_compact_scan_tile: counts one pass of the scan kernel
+ * covers (for tests that need more than one pass). */
+int effi_fusion_compact_blocks(int n_ref, int h, int w);
+int effi_fusion_compact_scan_tile(void);
+int effi_fusion_compact_count_u8(const unsigned char* mask, int n_ref, int h, int w, int* block_base, int* offsets, effi_stream_t stream);
+int effi_fusion_compact_scatter_f32(const unsigned char* mask, const float* points, const float* images, int n_images,
+                                    const int* pair_table_host, const int* pair_table, int table_stride, long img_view_stride,
+                                    long pix_stride, long ch_stride, int n_ref, int h, int w, const int* block_base, float* xyz,
+                                    unsigned char* rgb, effi_stream_t stream);
+
 /* ---- tuning / A-B switches.  A table of named integers, initialised ONCE per process from the environment (variable EFFI_<NAME in
  * upper case>) and changed afterwards only through effi_set_option; no entry point reads the environment.  Names: warp_lds_kb
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =
