@@ -3,7 +3,8 @@
 Public classes / functions keep the reference's names, signatures, return structures and state-dict
 keys (``models/Effi_MVS_plus.py`` in bdwsq1996/Effi-MVS-plus); the work is done by the gfx950 kernels.
 ``Effi_MVS_plus.forward`` runs the feature / context pyramids (scope row n1, also on the HIP conv kernels) and then
-``forward_hot`` -- the cost-volume path this repository accelerates and ``bench.py`` times.  Inference only.
+``forward_hot`` -- the cost-volume path this repository accelerates and ``bench.py`` times.  In ``train()`` mode the modules
+route to ``train_path`` (the differentiable forms); everything written out here is the inference path.
 """
 from __future__ import annotations
 
@@ -99,7 +100,6 @@ class PixelwiseNet2d(nn.Sequential):
         return ops.pixelwise_net(entropy, self._cache.get(t, lambda: packing.pack_pixelwise_net(self)))
 
     @ops.on_tensor_device
-
     def forward(self, x):
         n, c, h, w = x.shape
         return self.run(x.reshape(n * c, h, w).contiguous()).view(n, c, h, w)
@@ -108,50 +108,66 @@ class PixelwiseNet2d(nn.Sequential):
 # =============================================================================================
 # a2: stage-1 cost volume (reference: Effi_MVS_plus.py:9-89)
 # =============================================================================================
+def cascade_setup(disp_range, pairs, D1):
+    """Stage-1 hypotheses and the relative projections of every stage: disp_range [R] and pairs = per stage [N,2,4,4] -- or, for B
+    samples, [B,R] and [B,N,2,4,4] (samples contiguous) -> (hyp [D1], misc [5] = 3 intervals, depth_min_, depth_max_, [rt [N-1,12]
+    per stage]), with a leading B on each for a batch.  One launch (option setup_fused), else the separate set-up launches."""
+    if len(pairs) <= 4 and ops.option("setup_fused"):
+        (hyp, misc), rts = ops.cascade_setup(disp_range, D1, pairs)
+        return hyp, misc, rts
+    rel = (lambda ps: ops.compose_rel_proj_stages(ps)) if len(pairs) <= 4 else (lambda ps: [ops.compose_rel_proj(p_) for p_ in ps])
+    if disp_range.dim() == 1:
+        return (*ops.stage1_hypotheses(disp_range, D1), rel(pairs))
+    hm = [ops.stage1_hypotheses(r, D1) for r in disp_range]    # the separate set-up launches have no sample index: per sample, stacked
+    per = [rel([p_[b] for p_ in pairs]) for b in range(len(hm))]
+    return (torch.stack([x[0] for x in hm]), torch.stack([x[1] for x in hm]),
+            [torch.stack([r[s] for r in per]) for s in range(len(pairs))])
+
+
+def stage1_volume(maps, rt, hyp, D, cost_regularization, pixel_wise_net, disp_range=None, x3=False):
+    """The stage-1 cost volume, ONE sample or (every tensor with a leading B) a batch of them in batched launches: warp and
+    correlate -> view weights -> aggregate -> regularise -> soft-argmin.  ``maps``: the channel-last maps [h,w,C], reference first,
+    or an ``ops.ViewTable`` (its stage 0; one sample).  ``pixel_wise_net`` None = the plain mean over the views.  With
+    ``disp_range`` the soft-argmin also writes the normalised inverse depth the first update block starts from and (option
+    conf_fused) the confidence at full size
+    -> (view weights, cur_vol, reg_vol, depth, confidence, inv_next or None, full-size confidence or None)."""
+    if isinstance(maps, ops.ViewTable):
+        sim_views, entropy = ops.warpcorr_views_tbl(maps, 0, rt, hyp, D, x3=x3)
+    else:
+        sim_views, entropy = ops.warpcorr_views(maps[0], maps[1:], rt, hyp, D, x3=x3)
+    if pixel_wise_net is None:                  # unweighted average of the views (reference :55-58,70)
+        weights = None
+    elif hasattr(pixel_wise_net, "run"):
+        weights = pixel_wise_net.run(entropy)
+    else:                                       # a foreign module: every plane of every sample as one [., 1, h, w] batch
+        weights = pixel_wise_net(entropy.reshape((-1, 1) + entropy.shape[-2:])).squeeze(1).contiguous().view(entropy.shape)
+    cur_vol = ops.view_aggregate(sim_views, weights)
+    reg_vol = cost_regularization.run(cur_vol.unsqueeze(-4))[0].select(-4, 0)
+    inv_next = conf_up = None
+    if disp_range is None:
+        depth, conf = ops.softmax_regress_conf(reg_vol, hyp)
+    elif ops.option("conf_fused"):              # the full-size confidence map comes out of the same launch
+        depth, conf, inv_next, conf_up = ops.softmax_regress_conf(reg_vol, hyp, disp_range, conf_up=4)
+    else:
+        depth, conf, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)     # + depth_to_inv of it (:538)
+    return weights, cur_vol, reg_vol, depth, conf, inv_next, conf_up
+
+
 class DepthNet(nn.Module):
     def __init__(self, cnnpixel=False):
         super().__init__()
 
     @staticmethod
     def run(feats, pairs, depth, num_depth, cost_regularization, pixel_wise_net):
-        """Unbatched: feats list of [C,h,w]; pairs [N,2,4,4]; depth [D] or [D,h,w]."""
-        nhwc = ops.to_nhwc(feats)
-        rt = ops.compose_rel_proj(pairs)
-        sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rt, depth, num_depth)
-        if pixel_wise_net is None:              # unweighted average of the views (reference :55-58,70); view_weights stays the empty list
-            weights = None
-        else:
-            weights = pixel_wise_net.run(entropy) if hasattr(pixel_wise_net, "run") else \
-                pixel_wise_net(entropy.unsqueeze(1)).squeeze(1).contiguous()
-        volume = ops.view_aggregate(sim_views, weights)
-        reg, _ = cost_regularization.run(volume.unsqueeze(0))
-        d, conf = ops.softmax_regress_conf(reg[0], depth)
+        """feats list of [C,h,w]; pairs [N,2,4,4]; depth [D] or [D,h,w] -- or B samples in one pass of batched launches: feats
+        list of [B,C,h,w]; pairs [B,N,2,4,4] (samples contiguous); depth [B,D] or [B,D,h,w] -> every tensor of the dictionary with a
+        leading B, sample b bitwise the unbatched call on sample b."""
+        weights, volume, reg, d, conf, _, _ = stage1_volume(ops.to_nhwc(feats), ops.compose_rel_proj(pairs), depth, num_depth,
+                                                            cost_regularization, pixel_wise_net)
         return {"depth": d, "photometric_confidence": conf, **({"view_weights": weights} if weights is not None else {}),
-                "reg_volume": reg[0], "volume": volume.unsqueeze(0)}
-
-    @staticmethod
-    def run_batch(feats, pairs, depth, num_depth, cost_regularization, pixel_wise_net):
-        """``run`` for B samples in one pass of batched launches: feats list of [B,C,h,w]; pairs [B,N,2,4,4]; depth [B,D] or
-        [B,D,h,w] -> the dictionary of ``run`` with a leading B on every tensor, sample b bitwise ``run`` on sample b."""
-        B = feats[0].shape[0]
-        nhwc = ops.to_nhwc(feats)
-        rt = ops.compose_rel_proj(pairs if pairs[0].is_contiguous() else pairs.contiguous())
-        sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rt, depth, num_depth)
-        if pixel_wise_net is None:
-            weights = None
-        elif hasattr(pixel_wise_net, "run"):
-            weights = pixel_wise_net.run(entropy)
-        else:
-            S = entropy.shape[1]
-            weights = pixel_wise_net(entropy.flatten(0, 1).unsqueeze(1)).squeeze(1).contiguous().unflatten(0, (B, S))
-        volume = ops.view_aggregate(sim_views, weights)
-        reg, _ = cost_regularization.run(volume.unsqueeze(1))
-        d, conf = ops.softmax_regress_conf(reg[:, 0], depth)
-        return {"depth": d, "photometric_confidence": conf, **({"view_weights": weights} if weights is not None else {}),
-                "reg_volume": reg[:, 0], "volume": volume.unsqueeze(1)}
+                "reg_volume": reg, "volume": volume.unsqueeze(-4)}
 
     @ops.on_tensor_device
-
     def forward(self, features, proj_matrices, depth_values, num_depth, cost_regularization, pixel_wise_net, G=8):
         assert len(features) == proj_matrices.shape[1], "Different number of images and projection matrices"
         assert depth_values.shape[1] == num_depth, "depth_values.shape[1]:{}  num_depth:{}".format(
@@ -165,7 +181,8 @@ class DepthNet(nn.Module):
             from .. import train_path
             return train_path.depthnet(pixel_wise_net, cost_regularization, features, proj_matrices, depth_values)
         if features[0].shape[0] > 1 and hasattr(cost_regularization, "run"):
-            res = self.run_batch(list(features), proj_matrices, depth_values, num_depth, cost_regularization, pixel_wise_net)
+            pairs = proj_matrices if proj_matrices[0].is_contiguous() else proj_matrices.contiguous()
+            res = self.run(list(features), pairs, depth_values, num_depth, cost_regularization, pixel_wise_net)
             if pixel_wise_net is None:
                 res["view_weights"] = []
             return res
@@ -187,7 +204,6 @@ class GetCost_initvolume(nn.Module):
         super().__init__()
 
     @ops.on_tensor_device
-
     def forward(self, depth_values, features, proj_matrices, depth_interval, depth_max, depth_min, view_weights,
                 CostNum=4, Inverse=True, G=8, iter=1, inter_iter=[1, 1, 1, 1]):
         if not Inverse or G != 1 or view_weights is None:
@@ -213,60 +229,59 @@ class GetCost_initvolume(nn.Module):
 # =============================================================================================
 # a11: per-iteration cost lookup (reference: Effi_MVS_plus.py:253-303)
 # =============================================================================================
+class CostLookup:
+    """What the fused update block looks the two cached volumes up with: ``lookup(inv_depth)``, normalised inverse depth [1,h,w] ->
+    cost [2*nq,h,w], and the forms of it that apply the first encoder layers in the same launch.  A form the configuration has no
+    kernel for is None (the block asks with ``getattr(lookup, name, None) is not None``): ``conv1x1`` needs nq in (2, 3, 4), the
+    other three nq == 3.  ``cur`` / ``reg``: ONE sample's volumes, planar [D,h,w] or pixel-major [h*w,1,1,D]; the map size is the
+    query's."""
+
+    def __init__(self, disp_range, interval, cur, reg, lo, hi, nq):
+        self.vols = (disp_range, interval, cur, reg, lo, hi, nq)
+        if nq not in (2, 3, 4):
+            self.conv1x1 = None
+        if nq != 3:
+            self.encoder_inputs = self.encoder_inputs_sr = self.encoder_pair_sr = None
+
+    def __call__(self, inv_depth, out=None):
+        h, w = inv_depth.shape[-2:]
+        return ops.getcost(inv_depth, *self.vols, h, w, out=out)
+
+    def conv1x1(self, inv_depth, weight, bias, cout, out=None):
+        """Same lookup with the encoder's convc1 (+ReLU) applied in the kernel: -> [cout,h,w]."""
+        h, w = inv_depth.shape[-2:]
+        return ops.getcost_conv1x1(inv_depth, *self.vols, h, w, weight, bias, cout, relu=True, out=out)
+
+    def encoder_inputs(self, inv_depth, wc1, bc1, wd1, bd1, cout, out_c1=None, out_d1=None):
+        """``conv1x1`` and the encoder's convd1 (7x7, +ReLU) of the same map in one launch."""
+        h, w = inv_depth.shape[-2:]
+        return ops.encoder_inputs(inv_depth, *self.vols, h, w, wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
+
+    def encoder_inputs_sr(self, inv_depth, wc1, bc1, wd1, bd1, cout, out_c1, out_d1):
+        """``encoder_inputs`` writing split-resident maps (ops.SRMap)."""
+        h, w = inv_depth.shape[-2:]
+        return ops.encoder_inputs_sr(inv_depth, *self.vols, h, w, wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
+
+    def encoder_pair_sr(self, inv_depth, wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2):
+        """``encoder_inputs_sr`` + the convc2 | convd2 pair in one launch (ops.encoder_pair_gen_sr)."""
+        h, w = inv_depth.shape[-2:]
+        return ops.encoder_pair_gen_sr(inv_depth, *self.vols, h, w, wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2, hd)
+
+
 class GetCost(nn.Module):
     def __init__(self):
         super().__init__()
 
     def make_lookup(self, b, pro, depth_interval, depth_max_cur_volume=0, depth_min_cur_volume=0, CostNum=4,
                     disp_range=None, **unused):
-        """Closure used by the fused update block: normalised inverse depth [1,h,w] -> cost [2*CostNum,h,w]."""
-        interval = depth_interval[b].reshape(1).contiguous()
+        """The ``CostLookup`` of sample ``b`` from the reference-shaped arguments (``pro``: pixel-major volumes of all samples)."""
         lo = depth_min_cur_volume[b] if depth_min_cur_volume.shape[0] > 1 else depth_min_cur_volume[0]
         hi = depth_max_cur_volume[b] if depth_max_cur_volume.shape[0] > 1 else depth_max_cur_volume[0]
-        cur, reg = pro[-1], pro[0]
-
-        def lookup(inv_depth, out=None):
-            h, w = inv_depth.shape[-2:]
-            n = h * w
-            return ops.getcost(inv_depth, disp_range[b], interval, cur[b * n:(b + 1) * n], reg[b * n:(b + 1) * n],
-                               lo, hi, CostNum, h, w, input_is_depth=False, out=out)
-
-        def lookup_conv1x1(inv_depth, weight, bias, cout, out=None):
-            """Same lookup with the encoder's convc1 (+ReLU) applied in the kernel: -> [cout,h,w]."""
-            h, w = inv_depth.shape[-2:]
-            n = h * w
-            return ops.getcost_conv1x1(inv_depth, disp_range[b], interval, cur[b * n:(b + 1) * n], reg[b * n:(b + 1) * n],
-                                       lo, hi, CostNum, h, w, weight, bias, cout, relu=True, out=out)
-
-        def lookup_encoder_inputs(inv_depth, wc1, bc1, wd1, bd1, cout, out_c1=None, out_d1=None):
-            """lookup_conv1x1 and the encoder's convd1 (7x7, +ReLU) of the same map in one launch."""
-            h, w = inv_depth.shape[-2:]
-            n = h * w
-            return ops.encoder_inputs(inv_depth, disp_range[b], interval, cur[b * n:(b + 1) * n], reg[b * n:(b + 1) * n],
-                                      lo, hi, CostNum, h, w, wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
-
-        def lookup_encoder_inputs_sr(inv_depth, wc1, bc1, wd1, bd1, cout, out_c1, out_d1):
-            """lookup_encoder_inputs writing split-resident maps (ops.SRMap)."""
-            h, w = inv_depth.shape[-2:]
-            n = h * w
-            return ops.encoder_inputs_sr(inv_depth, disp_range[b], interval, cur[b * n:(b + 1) * n], reg[b * n:(b + 1) * n],
-                                         lo, hi, CostNum, h, w, wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
-
-        lookup.conv1x1 = lookup_conv1x1 if CostNum in (2, 3, 4) else None
-        lookup.encoder_inputs = lookup_encoder_inputs if CostNum == 3 else None
-        def lookup_encoder_pair_sr(inv_depth, wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2):
-            """lookup_encoder_inputs_sr + the convc2 | convd2 pair in one launch (ops.encoder_pair_gen_sr)."""
-            h, w = inv_depth.shape[-2:]
-            n = h * w
-            return ops.encoder_pair_gen_sr(inv_depth, disp_range[b], interval, cur[b * n:(b + 1) * n], reg[b * n:(b + 1) * n],
-                                           lo, hi, CostNum, h, w, wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2, hd)
-
-        lookup.encoder_inputs_sr = lookup_encoder_inputs_sr if CostNum == 3 else None
-        lookup.encoder_pair_sr = lookup_encoder_pair_sr if CostNum == 3 else None
-        return lookup
+        n = pro[0].shape[0] // depth_interval.shape[0]          # pixels per sample
+        return CostLookup(disp_range[b], depth_interval[b].reshape(1).contiguous(), pro[-1][b * n:(b + 1) * n],
+                          pro[0][b * n:(b + 1) * n], lo, hi, CostNum)
 
     @ops.on_tensor_device
-
     def forward(self, depth_values, pro, features, proj_matrices, depth_interval, depth_max, depth_min, view_weights,
                 CostNum=4, Inverse=True, G=8, depth_max_cur_volume=0, depth_min_cur_volume=0, iter=1,
                 inter_iter=[1, 1, 1, 1], disp_range=None):
@@ -348,6 +363,8 @@ class Effi_MVS_plus(nn.Module):
         self.cost_regularization = CostRegNet_2_sample_FPN3D_Fast(in_channels=self.G, base_channels=8)
 
     # -----------------------------------------------------------------------------------------
+    _STAGE1_KEYS = ("weights", "cur_vol", "reg_vol", "depth", "c", "inv_next", "conf")      # what ``stage1_volume`` returns, in its order
+
     def _stage1_batch(self, features, proj_matrices, depth_values):
         """Set-up and stage-1 cost volume of ALL B samples in one pass of batched launches (what ``_hot_single`` does up to its
         first update block): -> one dictionary per sample, views of the batched results, for ``_hot_single(stage1=...)``."""
@@ -356,27 +373,11 @@ class Effi_MVS_plus(nn.Module):
         keys = ["stage{}".format(s + 1) for s in range(self.num_stage)]
         disp_range = depth_values if depth_values[0].is_contiguous() else depth_values.contiguous()
         pairs = [proj_matrices[k] if proj_matrices[k][0].is_contiguous() else proj_matrices[k].contiguous() for k in keys]
-        if self.num_stage <= 4 and ops.option("setup_fused"):
-            (hyp, misc), rts = ops.cascade_setup(disp_range, D1, pairs)
-        else:                                   # the separate set-up launches have no sample index: per sample, stacked
-            hm = [ops.stage1_hypotheses(disp_range[b], D1) for b in range(B)]
-            hyp, misc = torch.stack([x[0] for x in hm]), torch.stack([x[1] for x in hm])
-            per = [ops.compose_rel_proj_stages([p_[b] for p_ in pairs]) if self.num_stage <= 4 else
-                   [ops.compose_rel_proj(p_[b]) for p_ in pairs] for b in range(B)]
-            rts = [torch.stack([per[b][s] for b in range(B)]) for s in range(self.num_stage)]
+        hyp, misc, rts = cascade_setup(disp_range, pairs, D1)
         nhwc = ops.to_nhwc([f[keys[0]] for f in features])
-        sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rts[0], hyp, D1, x3=bool(ops.option("warp_x3")))
-        weights = self.PixelwiseNet.run(entropy)
-        cur_vol = ops.view_aggregate(sim_views, weights)
-        reg_vol = self.cost_regularization.run(cur_vol.unsqueeze(1))[0][:, 0]
-        if ops.option("conf_fused"):
-            depth, c, inv_next, conf = ops.softmax_regress_conf(reg_vol, hyp, disp_range, conf_up=4)
-        else:
-            depth, c, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)
-            conf = None
-        return [{"hyp": hyp[b], "misc": misc[b], "rts": [r[b] for r in rts], "weights": weights[b], "cur_vol": cur_vol[b],
-                 "reg_vol": reg_vol[b], "depth": depth[b], "c": c[b], "inv_next": inv_next[b], "conf": None if conf is None else conf[b]}
-                for b in range(B)]
+        vol = stage1_volume(nhwc, rts[0], hyp, D1, self.cost_regularization, self.PixelwiseNet, disp_range, x3=bool(ops.option("warp_x3")))
+        return [{"hyp": hyp[b], "misc": misc[b], "rts": [r[b] for r in rts],
+                 **{k: None if v is None else v[b] for k, v in zip(self._STAGE1_KEYS, vol)}} for b in range(B)]
 
     def _hot_single(self, feats, ctx, pairs, disp_range, want_intermediates=False, stage1=None):
         """One sample, unbatched.  feats: per view {stageK: [C,h,w]}; ctx {stageK: [hd+cd,h,w]};
@@ -390,14 +391,8 @@ class Effi_MVS_plus(nn.Module):
         # context maps (hidden state and context input of the update blocks) in one launch
         if stage1 is not None:
             hyp, misc, rts = stage1["hyp"], stage1["misc"], stage1["rts"]
-        elif self.num_stage <= 4 and ops.option("setup_fused"):
-            (hyp, misc), rts = ops.cascade_setup(disp_range, D1, [pairs[k].contiguous() for k in keys])
         else:
-            hyp, misc = ops.stage1_hypotheses(disp_range, D1)      # misc: 3 intervals, depth_min_, depth_max_
-            if self.num_stage <= 4:
-                rts = ops.compose_rel_proj_stages([pairs[k].contiguous() for k in keys])
-            else:
-                rts = [ops.compose_rel_proj(pairs[k]) for k in keys]
+            hyp, misc, rts = cascade_setup(disp_range, [pairs[k].contiguous() for k in keys], D1)
         g_min, g_max = misc[3:4], misc[4:5]
         preds, inter = [], {}
         conf = None
@@ -455,27 +450,12 @@ class Effi_MVS_plus(nn.Module):
             if s > 0:
                 ops.mark("stage{}".format(s))              # end of the previous stage
             nhwc, rt, (_, h, w) = geo[s]
-            if s == 0 and stage1 is not None:
-                weights, cur_vol, reg_vol = stage1["weights"], stage1["cur_vol"], stage1["reg_vol"]
-                depth, c, inv_next, conf = stage1["depth"], stage1["c"], stage1["inv_next"], stage1["conf"]
-                if conf is None:
+            if s == 0:
+                weights, cur_vol, reg_vol, depth, c, inv_next, conf = [stage1[k] for k in self._STAGE1_KEYS] if stage1 is not None else \
+                    stage1_volume(table if table is not None else nhwc, rt, hyp, D1, self.cost_regularization, self.PixelwiseNet, disp_range,
+                                  x3=bool(ops.option("warp_x3")))
+                if conf is None:                       # (option conf_fused off) the confidence map is only an output: off the critical path
                     with ops.Branch() as tail_branch:
-                        conf = ops.upsample_nearest(c.unsqueeze(0), 4)[0]
-                preds.append(depth)
-                lo_cur, hi_cur = g_min, g_max
-            elif s == 0:
-                if table is not None:
-                    sim_views, entropy = ops.warpcorr_views_tbl(table, 0, rt, hyp, D1, x3=bool(ops.option("warp_x3")))
-                else:
-                    sim_views, entropy = ops.warpcorr_views(nhwc[0], nhwc[1:], rt, hyp, D1, x3=bool(ops.option("warp_x3")))
-                weights = self.PixelwiseNet.run(entropy)
-                cur_vol = ops.view_aggregate(sim_views, weights)
-                reg_vol = self.cost_regularization.run(cur_vol.unsqueeze(0))[0][0]
-                if ops.option("conf_fused"):           # the full-size confidence map comes out of the same launch
-                    depth, c, inv_next, conf = ops.softmax_regress_conf(reg_vol, hyp, disp_range, conf_up=4)
-                else:
-                    depth, c, inv_next = ops.softmax_regress_conf(reg_vol, hyp, disp_range)     # + depth_to_inv of it (:538)
-                    with ops.Branch() as tail_branch:      # the confidence map is only an output: off the critical path
                         conf = ops.upsample_nearest(c.unsqueeze(0), 4)[0]
                 preds.append(depth)
                 lo_cur, hi_cur = g_min, g_max
@@ -511,35 +491,7 @@ class Effi_MVS_plus(nn.Module):
                 prep_joined = True
             hidden, inp = st[s]
             inv_cur = (inv_next if inv_next is not None else ops.depth_to_inv(preds[-1], disp_range)).unsqueeze(0)
-            cur_c, reg_c, lo_c, hi_c, itv = cur_vol, reg_vol, lo_cur, hi_cur, misc[s:s + 1]
-
-            def lookup(inv_depth, out=None, cur_c=cur_c, reg_c=reg_c, lo_c=lo_c, hi_c=hi_c, itv=itv, h=h, w=w):
-                return ops.getcost(inv_depth, disp_range, itv, cur_c, reg_c, lo_c, hi_c, self.CostNum, h, w, out=out)
-
-            def lookup_conv1x1(inv_depth, weight, bias, cout, out=None, cur_c=cur_c, reg_c=reg_c, lo_c=lo_c, hi_c=hi_c,
-                               itv=itv, h=h, w=w):
-                return ops.getcost_conv1x1(inv_depth, disp_range, itv, cur_c, reg_c, lo_c, hi_c, self.CostNum, h, w,
-                                           weight, bias, cout, relu=True, out=out)
-
-            def lookup_encoder_inputs(inv_depth, wc1, bc1, wd1, bd1, cout, out_c1=None, out_d1=None, cur_c=cur_c, reg_c=reg_c,
-                                      lo_c=lo_c, hi_c=hi_c, itv=itv, h=h, w=w):
-                return ops.encoder_inputs(inv_depth, disp_range, itv, cur_c, reg_c, lo_c, hi_c, self.CostNum, h, w,
-                                          wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
-
-            def lookup_encoder_inputs_sr(inv_depth, wc1, bc1, wd1, bd1, cout, out_c1, out_d1, cur_c=cur_c, reg_c=reg_c,
-                                         lo_c=lo_c, hi_c=hi_c, itv=itv, h=h, w=w):
-                return ops.encoder_inputs_sr(inv_depth, disp_range, itv, cur_c, reg_c, lo_c, hi_c, self.CostNum, h, w,
-                                             wc1, bc1, wd1, bd1, cout, out_c1, out_d1)
-
-            lookup.conv1x1 = lookup_conv1x1 if self.CostNum in (2, 3, 4) else None
-            lookup.encoder_inputs = lookup_encoder_inputs if self.CostNum == 3 else None
-            def lookup_encoder_pair_sr(inv_depth, wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2, cur_c=cur_c, reg_c=reg_c,
-                                       lo_c=lo_c, hi_c=hi_c, itv=itv, h=h, w=w):
-                return ops.encoder_pair_gen_sr(inv_depth, disp_range, itv, cur_c, reg_c, lo_c, hi_c, self.CostNum, h, w,
-                                               wc1, bc1, wd1, bd1, hd, wc2, bc2, out_c2, wd2, bd2, out_d2, hd)
-
-            lookup.encoder_inputs_sr = lookup_encoder_inputs_sr if self.CostNum == 3 else None
-            lookup.encoder_pair_sr = lookup_encoder_pair_sr if self.CostNum == 3 else None
+            lookup = CostLookup(disp_range, misc[s:s + 1], cur_vol, reg_vol, lo_cur, hi_cur, self.CostNum)
             _, masks, invs, depths = self.update_block[s].run_fused(hidden, lookup, inv_cur, inp, self.seq_len[s],
                                                                      disp_range, fuse_upsample=not want_intermediates,
                                                                      sr_maps=None if sr_maps is None else sr_maps[s],
@@ -560,7 +512,6 @@ class Effi_MVS_plus(nn.Module):
         return out
 
     @ops.on_tensor_device
-
     def forward_hot(self, features, cnet_depth, proj_matrices, depth_values, want_intermediates=False):
         """The accelerated path: everything of ``forward`` after the FPN (reference: Effi_MVS_plus.py:437-568).
 
@@ -593,7 +544,6 @@ class Effi_MVS_plus(nn.Module):
         return res
 
     @ops.on_tensor_device
-
     def forward(self, imgs, proj_matrices, depth_values):
         # kept for callers that use it like the reference does (Effi_MVS_plus.py:423)
         disp_min = depth_values[:, 0, None, None, None]

@@ -2,7 +2,7 @@
 
 All functions take fp32 CUDA (ROCm) tensors without a batch dimension and enqueue on the current
 stream.  CPU tensors raise: there is no fallback path.  The feature pyramid's convolutions (image batches) and the wrappers of the
-stage-1 cost volume (sample batches, ``_smp`` below) also take a leading batch dimension: ONE launch, element i bitwise the
+stage-1 cost volume (sample batches, ``_sample_form`` below) also take a leading batch dimension: ONE launch, element i bitwise the
 unbatched call on element i.
 """
 from __future__ import annotations
@@ -358,16 +358,10 @@ def _int_array(vals):
 def compose_rel_proj(pairs: torch.Tensor) -> torch.Tensor:
     """pairs [N,2,4,4] -> rt [N-1,12]  (K.[R|t] then P_src . P_ref^-1).  Sample batch: [n,N,2,4,4] -> [n,N-1,12], one launch."""
     pairs = _samples(pairs)
-    if pairs.dim() == 5:
-        n, ps = _smp(pairs, 4, "pairs")
-        rt = torch.empty(n, pairs.shape[1] - 1, 12, device=pairs.device, dtype=torch.float32)
-        check(_lib.lib().effi_compose_rel_proj_f32_batch(_p(pairs), pairs.shape[1], _p(rt), n, ps, rt.stride(0), _stream()),
-              "effi_compose_rel_proj_f32_batch")
-        return rt
-    _t(pairs, "pairs")
-    n = pairs.shape[0]
-    rt = torch.empty(n - 1, 12, device=pairs.device, dtype=torch.float32)
-    check(_lib.lib().effi_compose_rel_proj_f32(_p(pairs), n, _p(rt), _stream()), "effi_compose_rel_proj_f32")
+    n, ps = _in(pairs, 4, "pairs")
+    nv = pairs.shape[-4]
+    rt = torch.empty((() if n is None else (n,)) + (nv - 1, 12), device=pairs.device, dtype=torch.float32)
+    _launch("effi_compose_rel_proj_f32", (_p(pairs), nv, _p(rt)), n, lambda: (ps, rt.stride(0)))
     return rt
 
 
@@ -384,12 +378,11 @@ def compose_rel_proj_stages(pairs_list):
     return [rt[k] for k in range(len(pairs_list))]
 
 
-# ---- sample batches of the stage-1 cost volume ----------------------------------------------------------------------------------
-def _smp(x, nd, name):
-    """Sample form of one tensor argument: ``nd`` dims = ONE tensor (in a batched call: shared by all samples, stride 0), ``nd + 1``
-    dims = [n, ...] with contiguous samples at ANY uniform sample stride (a slice of a larger allocation is fine; an expanded
-    leading dimension is stride 0) -> (n or None, sample stride in floats)."""
-    _t(x, name, contiguous=False)
+# ---- sample forms: a tensor argument is ONE item, or a batch [n, ...] of them ----------------------------------------------------
+def _sample_form(x, nd, name):
+    """Sample form of one tensor argument, read from its shape and strides alone: ``nd`` dims = ONE item (beside batched tensors:
+    shared by all samples, stride 0), ``nd + 1`` dims = [n, ...] with contiguous items at ANY uniform item stride (a slice of a
+    larger allocation is fine; an expanded leading dimension, or n == 1, is stride 0) -> (n or None, item stride in floats)."""
     if x.dim() == nd:
         if not x.is_contiguous():
             raise ValueError(f"{name}: must be contiguous")
@@ -401,12 +394,86 @@ def _smp(x, nd, name):
     return x.shape[0], (x.stride(0) if x.shape[0] > 1 else 0)
 
 
-def _smp_count(counts, what):
+def _sample_count(counts, what):
     """The one sample count of a call's tensors (None entries = unbatched tensors); ValueError when they disagree."""
     ns = {c for c in counts if c is not None}
     if len(ns) > 1:
         raise ValueError(f"{what}: sample counts differ ({sorted(ns)})")
     return ns.pop() if ns else None
+
+
+def _sample_forms(tensors, nd, name):
+    """``_sample_form`` of several tensors of one call -> (their one sample count or None, [item strides])."""
+    forms = [_sample_form(x, nd, name) for x in tensors]
+    return _sample_count([f[0] for f in forms], name), [f[1] for f in forms]
+
+
+def _in(x, nd, name):
+    """An input tensor of a wrapper: the device / dtype / workspace check (``_t``), then its sample form."""
+    _t(x, name, contiguous=False)
+    return _sample_form(x, nd, name)
+
+
+def _depth_strides(depth, n, D, h, w):
+    """Depth hypotheses -> (tensor, hypothesis stride, pixel stride, sample stride).  Unbatched call (``n`` None): [D] (uniform),
+    [D,h,w] contiguous, or an expanded [D,h,w] view.  Batched call: [D] shared by all samples, [n,D], or [n,D,h,w] (contiguous, or
+    expanded over the map as the reference passes them); these are checked against ``D`` and the map size."""
+    k = 0 if n is None else 1                   # position of the hypothesis dimension in the per-pixel forms
+    if depth.dim() not in (1, k + 1, k + 3):
+        raise ValueError("depth hypotheses: expected " + ("[D] or [D,h,w]" if n is None else "[D], [n,D] or [n,D,h,w]")
+                         + f", got {tuple(depth.shape)}")
+    if n is not None:
+        per_pixel = depth.dim() == 4
+        if depth.shape[min(1, depth.dim() - 1)] != D or (per_pixel and tuple(depth.shape[2:]) != (h, w)):
+            raise ValueError(f"depth hypotheses: {tuple(depth.shape)} do not hold D = {D} hypotheses" + (f" on a {h} x {w} map" if per_pixel else ""))
+        if depth.dim() > 1 and depth.shape[0] != n:
+            raise ValueError(f"depth hypotheses: sample counts differ ({n} and {depth.shape[0]})")
+    if depth.dim() == 1:
+        return (depth if depth.is_contiguous() else depth.contiguous()), 1, 0, 0
+    st = depth.stride()
+    if depth.dim() == 2:
+        if st[1] != 1 or st[0] < 0:
+            depth = depth.contiguous()
+        dds, dps = 1, 0
+    elif st[k + 1] == 0 and st[k + 2] == 0 and min(st) >= 0:
+        dds, dps = st[k], 0
+    else:
+        if not depth.is_contiguous():
+            depth = depth.contiguous()
+        dds, dps = h * w, 1
+    return depth, dds, dps, (depth.stride(0) if n is not None and n > 1 else 0)
+
+
+def _launch(name, args, n, tail, key=None, work=None, x3=False):
+    """The one C call of a wrapper: the plain entry ``name`` for an unbatched call (``n`` None), else its ``_batch`` twin with the
+    sample count and the strides of ``tail()`` appended.  ``key`` / ``work``: the profile record of ``_call``; ``x3``: a
+    split-precision entry (``_x3``)."""
+    if n is not None:
+        name, args = name + "_batch", args + (n,) + tail()
+    fn = _x3(name) if x3 else getattr(_lib.lib(), name)
+    check(fn(*args, _stream()) if key is None else _call(key, work, fn, *args, _stream()), name)
+
+
+def _long_array(vals):
+    return (C.c_long * len(vals))(*[int(v) for v in vals])
+
+
+def _batch_out(out, shape, dev, name):
+    """Output of a batched convolution: allocated [n, ...], or the caller's (images contiguous, uniform image stride)."""
+    if out is None:
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    _t(out, name, contiguous=False)
+    if tuple(out.shape) != tuple(shape) or not out[0].is_contiguous() or (shape[0] > 1 and out.stride(0) < out[0].numel()):
+        raise ValueError(f"{name}: expected {tuple(shape)} with contiguous, non-overlapping images")
+    return out
+
+
+def _out(n, shape, dev, out, name):
+    """Output ``shape`` of a convolution: unbatched (``n`` None) the caller's ``out`` as it is, or allocated; [n, ...] in a batched
+    call (``_batch_out``)."""
+    if n is not None:
+        return _batch_out(out, (n,) + shape, dev, name)
+    return torch.empty(shape, device=dev, dtype=torch.float32) if out is None else out
 
 
 def as_samples(tensors):
@@ -435,46 +502,27 @@ def _samples(x):
     return torch.stack(list(x)) if v is None else v
 
 
-def _cascade_setup_batch(disp_range, D, pairs_list):
-    n, rs = _smp(disp_range, 1, "disp_range")
-    strides = []
-    for p_ in pairs_list:
-        m, ps = _smp(p_, 4, "pairs")
-        if m != n:
-            raise ValueError(f"cascade_setup: sample counts differ ({n} ranges, {m} camera sets)")
-        strides.append(ps)
-    nv = pairs_list[0].shape[1]
-    if len(pairs_list) > 4 or any(p_.shape[1] != nv for p_ in pairs_list):
-        raise ValueError("cascade_setup: up to 4 stages with the same number of views")
-    dev = disp_range.device
-    depths = torch.empty(n, D, device=dev, dtype=torch.float32)
-    intervals = torch.empty(n, 5, device=dev, dtype=torch.float32)
-    rt = torch.empty(n, len(pairs_list), nv - 1, 12, device=dev, dtype=torch.float32)
-    check(_lib.lib().effi_cascade_setup_f32_batch(_p(disp_range), disp_range.shape[1], D, _p(depths), _p(intervals), _ptr_array(pairs_list),
-                                                  len(pairs_list), nv, _p(rt), n, rs, D, 5, _long_array(strides), rt.stride(0), _stream()),
-          "effi_cascade_setup_f32_batch")
-    return (depths, intervals), [rt[:, k] for k in range(len(pairs_list))]
-
-
 def cascade_setup(disp_range, D, pairs_list):
     """``stage1_hypotheses`` and ``compose_rel_proj_stages`` in one launch -> ((depths [D], intervals [5]), [rt [N-1,12], ...]).
     Sample batch: disp_range [n,R] and pairs [n,N,2,4,4] -> ((depths [n,D], intervals [n,5]), [rt [n,N-1,12], ...]), one launch."""
     disp_range, pairs_list = _samples(disp_range), [_samples(p_) for p_ in pairs_list]
-    if disp_range.dim() == 2:
-        return _cascade_setup_batch(disp_range, D, pairs_list)
-    _t(disp_range, "disp_range")
+    n, rs = _in(disp_range, 1, "disp_range")
+    strides = []
     for p_ in pairs_list:
-        _t(p_, "pairs")
-    n = pairs_list[0].shape[0]
-    if len(pairs_list) > 4 or any(p_.shape[0] != n for p_ in pairs_list):
+        m, ps = _in(p_, 4, "pairs")
+        if m != n:
+            raise ValueError(f"cascade_setup: sample counts differ ({n} ranges, {m} camera sets)")
+        strides.append(ps)
+    nv = pairs_list[0].shape[-4]
+    if len(pairs_list) > 4 or any(p_.shape[-4] != nv for p_ in pairs_list):
         raise ValueError("cascade_setup: up to 4 stages with the same number of views")
-    dev = disp_range.device
-    depths = torch.empty(D, device=dev, dtype=torch.float32)
-    intervals = torch.empty(5, device=dev, dtype=torch.float32)   # 3 intervals, depth_min_, depth_max_
-    rt = torch.empty(len(pairs_list), n - 1, 12, device=dev, dtype=torch.float32)
-    check(_lib.lib().effi_cascade_setup_f32(_p(disp_range), disp_range.numel(), D, _p(depths), _p(intervals), _ptr_array(pairs_list),
-                                            len(pairs_list), n, _p(rt), _stream()), "effi_cascade_setup_f32")
-    return (depths, intervals), [rt[k] for k in range(len(pairs_list))]
+    dev, lead = disp_range.device, () if n is None else (n,)
+    depths = torch.empty(lead + (D,), device=dev, dtype=torch.float32)
+    intervals = torch.empty(lead + (5,), device=dev, dtype=torch.float32)   # 3 intervals, depth_min_, depth_max_
+    rt = torch.empty(lead + (len(pairs_list), nv - 1, 12), device=dev, dtype=torch.float32)
+    _launch("effi_cascade_setup_f32", (_p(disp_range), disp_range.shape[-1], D, _p(depths), _p(intervals), _ptr_array(pairs_list),
+                                       len(pairs_list), nv, _p(rt)), n, lambda: (rs, D, 5, _long_array(strides), rt.stride(0)))
+    return (depths, intervals), [rt.select(-3, k) for k in range(len(pairs_list))]
 
 
 def rel_proj(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch.Tensor:
@@ -484,72 +532,47 @@ def rel_proj(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch.Tensor:
     return rt
 
 
-def _to_nhwc_batch(feats):
-    """``to_nhwc`` of [n,C,h,w] maps -> [n,h,w,C] maps: passed through when every sample is channel-last in memory, else ALL of
-    them are transposed into one [n,N,h,w,C] allocation (one uniform sample stride for the batched warp)."""
-    n, C_, h, w = feats[0].shape
+def to_nhwc(feats):
+    """list of planar [C,h,w] maps -> list of channel-last [h,w,C] maps.  A map that is already channel-last in memory
+    (torch.channels_last) is passed through without a copy; the others (of one shape) are transposed into ONE allocation.  Sample
+    batch: [n,C,h,w] maps -> [n,h,w,C] maps (the transposed ones at one uniform sample stride, as the batched warp wants them)."""
+    batched = feats[0].dim() == 4
+    out, todo = [], []
     for f in feats:
         _t(f, "feature", contiguous=False)
-        if tuple(f.shape) != (n, C_, h, w):
-            raise ValueError("to_nhwc: feature maps of a batch must share one shape")
-    if C_ > 1 and all(f[0].permute(1, 2, 0).is_contiguous() for f in feats):
-        return [f.permute(0, 2, 3, 1) for f in feats]
-    dst = torch.empty(n, len(feats), h, w, C_, device=feats[0].device, dtype=torch.float32)
+        if f.dim() != feats[0].dim() or f.dim() not in (3, 4) or (batched and f.shape[0] != feats[0].shape[0]):
+            raise ValueError("to_nhwc: expected [C,h,w] maps, or [n,C,h,w] maps of one n")
+        last = f.movedim(-3, -1)
+        if f.shape[-3] > 1 and (last[0] if batched else last).is_contiguous():
+            out.append(last)
+        else:
+            todo.append(len(out))
+            out.append(None)
+    if not todo:
+        return out
+    shape = feats[todo[0]].shape
+    if any(feats[i].shape != shape for i in todo):
+        raise ValueError("to_nhwc: the planar feature maps of a call must share one shape")
+    C_, h, w = shape[-3:]
+    dst = torch.empty(tuple(shape[:-3]) + (len(todo), h, w, C_), device=feats[0].device, dtype=torch.float32)
     src_l, dst_l = [], []
-    for v, f in enumerate(feats):
-        for b in range(n):
-            if not f[b].is_contiguous():
+    for j, i in enumerate(todo):
+        out[i] = dst.select(-4, j)
+        for s_, d_ in zip(feats[i] if batched else (feats[i],), out[i] if batched else (out[i],)):
+            if not s_.is_contiguous():
                 raise ValueError("feature map must be planar-contiguous or channels-last")
-            src_l.append(f[b])
-            dst_l.append(dst[b, v])
+            src_l.append(s_)
+            dst_l.append(d_)
     for k in range(0, len(src_l), MAX_VIEWS + 1):
         s_, d_ = src_l[k:k + MAX_VIEWS + 1], dst_l[k:k + MAX_VIEWS + 1]
         check(_lib.lib().effi_planar_to_nhwc_f32(_ptr_array(s_), _ptr_array(d_), len(s_), C_, h * w, _stream()), "effi_planar_to_nhwc_f32")
-    return [dst[:, v] for v in range(len(feats))]
-
-
-def to_nhwc(feats):
-    """list of planar [C,h,w] maps -> list of channel-last [h,w,C] maps.  A map that is already
-    channel-last in memory (torch.channels_last) is passed through without a copy.  Sample batch: [n,C,h,w] maps -> [n,h,w,C]."""
-    if feats[0].dim() == 4:
-        return _to_nhwc_batch(feats)
-    out, todo_src, todo_dst = [None] * len(feats), [], []
-    for i, f in enumerate(feats):
-        _t(f, "feature", contiguous=False)
-        C_, h, w = f.shape
-        if f.permute(1, 2, 0).is_contiguous() and C_ > 1:
-            out[i] = f.permute(1, 2, 0)
-        else:
-            if not f.is_contiguous():
-                raise ValueError("feature map must be planar-contiguous or channels-last")
-            d = torch.empty(h, w, C_, device=f.device, dtype=torch.float32)
-            out[i] = d
-            todo_src.append(f)
-            todo_dst.append(d)
-    if todo_src:
-        C_, h, w = todo_src[0].shape
-        for k in range(0, len(todo_src), MAX_VIEWS + 1):
-            s, d = todo_src[k:k + MAX_VIEWS + 1], todo_dst[k:k + MAX_VIEWS + 1]
-            check(_lib.lib().effi_planar_to_nhwc_f32(_ptr_array(s), _ptr_array(d), len(s), C_, h * w, _stream()),
-                  "effi_planar_to_nhwc_f32")
     return out
-
-
-def _depth_strides(depth: torch.Tensor, D, h, w):
-    """depth hypotheses given as [D] (uniform), [D,h,w] contiguous, or an expanded [D,h,w] view."""
-    if depth.dim() == 1:
-        return depth, 1, 0
-    if depth.stride(1) == 0 and depth.stride(2) == 0:
-        return depth, depth.stride(0), 0
-    if not depth.is_contiguous():
-        depth = depth.contiguous()
-    return depth, h * w, 1
 
 
 def homo_warp(src_nhwc, rt, depth, D):
     h, w, Cc = src_nhwc.shape
     _t(src_nhwc, "src_nhwc"), _t(rt, "rt"), _t(depth, "depth", contiguous=False)
-    depth, dds, dps = _depth_strides(depth, D, h, w)
+    depth, dds, dps, _ = _depth_strides(depth, None, D, h, w)
     out = torch.empty(Cc, D, h, w, device=src_nhwc.device, dtype=torch.float32)
     check(_lib.lib().effi_homo_warp_f32(_p(src_nhwc), _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(out), _stream()),
           "effi_homo_warp_f32")
@@ -560,70 +583,11 @@ def homo_warp_bwd(rt, depth, D, grad_out, h, w):
     """Backward of ``homo_warp`` w.r.t. the source features: grad_out [C,D,h,w] -> grad_src [h,w,C] (scope row n2)."""
     _t(rt, "rt"), _t(depth, "depth", contiguous=False), _t(grad_out, "grad_out")
     Cc = grad_out.shape[0]
-    depth, dds, dps = _depth_strides(depth, D, h, w)
+    depth, dds, dps, _ = _depth_strides(depth, None, D, h, w)
     g_src = torch.zeros(h, w, Cc, device=grad_out.device, dtype=torch.float32)
     check(_lib.lib().effi_homo_warp_bwd_f32(_p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(grad_out), _p(g_src), _stream()),
           "effi_homo_warp_bwd_f32")
     return g_src
-
-
-def _depth_strides_batch(depth, n, D, h, w):
-    """Hypotheses of a batched call -> (tensor, dstride, pstride, sample stride): [D] shared by all samples, [n,D], or [n,D,h,w]
-    (contiguous, or expanded over the map as the reference passes them)."""
-    _t(depth, "depth", contiguous=False)
-    if depth.dim() not in (1, 2, 4):
-        raise ValueError(f"depth hypotheses: expected [D], [n,D] or [n,D,h,w], got {tuple(depth.shape)}")
-    if depth.shape[min(1, depth.dim() - 1)] != D or (depth.dim() == 4 and tuple(depth.shape[2:]) != (h, w)):
-        raise ValueError(f"depth hypotheses: {tuple(depth.shape)} do not hold D = {D} hypotheses" + (f" on a {h} x {w} map" if depth.dim() == 4 else ""))
-    if depth.dim() == 1:
-        return (depth if depth.is_contiguous() else depth.contiguous()), 1, 0, 0
-    if depth.shape[0] != n:
-        raise ValueError(f"depth hypotheses: sample counts differ ({n} and {depth.shape[0]})")
-    if depth.dim() == 2:
-        if depth.stride(1) != 1 or depth.stride(0) < 0:
-            depth = depth.contiguous()
-        return depth, 1, 0, (depth.stride(0) if n > 1 else 0)
-    if depth.stride(2) == 0 and depth.stride(3) == 0 and depth.stride(1) >= 0 and depth.stride(0) >= 0:
-        return depth, depth.stride(1), 0, (depth.stride(0) if n > 1 else 0)
-    if not depth.is_contiguous():
-        depth = depth.contiguous()
-    return depth, h * w, 1, (depth.stride(0) if n > 1 else 0)
-
-
-def _warpcorr_views_batch(ref_nhwc, srcs_nhwc, rt, depth, D, x3):
-    n, rs = _smp(ref_nhwc, 3, "ref_nhwc")
-    _, h, w, Cc = ref_nhwc.shape
-    S = len(srcs_nhwc)
-    sstr = set()
-    for s_ in srcs_nhwc:
-        m, ss = _smp(s_, 3, "src_nhwc")
-        if tuple(s_.shape[1:]) != (h, w, Cc):
-            raise ValueError("source / reference feature shapes differ")
-        if m != n:
-            raise ValueError(f"warpcorr_views: sample counts differ ({n} and {m})")
-        sstr.add(ss)
-    m, rts = _smp(rt, 2, "rt")
-    if m != n:
-        raise ValueError(f"warpcorr_views: sample counts differ ({n} maps, {m} projection sets)")
-    if rt.shape[1] != S:
-        raise ValueError("Different number of images and projection matrices")
-    if len(sstr) > 1:               # sources at different sample strides: not expressible as pointer list + ONE stride -> per sample
-        outs = [warpcorr_views(ref_nhwc[b], [s_[b] for s_ in srcs_nhwc], rt[b], depth if depth.dim() == 1 else depth[b], D, x3=x3)
-                for b in range(n)]
-        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
-    depth, dds, dps, dss = _depth_strides_batch(depth, n, D, h, w)
-    sim = torch.empty(n, S, D, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    ent = torch.empty(n, S, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    work = lambda: {"flops": n * S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * n * h * w * (S * Cc + Cc + S * D + S)}
-    tail = (n, rs, sstr.pop(), rts, dss, sim.stride(0), ent.stride(0), _stream())
-    if x3 and uses_split():
-        check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_x3_f32_batch, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
-                    _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), int(_PRECISION == "bf16"), *tail),
-              "effi_warpcorr_views_x3_f32_batch")
-        return sim, ent
-    check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_f32_batch, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
-                _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), *tail), "effi_warpcorr_views_f32_batch")
-    return sim, ent
 
 
 def warpcorr_views(ref_nhwc, srcs_nhwc, rt, depth, D, x3=False):
@@ -633,28 +597,37 @@ def warpcorr_views(ref_nhwc, srcs_nhwc, rt, depth, D, x3=False):
     (``effi_warpcorr_views_x3_f32``: correlations of the tap pixels as split-precision MFMAs, then interpolated) -- inference only;
     the default is the exact fp32 kernel (what training and the exact-fp32 precision use)."""
     ref_nhwc, srcs_nhwc, rt, depth = _samples(ref_nhwc), [_samples(s_) for s_ in srcs_nhwc], _samples(rt), _samples(depth)
-    if ref_nhwc.dim() == 4:
-        return _warpcorr_views_batch(ref_nhwc, srcs_nhwc, rt, depth, D, x3)
-    h, w, Cc = ref_nhwc.shape
+    n, rs = _in(ref_nhwc, 3, "ref_nhwc")
+    h, w, Cc = ref_nhwc.shape[-3:]
     S = len(srcs_nhwc)
-    _t(ref_nhwc, "ref_nhwc"), _t(rt, "rt"), _t(depth, "depth", contiguous=False)
-    for s in srcs_nhwc:
-        _t(s, "src_nhwc")
-        if tuple(s.shape) != (h, w, Cc):
+    sstr = set()
+    for s_ in srcs_nhwc:
+        m, ss = _in(s_, 3, "src_nhwc")
+        if tuple(s_.shape[-3:]) != (h, w, Cc):
             raise ValueError("source / reference feature shapes differ")
-    if rt.shape[0] != S:
+        if m != n:
+            raise ValueError(f"warpcorr_views: sample counts differ ({n} and {m})")
+        sstr.add(ss)
+    m, rts = _in(rt, 2, "rt")
+    if m != n:
+        raise ValueError(f"warpcorr_views: sample counts differ ({n} maps, {m} projection sets)")
+    if rt.shape[-2] != S:
         raise ValueError("Different number of images and projection matrices")
-    depth, dds, dps = _depth_strides(depth, D, h, w)
-    sim = torch.empty(S, D, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    ent = torch.empty(S, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    work = lambda: {"flops": S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * h * w * (S * Cc + Cc + S * D + S)}
-    if x3 and uses_split():
-        check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_x3_f32, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
-                    _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), int(_PRECISION == "bf16"), _stream()),
-              "effi_warpcorr_views_x3_f32")
-        return sim, ent
-    check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_f32, _p(ref_nhwc), _ptr_array(srcs_nhwc), S,
-                _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent), _stream()), "effi_warpcorr_views_f32")
+    _t(depth, "depth", contiguous=False)
+    if len(sstr) > 1:               # sources at different sample strides: not expressible as pointer list + ONE stride -> per sample
+        outs = [warpcorr_views(ref_nhwc[b], [s_[b] for s_ in srcs_nhwc], rt[b], depth if depth.dim() == 1 else depth[b], D, x3=x3)
+                for b in range(n)]
+        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+    depth, dds, dps, dss = _depth_strides(depth, n, D, h, w)
+    lead, reps = (() if n is None else (n,)), n or 1
+    sim = torch.empty(lead + (S, D, h, w), device=ref_nhwc.device, dtype=torch.float32)
+    ent = torch.empty(lead + (S, h, w), device=ref_nhwc.device, dtype=torch.float32)
+    work = lambda: {"flops": reps * S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * reps * h * w * (S * Cc + Cc + S * D + S)}
+    x3 = bool(x3) and uses_split()
+    _launch("effi_warpcorr_views_x3_f32" if x3 else "effi_warpcorr_views_f32",
+            (_p(ref_nhwc), _ptr_array(srcs_nhwc), S, _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent))
+            + ((int(_PRECISION == "bf16"),) if x3 else ()),
+            n, lambda: (rs, sstr.pop(), rts, dss, sim.stride(0), ent.stride(0)), key=f"warpcorr_views_c{Cc}", work=work)
     return sim, ent
 
 
@@ -667,7 +640,7 @@ def warpcorr_views_bwd(ref_nhwc, srcs_nhwc, rt, depth, D, grad_sim):
         _t(s_, "src_nhwc")
     if tuple(grad_sim.shape) != (S, D, h, w):
         raise ValueError(f"grad_sim {tuple(grad_sim.shape)} does not match (S, D, h, w) = {(S, D, h, w)}")
-    depth, dds, dps = _depth_strides(depth, D, h, w)
+    depth, dds, dps, _ = _depth_strides(depth, None, D, h, w)
     g_ref = torch.zeros_like(ref_nhwc)          # accumulated per source view by the windowed kernel
     g_src = [torch.zeros_like(s_) for s_ in srcs_nhwc]
     check(_lib.lib().effi_warpcorr_views_bwd_f32(_p(ref_nhwc), _ptr_array(srcs_nhwc), S, _p(rt), _p(depth), dds, dps, Cc, h, w, D,
@@ -726,7 +699,7 @@ def warpcorr_views_tbl(table, stage, rt, depth, D, x3=False):
     _t(rt, "rt"), _t(depth, "depth", contiguous=False)
     if rt.shape[0] != S:
         raise ValueError("Different number of images and projection matrices")
-    depth, dds, dps = _depth_strides(depth, D, h, w)
+    depth, dds, dps, _ = _depth_strides(depth, None, D, h, w)
     sim = torch.empty(S, D, h, w, device=rt.device, dtype=torch.float32)
     ent = torch.empty(S, h, w, device=rt.device, dtype=torch.float32)
     work = lambda: {"flops": S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * h * w * (S * Cc + Cc + S * D + S)}
@@ -774,27 +747,18 @@ def pixelwise_net(entropy, params):
 
 
 def view_aggregate(sim_views, weights):
-    """sum_v sim_v w_v / (sum_v w_v + 1e-6); ``weights`` None = the plain mean over the views (pixel_wise_net = None)."""
+    """sum_v sim_v w_v / (sum_v w_v + 1e-6); ``weights`` None = the plain mean over the views (pixel_wise_net = None).  Sample
+    batch: sim_views [n,S,D,h,w], weights [n,S,h,w] or None -> [n,D,h,w], one launch."""
     sim_views, weights = _samples(sim_views), _samples(weights)
-    if sim_views.dim() == 5:            # sample batch: sim_views [n,S,D,h,w], weights [n,S,h,w] or None -> [n,D,h,w], one launch
-        n, ss = _smp(sim_views, 4, "sim_views")
-        _, S, D, h, w = sim_views.shape
-        ws = 0
-        if weights is not None:
-            m, ws = _smp(weights, 3, "weights")
-            if m != n or weights.shape[1] != S:
-                raise ValueError(f"view_aggregate: sample / view counts differ ({n} x {S} volumes, weights {tuple(weights.shape)})")
-        out = torch.empty(n, D, h, w, device=sim_views.device, dtype=torch.float32)
-        check(_lib.lib().effi_view_aggregate_f32_batch(_p(sim_views), _p(weights), S, D, h * w, _p(out), n, ss, ws, out.stride(0),
-                                                       _stream()), "effi_view_aggregate_f32_batch")
-        return out
-    S, D, h, w = sim_views.shape
-    _t(sim_views, "sim_views")
+    n, ss = _in(sim_views, 4, "sim_views")
+    S, D, h, w = sim_views.shape[-4:]
+    ws = 0
     if weights is not None:
-        _t(weights, "weights")
-    out = torch.empty(D, h, w, device=sim_views.device, dtype=torch.float32)
-    check(_lib.lib().effi_view_aggregate_f32(_p(sim_views), _p(weights), S, D, h * w, _p(out), _stream()),
-          "effi_view_aggregate_f32")
+        m, ws = _in(weights, 3, "weights")
+        if m != n or weights.shape[-3] != S:
+            raise ValueError(f"view_aggregate: sample / view counts differ ({n} x {S} volumes, weights {tuple(weights.shape)})")
+    out = torch.empty((() if n is None else (n,)) + (D, h, w), device=sim_views.device, dtype=torch.float32)
+    _launch("effi_view_aggregate_f32", (_p(sim_views), _p(weights), S, D, h * w, _p(out)), n, lambda: (ss, ws, out.stride(0)))
     return out
 
 
@@ -822,20 +786,41 @@ def warpcorr_dyn(ref_nhwc, srcs_nhwc, rt, cur_depth, interval, view_w, D):
     return sim, samples
 
 
-def _vol_samples(srcs, skip, what):
-    """(n, source strides, skip stride) of a batched 3-D convolution's tensors [n,C,D,h,w]."""
-    forms = [_smp(s_, 4, what + " input") for s_ in srcs]
-    n = _smp_count([f[0] for f in forms] + ([skip.shape[0]] if skip is not None and skip.dim() == 5 else []), what)
-    if any(f[0] is None for f in forms):
+def _conv_out(size, stride):
+    """Output extent of a 3-tap pad-1 (or 5-tap pad-2) convolution at ``stride``."""
+    return (size - 1) // stride + 1
+
+
+def _channels(srcs, axis):
+    """Channel counts of a convolution's concatenated sources -> (the C array the entries take, their sum)."""
+    chans = [s_.shape[axis] for s_ in srcs]
+    return _int_array(chans), sum(chans)
+
+
+def _vol_inputs(srcs, skip, what):
+    """The [C,D,h,w] sources and the skip volume of a 3-D convolution, or sample batches [n,C,D,h,w] of them ->
+    (n or None, source strides, skip stride, (D, h, w))."""
+    for s_ in srcs:
+        _t(s_, what + " input", contiguous=False)
+    n, sstr = _sample_forms(srcs, 4, what + " input")
+    if n is not None and any(s_.dim() != 5 for s_ in srcs):
         raise ValueError(f"{what}: every source of a batched call must be [n,C,D,h,w]")
-    if any(tuple(s_.shape[-3:]) != tuple(srcs[0].shape[-3:]) for s_ in srcs):
+    if any(s_.shape[-3:] != srcs[0].shape[-3:] for s_ in srcs):
         raise ValueError(f"{what}: the sources must share one (D, h, w), got {[tuple(s_.shape) for s_ in srcs]}")
     ks = 0
     if skip is not None:
-        m, ks = _smp(skip, 4, "skip")
+        m, ks = _in(skip, 4, "skip")
         if m != n:
             raise ValueError(f"{what}: skip must be [n, ...] with n = {n}")
-    return n, [f[1] for f in forms], ks
+    return n, sstr, ks, tuple(srcs[0].shape[-3:])
+
+
+def _vol_out(n, shape, dev, skip, out=None):
+    """Output volume ``shape`` of a 3-D convolution ([n, ...] in a batched call, where it may be the caller's ``out``)."""
+    out = _out(n, shape, dev, out, "conv3d output")
+    if skip is not None:
+        assert skip.shape == out.shape, f"skip {tuple(skip.shape)} vs out {tuple(out.shape)}"
+    return out
 
 
 def conv3d_k3(srcs, weight, bias, cout, stride=(1, 1, 1), relu=True, skip=None, out=None):
@@ -843,208 +828,100 @@ def conv3d_k3(srcs, weight, bias, cout, stride=(1, 1, 1), relu=True, skip=None, 
     convolution wrappers): sources / skip [n,...] -> [n,cout,Do,ho,wo] in one launch; ``out`` may be [n,...] slices of a larger
     allocation."""
     srcs, skip = [_samples(s_) for s_ in srcs], _samples(skip)
-    if srcs[0].dim() == 5:
-        n, sstr, ks = _vol_samples(srcs, skip, "conv3d")
-        D, h, w = srcs[0].shape[-3:]
-        sz, sxy = int(stride[0]), int(stride[1])
-        Do, ho, wo = (D - 1) // sz + 1, (h - 1) // sxy + 1, (w - 1) // sxy + 1
-        out = _batch_out(out, (n, cout, Do, ho, wo), srcs[0].device, "conv3d output")
-        if skip is not None:
-            assert skip.shape == out.shape
-        cin = sum(s_.shape[1] for s_ in srcs)
-        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * Do * ho * wo,
-                        "bytes": 4.0 * n * (cin * D * h * w + cout * Do * ho * wo * (2 if skip is not None else 1))}
-        check(_call(f"conv3d_c{'8' if cout % 8 == 0 else '1'}_s{sz}{sxy}", work, _lib.lib().effi_conv3d_k3_f32_batch, _ptr_array(srcs),
-                    _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(weight), _p(bias), cout, D, h, w, sz, sxy, int(relu),
-                    _p(skip), _p(out), n, _long_array(sstr), ks, out.stride(0) if n > 1 else 0, _stream()), "effi_conv3d_k3_f32_batch")
-        return out
-    if out is not None:
+    n, sstr, ks, (D, h, w) = _vol_inputs(srcs, skip, "conv3d")
+    if n is None and out is not None:
         raise ValueError("conv3d_k3: out= belongs to the batched call")
-    for s in srcs:
-        _t(s, "conv3d input")
-    _, D, h, w = srcs[0].shape
     sz, sxy = int(stride[0]), int(stride[1])
-    Do, ho, wo = (D - 1) // sz + 1, (h - 1) // sxy + 1, (w - 1) // sxy + 1
-    out = torch.empty(cout, Do, ho, wo, device=srcs[0].device, dtype=torch.float32)
-    if skip is not None:
-        _t(skip, "skip")
-        assert skip.shape == out.shape
-    cin = sum(s.shape[0] for s in srcs)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * Do * ho * wo,
-                    "bytes": 4.0 * (cin * D * h * w + cout * Do * ho * wo * (2 if skip is not None else 1))}
-    check(_call(f"conv3d_c{'8' if cout % 8 == 0 else '1'}_s{sz}{sxy}", work, _lib.lib().effi_conv3d_k3_f32, _ptr_array(srcs),
-                _int_array([s.shape[0] for s in srcs]), len(srcs), _p(weight), _p(bias), cout, D, h, w, sz, sxy, int(relu),
-                _p(skip), _p(out), _stream()), "effi_conv3d_k3_f32")
+    Do, ho, wo = _conv_out(D, sz), _conv_out(h, sxy), _conv_out(w, sxy)
+    out = _vol_out(n, (cout, Do, ho, wo), srcs[0].device, skip, out)
+    chans, cin = _channels(srcs, -4)
+    reps = n or 1
+    work = lambda: {"flops": 2.0 * 27 * reps * cin * cout * Do * ho * wo,
+                    "bytes": 4.0 * reps * (cin * D * h * w + cout * Do * ho * wo * (2 if skip is not None else 1))}
+    _launch("effi_conv3d_k3_f32", (_ptr_array(srcs), chans, len(srcs), _p(weight), _p(bias), cout, D, h, w, sz, sxy, int(relu),
+                                   _p(skip), _p(out)), n, lambda: (_long_array(sstr), ks, out.stride(0) if n > 1 else 0),
+            key=f"conv3d_c{'8' if cout % 8 == 0 else '1'}_s{sz}{sxy}", work=work)
+    return out
+
+
+def _conv3d_one(x, wpack, bias, cout, relu, s, key, name, x3):
+    """The 3-D convolutions of ONE planar source x [cin,D,h,w] (or [n,cin,D,h,w]) at stride (s,s,s) -> [cout,Do,ho,wo]."""
+    x = _samples(x)
+    n, xs = _in(x, 4, "conv3d input")
+    cin, D, h, w = x.shape[-4:]
+    Do, ho, wo = _conv_out(D, s), _conv_out(h, s), _conv_out(w, s)
+    out = _vol_out(n, (cout, Do, ho, wo), x.device, None)
+    reps = n or 1
+    work = lambda: {"flops": 2.0 * 27 * reps * cin * cout * Do * ho * wo, "bytes": 4.0 * reps * (cin * D * h * w + cout * Do * ho * wo)}
+    _launch(name, (_p(x), cin, _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out)), n, lambda: (xs, out.stride(0)), key=key, work=work,
+            x3=x3)
     return out
 
 
 def conv3d_k3s1_mfma(x, wpack, bias, cout, relu=True):
     """x planar [cin,D,h,w]; stride-1 3-D conv as z-batched 2-D MFMA convs -> [cout,D,h,w]."""
-    x = _samples(x)
-    if x.dim() == 5:
-        n, xs = _smp(x, 4, "conv3d input")
-        _, cin, D, h, w = x.shape
-        out = torch.empty(n, cout, D, h, w, device=x.device, dtype=torch.float32)
-        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
-        check(_call(f"conv3d_mfma_nt{cout // 16}", work, _lib.lib().effi_conv3d_k3s1_mfma_f32_batch, _p(x), cin, _p(wpack), _p(bias), cout,
-                    D, h, w, int(relu), _p(out), n, xs, out.stride(0), _stream()), "effi_conv3d_k3s1_mfma_f32_batch")
-        return out
-    _t(x, "conv3d input")
-    cin, D, h, w = x.shape
-    out = torch.empty(cout, D, h, w, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * D * h * w, "bytes": 4.0 * (cin + cout) * D * h * w}
-    check(_call(f"conv3d_mfma_nt{cout // 16}", work, _lib.lib().effi_conv3d_k3s1_mfma_f32, _p(x), cin, _p(wpack), _p(bias), cout,
-                D, h, w, int(relu), _p(out), _stream()), "effi_conv3d_k3s1_mfma_f32")
+    return _conv3d_one(x, wpack, bias, cout, relu, 1, f"conv3d_mfma_nt{cout // 16}", "effi_conv3d_k3s1_mfma_f32", False)
+
+
+def conv3d_k3s2_x3(x, wpack, bias, cout, relu=True):
+    """x planar [cin,D,h,w] (w % 4 == 0); stride-(2,2,2) 3-D conv in split precision (``packing.pack_conv3d_s2_bf16x3``) ->
+    [cout,Do,ho,wo]."""
+    return _conv3d_one(x, wpack, bias, cout, relu, 2, f"conv3d_s2x3_nt{(cout + 15) // 16}", "effi_conv3d_k3s2_bf16x3_f32", True)
+
+
+def conv3d_k3s2_mfma(x, wpack, bias, cout, relu=True):
+    """x planar [cin,D,h,w]; stride-(2,2,2) 3-D conv as z-batched stride-2 2-D MFMA convs -> [cout,Do,ho,wo]."""
+    return _conv3d_one(x, wpack, bias, cout, relu, 2, f"conv3d_mfma_s2_nt{cout // 16}", "effi_conv3d_k3s2_mfma_f32", False)
+
+
+def _conv3d_s1_x3(srcs, wpack, bias, cout, relu, key, name):
+    """The stride-1 split-precision 3-D convolutions of concatenated sources; ``key`` is formatted with cin // 8 and cout's tiles."""
+    srcs = [_samples(s_) for s_ in srcs]
+    n, sstr, _, (D, h, w) = _vol_inputs(srcs, None, "conv3d")
+    chans, cin = _channels(srcs, -4)
+    out = _vol_out(n, (cout, D, h, w), srcs[0].device, None)
+    reps = n or 1
+    work = lambda: {"flops": 2.0 * 27 * reps * cin * cout * D * h * w, "bytes": 4.0 * reps * (cin + cout) * D * h * w}
+    _launch(name, (_ptr_array(srcs), chans, len(srcs), _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out)), n,
+            lambda: (_long_array(sstr), out.stride(0)), key=key.format(oct=cin // 8, nt=(cout + 15) // 16), work=work, x3=True)
     return out
 
 
 def conv3d_k3s1_bf16x3(srcs, wpack, bias, cout, relu=True):
     """srcs: planar [Ci,D,h,w] tensors (channel concatenation); stride-1 3-D conv as z-batched 2-D convs in split precision
     (``packing.pack_conv3d_planes_bf16x3``) -> [cout,D,h,w].  w % 4 == 0, cout <= 32."""
-    srcs = [_samples(s_) for s_ in srcs]
-    if srcs[0].dim() == 5:
-        n, sstr, _ = _vol_samples(srcs, None, "conv3d")
-        D, h, w = srcs[0].shape[-3:]
-        cin = sum(s_.shape[1] for s_ in srcs)
-        out = torch.empty(n, cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
-        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
-        check(_call(f"conv3d_x3_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_bf16x3_f32_batch"), _ptr_array(srcs), _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(wpack),
-                    _p(bias), cout, D, h, w, int(relu), _p(out), n, _long_array(sstr), out.stride(0), _stream()),
-              "effi_conv3d_k3s1_bf16x3_f32_batch")
-        return out
-    for s in srcs:
-        _t(s, "conv3d input")
-    _, D, h, w = srcs[0].shape
-    cin = sum(s.shape[0] for s in srcs)
-    out = torch.empty(cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * D * h * w, "bytes": 4.0 * (cin + cout) * D * h * w}
-    check(_call(f"conv3d_x3_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_bf16x3_f32"), _ptr_array(srcs),
-                _int_array([s.shape[0] for s in srcs]), len(srcs), _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out),
-                _stream()), "effi_conv3d_k3s1_bf16x3_f32")
-    return out
+    return _conv3d_s1_x3(srcs, wpack, bias, cout, relu, "conv3d_x3_nt{nt}", "effi_conv3d_k3s1_bf16x3_f32")
 
 
 def conv3d_k3s1_roll(srcs, wpack, bias, cout, relu=True):
     """srcs: one or two planar [Ci,D,h,w] tensors, 8 or 16 channels in total; stride-1 3-D conv with a rolling window of
     input planes in split precision (``packing.pack_conv3d_roll_bf16x3``) -> [cout,D,h,w].  w % 4 == 0, cout <= 32."""
-    srcs = [_samples(s_) for s_ in srcs]
-    if srcs[0].dim() == 5:
-        n, sstr, _ = _vol_samples(srcs, None, "conv3d")
-        D, h, w = srcs[0].shape[-3:]
-        cin = sum(s_.shape[1] for s_ in srcs)
-        out = torch.empty(n, cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
-        work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w, "bytes": 4.0 * n * (cin + cout) * D * h * w}
-        check(_call(f"conv3d_roll_oct{cin // 8}_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_roll_bf16x3_f32_batch"), _ptr_array(srcs), _int_array([s_.shape[1] for s_ in srcs]), len(srcs), _p(wpack),
-                    _p(bias), cout, D, h, w, int(relu), _p(out), n, _long_array(sstr), out.stride(0), _stream()),
-              "effi_conv3d_k3s1_roll_bf16x3_f32_batch")
-        return out
-    for s in srcs:
-        _t(s, "conv3d input")
-    _, D, h, w = srcs[0].shape
-    cin = sum(s.shape[0] for s in srcs)
-    out = torch.empty(cout, D, h, w, device=srcs[0].device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * D * h * w, "bytes": 4.0 * (cin + cout) * D * h * w}
-    check(_call(f"conv3d_roll_oct{cin // 8}_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s1_roll_bf16x3_f32"), _ptr_array(srcs),
-                _int_array([s.shape[0] for s in srcs]), len(srcs), _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out),
-                _stream()), "effi_conv3d_k3s1_roll_bf16x3_f32")
-    return out
+    return _conv3d_s1_x3(srcs, wpack, bias, cout, relu, "conv3d_roll_oct{oct}_nt{nt}", "effi_conv3d_k3s1_roll_bf16x3_f32")
 
 
-def _conv3d_s2_batch(x, wpack, bias, cout, relu, key, fn, what):
-    """The stride-(2,2,2) forms on [n,cin,D,h,w] in one launch."""
-    n, xs = _smp(x, 4, "conv3d input")
-    _, cin, D, h, w = x.shape
-    Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    out = torch.empty(n, cout, Do, ho, wo, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * n * cin * cout * Do * ho * wo, "bytes": 4.0 * n * (cin * D * h * w + cout * Do * ho * wo)}
-    check(_call(key, work, fn, _p(x), cin, _p(wpack), _p(bias), cout, D, h, w, int(relu), _p(out), n, xs, out.stride(0), _stream()), what)
-    return out
-
-
-def conv3d_k3s2_x3(x, wpack, bias, cout, relu=True):
-    """x planar [cin,D,h,w] (w % 4 == 0); stride-(2,2,2) 3-D conv in split precision (``packing.pack_conv3d_s2_bf16x3``) ->
-    [cout,Do,ho,wo]."""
-    x = _samples(x)
-    if x.dim() == 5:
-        return _conv3d_s2_batch(x, wpack, bias, cout, relu, f"conv3d_s2x3_nt{(cout + 15) // 16}", _x3("effi_conv3d_k3s2_bf16x3_f32_batch"),
-                                "effi_conv3d_k3s2_bf16x3_f32_batch")
-    _t(x, "conv3d input")
-    cin, D, h, w = x.shape
-    Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    out = torch.empty(cout, Do, ho, wo, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * Do * ho * wo, "bytes": 4.0 * (cin * D * h * w + cout * Do * ho * wo)}
-    check(_call(f"conv3d_s2x3_nt{(cout + 15) // 16}", work, _x3("effi_conv3d_k3s2_bf16x3_f32"), _p(x), cin, _p(wpack), _p(bias), cout,
-                D, h, w, int(relu), _p(out), _stream()), "effi_conv3d_k3s2_bf16x3_f32")
-    return out
-
-
-def conv3d_k3s2_mfma(x, wpack, bias, cout, relu=True):
-    """x planar [cin,D,h,w]; stride-(2,2,2) 3-D conv as z-batched stride-2 2-D MFMA convs -> [cout,Do,ho,wo]."""
-    x = _samples(x)
-    if x.dim() == 5:
-        return _conv3d_s2_batch(x, wpack, bias, cout, relu, f"conv3d_mfma_s2_nt{cout // 16}", _lib.lib().effi_conv3d_k3s2_mfma_f32_batch,
-                                "effi_conv3d_k3s2_mfma_f32_batch")
-    _t(x, "conv3d input")
-    cin, D, h, w = x.shape
-    Do, ho, wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    out = torch.empty(cout, Do, ho, wo, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * Do * ho * wo, "bytes": 4.0 * (cin * D * h * w + cout * Do * ho * wo)}
-    check(_call(f"conv3d_mfma_s2_nt{cout // 16}", work, _lib.lib().effi_conv3d_k3s2_mfma_f32, _p(x), cin, _p(wpack), _p(bias), cout,
-                D, h, w, int(relu), _p(out), _stream()), "effi_conv3d_k3s2_mfma_f32")
-    return out
-
-
-def _deconv3d_batch(x, wp, bias, cout, sz, relu, skip, key, fn, what, with_sz):
-    """The transposed forms on [n,cin,D,h,w] (+ skip [n,...]) in one launch."""
-    n, (xs,), ks = _vol_samples([x], skip, "deconv3d")
-    _, cin, D, h, w = x.shape
-    out = torch.empty(n, cout, sz * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
-    if skip is not None:
-        assert skip.shape == out.shape, f"skip {tuple(skip.shape)} vs out {tuple(out.shape)}"
-    work = lambda: {"flops": 2.0 * 27 * n * cin * cout * D * h * w,
-                    "bytes": 4.0 * n * (cin * D * h * w + cout * sz * D * 4 * h * w * (2 if skip is not None else 1))}
-    args = (_p(x), cin, _p(wp), _p(bias), cout, D, h, w) + ((sz,) if with_sz else ()) + (int(relu), _p(skip), _p(out), n, xs, ks,
-                                                                                      out.stride(0) if n > 1 else 0, _stream())
-    check(_call(key, work, fn, *args), what)
+def _deconv3d(x, wp, bias, cout, sz, relu, skip, key, name, x3):
+    """The transposed 3-D convolutions x [cin,D,h,w] (+ skip) -> [cout,sz*D,2h,2w], or sample batches of them in one launch; the
+    split-precision entry is stride (2,2,2) only and takes no ``sz``."""
+    x, skip = _samples(x), _samples(skip)
+    n, (xs,), ks, (D, h, w) = _vol_inputs([x], skip, "deconv3d")
+    cin = x.shape[-4]
+    out = _vol_out(n, (cout, sz * D, 2 * h, 2 * w), x.device, skip)
+    reps = n or 1
+    work = lambda: {"flops": 2.0 * 27 * reps * cin * cout * D * h * w,
+                    "bytes": 4.0 * reps * (cin * D * h * w + cout * sz * D * 4 * h * w * (2 if skip is not None else 1))}
+    _launch(name, (_p(x), cin, _p(wp), _p(bias), cout, D, h, w) + (() if x3 else (sz,)) + (int(relu), _p(skip), _p(out)), n,
+            lambda: (xs, ks, out.stride(0) if n > 1 else 0), key=key, work=work, x3=x3)
     return out
 
 
 def deconv3d_k3(x, weight, bias, cout, sz=2, relu=True, skip=None):
-    x, skip = _samples(x), _samples(skip)
-    if x.dim() == 5:
-        return _deconv3d_batch(x, weight, bias, cout, sz, relu, skip, f"deconv3d_c{cout if cout == 1 else 8}_s{sz}",
-                               _lib.lib().effi_deconv3d_k3_f32_batch, "effi_deconv3d_k3_f32_batch", True)
-    _t(x, "deconv3d input")
-    cin, D, h, w = x.shape
-    out = torch.empty(cout, sz * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
-    if skip is not None:
-        _t(skip, "skip")
-        assert skip.shape == out.shape, f"skip {tuple(skip.shape)} vs out {tuple(out.shape)}"
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * D * h * w,
-                    "bytes": 4.0 * (cin * D * h * w + cout * sz * D * 4 * h * w * (2 if skip is not None else 1))}
-    check(_call(f"deconv3d_c{cout if cout == 1 else 8}_s{sz}", work, _lib.lib().effi_deconv3d_k3_f32, _p(x), cin, _p(weight),
-                _p(bias), cout, D, h, w, sz, int(relu), _p(skip), _p(out), _stream()), "effi_deconv3d_k3_f32")
-    return out
+    return _deconv3d(x, weight, bias, cout, sz, relu, skip, f"deconv3d_c{cout if cout == 1 else 8}_s{sz}", "effi_deconv3d_k3_f32", False)
 
 
 def deconv3d_k3s2_x3(x, wpack, bias, cout, relu=True, skip=None):
     """Transposed 3-D conv, stride (2,2,2), on the bf16 matrix cores in split precision
     (``packing.pack_deconv3d_s2_bf16x3``): x [cin,D,h,w] -> [cout,2D,2h,2w] (+ skip after the ReLU)."""
-    x, skip = _samples(x), _samples(skip)
-    if x.dim() == 5:
-        return _deconv3d_batch(x, wpack, bias, cout, 2, relu, skip, "deconv3d_x3", _x3("effi_deconv3d_k3s2_bf16x3_f32_batch"),
-                               "effi_deconv3d_k3s2_bf16x3_f32_batch", False)
-    _t(x, "deconv3d input")
-    cin, D, h, w = x.shape
-    out = torch.empty(cout, 2 * D, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
-    if skip is not None:
-        _t(skip, "skip")
-        assert skip.shape == out.shape, f"skip {tuple(skip.shape)} vs out {tuple(out.shape)}"
-    work = lambda: {"flops": 2.0 * 27 * cin * cout * D * h * w,
-                    "bytes": 4.0 * (cin * D * h * w + cout * 8 * D * h * w * (2 if skip is not None else 1))}
-    check(_call("deconv3d_x3", work, _x3("effi_deconv3d_k3s2_bf16x3_f32"), _p(x), cin, _p(wpack), _p(bias), cout,
-                D, h, w, int(relu), _p(skip), _p(out), _stream()), "effi_deconv3d_k3s2_bf16x3_f32")
-    return out
+    return _deconv3d(x, wpack, bias, cout, 2, relu, skip, "deconv3d_x3", "effi_deconv3d_k3s2_bf16x3_f32", True)
 
 
 def fusion_dynamic_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf=None, prob_threshold=0.0, dh_view_num=2,
@@ -1331,56 +1208,33 @@ def resize_planar(x, dst_h, dst_w, out=None):
     return out
 
 
-def _softmax_regress_conf_batch(logits, depth, disp_range, conf_up):
-    """``softmax_regress_conf`` on logits [n,D,h,w] with hypotheses [D] / [n,D] / [n,D,h,w] and per-sample disp_range [n,R] (or one
-    [R] for all): every result with a leading n, one launch."""
-    n, ls = _smp(logits, 3, "logits")
-    _, D, h, w = logits.shape
-    depth, dds, dps, dss = _depth_strides_batch(depth, n, D, h, w)
-    dev = logits.device
-    od = torch.empty(n, h, w, device=dev, dtype=torch.float32)
-    oc = torch.empty(n, h, w, device=dev, dtype=torch.float32)
-    oi, n_range, rs = None, 0, 0
-    if disp_range is not None:
-        m, rs = _smp(disp_range, 1, "disp_range")
-        if m is not None and m != n:
-            raise ValueError(f"softmax_regress_conf: sample counts differ ({n} volumes, {m} ranges)")
-        oi, n_range = torch.empty(n, h, w, device=dev, dtype=torch.float32), disp_range.shape[-1]
-    if conf_up:
-        ou = torch.empty(n, h * conf_up, w * conf_up, device=dev, dtype=torch.float32)
-        check(_lib.lib().effi_softmax_regress_conf_up_f32_batch(_p(logits), _p(depth), dds, dps, D, h, w, _p(od), _p(oc), _p(disp_range),
-                                                                 n_range, _p(oi), _p(ou), conf_up, n, ls, dss, h * w, h * w, rs, h * w,
-                                                                 ou.stride(0), _stream()), "effi_softmax_regress_conf_up_f32_batch")
-        return (od, oc, ou) if disp_range is None else (od, oc, oi, ou)
-    check(_lib.lib().effi_softmax_regress_conf_f32_batch(_p(logits), _p(depth), dds, dps, D, h * w, _p(od), _p(oc), _p(disp_range), n_range,
-                                                          _p(oi), n, ls, dss, h * w, h * w, rs, h * w, _stream()),
-          "effi_softmax_regress_conf_f32_batch")
-    return (od, oc) if disp_range is None else (od, oc, oi)
-
-
 def softmax_regress_conf(logits, depth, disp_range=None, conf_up=0):
     """logits [D,h,w]; depth [D] / [D,h,w] -> (depth [h,w], confidence [h,w]) and, with ``disp_range``, also the regressed
     depth as normalised inverse depth (``depth_to_inv`` of it, written by the same kernel).  ``conf_up`` = f > 0: the result
-    tuple ends with the confidence replicated f x f ([h*f,w*f], ``upsample_nearest`` of it) written by the same kernel."""
+    tuple ends with the confidence replicated f x f ([h*f,w*f], ``upsample_nearest`` of it) written by the same kernel.
+    Sample batch: logits [n,D,h,w], depth [D] / [n,D] / [n,D,h,w], disp_range [n,R] (or one [R] for all) -> every result with a
+    leading n, one launch."""
     logits, depth, disp_range = _samples(logits), _samples(depth), _samples(disp_range)
-    if logits.dim() == 4:
-        return _softmax_regress_conf_batch(logits, depth, disp_range, conf_up)
-    D, h, w = logits.shape
-    _t(logits, "logits"), _t(depth, "depth", contiguous=False)
-    depth, dds, dps = _depth_strides(depth, D, h, w)
-    od = torch.empty(h, w, device=logits.device, dtype=torch.float32)
-    oc = torch.empty(h, w, device=logits.device, dtype=torch.float32)
-    oi, n_range = None, 0
+    n, ls = _in(logits, 3, "logits")
+    D, h, w = logits.shape[-3:]
+    _t(depth, "depth", contiguous=False)
+    depth, dds, dps, dss = _depth_strides(depth, n, D, h, w)
+    dev, lead = logits.device, () if n is None else (n,)
+    od = torch.empty(lead + (h, w), device=dev, dtype=torch.float32)
+    oc = torch.empty(lead + (h, w), device=dev, dtype=torch.float32)
+    oi, n_range, rs = None, 0, 0
     if disp_range is not None:
-        _t(disp_range, "disp_range")
-        oi, n_range = torch.empty(h, w, device=logits.device, dtype=torch.float32), disp_range.numel()
+        m, rs = _in(disp_range, 1, "disp_range")
+        if m is not None and m != n:
+            raise ValueError(f"softmax_regress_conf: sample counts differ ({n} volumes, {m} ranges)")
+        oi, n_range = torch.empty(lead + (h, w), device=dev, dtype=torch.float32), disp_range.shape[-1]
     if conf_up:
-        ou = torch.empty(h * conf_up, w * conf_up, device=logits.device, dtype=torch.float32)
-        check(_lib.lib().effi_softmax_regress_conf_up_f32(_p(logits), _p(depth), dds, dps, D, h, w, _p(od), _p(oc), _p(disp_range), n_range,
-                                                           _p(oi), _p(ou), conf_up, _stream()), "effi_softmax_regress_conf_up_f32")
+        ou = torch.empty(lead + (h * conf_up, w * conf_up), device=dev, dtype=torch.float32)
+        _launch("effi_softmax_regress_conf_up_f32", (_p(logits), _p(depth), dds, dps, D, h, w, _p(od), _p(oc), _p(disp_range), n_range,
+                                                     _p(oi), _p(ou), conf_up), n, lambda: (ls, dss, h * w, h * w, rs, h * w, ou.stride(0)))
         return (od, oc, ou) if disp_range is None else (od, oc, oi, ou)
-    check(_lib.lib().effi_softmax_regress_conf_f32(_p(logits), _p(depth), dds, dps, D, h * w, _p(od), _p(oc), _p(disp_range), n_range,
-                                                    _p(oi), _stream()), "effi_softmax_regress_conf_f32")
+    _launch("effi_softmax_regress_conf_f32", (_p(logits), _p(depth), dds, dps, D, h * w, _p(od), _p(oc), _p(disp_range), n_range, _p(oi)),
+            n, lambda: (ls, dss, h * w, h * w, rs, h * w))
     return (od, oc) if disp_range is None else (od, oc, oi)
 
 
@@ -1623,95 +1477,59 @@ def conv2d_k3_bf16x3_pair(srcs_a, wpack_a, bias_a, srcs_b, wpack_b, bias_b, cout
     return out_a, out_b
 
 
-def _images(tensors, name):
-    """Image-batch form of a convolution's tensors -> (n, image strides in floats); n is None when every tensor is 3-D (the
-    single-image call).  A 4-D tensor is [n,C,h,w] with contiguous images at ANY uniform image stride (a slice of a larger batch is
-    fine); a 3-D one beside it is shared by all images (stride 0)."""
-    n, strides = None, []
-    for t in tensors:
-        _t(t, name, contiguous=False)
-        if t.dim() == 4:
-            if n is None:
-                n = t.shape[0]
-            elif t.shape[0] != n:
-                raise ValueError(f"{name}: image counts differ ({n} and {t.shape[0]})")
-            if n < 1 or not t[0].is_contiguous():
-                raise ValueError(f"{name}: every image of a batch must be contiguous (the image stride itself is free)")
-            strides.append(t.stride(0) if n > 1 else 0)
-        elif t.dim() == 3:
-            if not t.is_contiguous():
-                raise ValueError(f"{name}: must be contiguous")
-            strides.append(0)
-        else:
-            raise ValueError(f"{name}: expected [C,h,w] or [n,C,h,w], got {tuple(t.shape)}")
-    return n, strides
+def _conv2d_out_shape(epilogue, cout, h, w):
+    """Shape of ``conv2d``'s outputs (both, where the epilogue has two) for one image."""
+    if epilogue == EPI_GRU_ZR:
+        return (cout // 2, h, w)
+    if epilogue == EPI_HEAD:
+        return (1, h, w)
+    if epilogue in (EPI_NHWC, EPI_NHWC_ADD_SHUF2):
+        return (h, w, cout)
+    return (cout, h, w)
 
 
-def _long_array(vals):
-    return (C.c_long * len(vals))(*[int(v) for v in vals])
-
-
-def _batch_out(out, shape, dev, name):
-    """Output of a batched convolution: allocated [n, ...], or the caller's (images contiguous, uniform image stride)."""
-    if out is None:
-        return torch.empty(shape, device=dev, dtype=torch.float32)
-    _t(out, name, contiguous=False)
-    if tuple(out.shape) != tuple(shape) or not out[0].is_contiguous() or (shape[0] > 1 and out.stride(0) < out[0].numel()):
-        raise ValueError(f"{name}: expected {tuple(shape)} with contiguous, non-overlapping images")
-    return out
-
-
-def _batch_aux(aux0, n, name):
-    """aux0 of a batched convolution, [n, ...] -> its image stride."""
-    if aux0 is None:
-        return 0
-    _t(aux0, name, contiguous=False)
-    if aux0.dim() != 4 or aux0.shape[0] != n:
-        raise ValueError(f"{name}: expected [n, ...] with n = {n}, got {tuple(aux0.shape)}")
-    if not aux0[0].is_contiguous():
-        raise ValueError(f"{name}: every image of a batch must be contiguous")
-    return aux0.stride(0) if n > 1 else 0
-
-
-def _conv2d_batch(n, istr, srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, split):
-    """``conv2d`` / ``conv2d_k3_bf16x3`` on n images in one launch (effi_conv2d_f32_batch / effi_conv2d_k3_bf16x3_f32_batch)."""
+def _conv2d(srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, split):
+    """``conv2d`` on the fp32 entry (effi_conv2d_f32) or, ``split``, ``conv2d_k3_bf16x3`` (effi_conv2d_k3_bf16x3_f32): one image, or
+    n images in one launch of the entry's ``_batch`` twin."""
     h, w = srcs[0].shape[-2:]
     dev = srcs[0].device
     for s in srcs:
+        _t(s, "conv2d input", contiguous=False)
         if tuple(s.shape[-2:]) != (h, w):
-            raise ValueError(f"conv2d: every source of a batch must be {h} x {w}, got {tuple(s.shape)}")
-    if n > 1 and aux1 is not None and (aux1.dim() != 4 or aux1.shape[0] != n):
+            raise ValueError(f"conv2d: every source of a call must be {h} x {w}, got {tuple(s.shape)}")
+    n, istr = _sample_forms(srcs, 3, "conv2d input")
+    if n is not None and n > 1 and aux1 is not None and (aux1.dim() != 4 or aux1.shape[0] != n):
         # (aux1 has no image stride in the library: the epilogues that read it are single-image only)
         raise ValueError(f"conv2d: aux1 of a batch must be [n, ...] with n = {n}")
-    if epilogue == EPI_GRU_ZR:
-        shape = (n, cout // 2, h, w)
-    elif epilogue == EPI_HEAD:
-        shape = (n, 1, h, w)
-    elif epilogue in (EPI_NHWC, EPI_NHWC_ADD_SHUF2):
-        shape = (n, h, w, cout)
-    else:
-        shape = (n, cout, h, w)
-    out0 = _batch_out(out0, shape, dev, "conv2d output")
+    shape = _conv2d_out_shape(epilogue, cout, h, w)
+    out0 = _out(n, shape, dev, out0, "conv2d output")
     if out1 is None and epilogue in (EPI_GRU_ZR, EPI_HEAD):
-        out1 = torch.empty(shape, device=dev, dtype=torch.float32)
-    if epilogue in (EPI_ADD_SHUF2, EPI_NHWC_ADD_SHUF2) and (aux0 is None or tuple(aux0.shape[1:]) != (4 * cout, h // 2, w // 2) or h % 2 or w % 2):
-        raise ValueError("conv2d_k3_bf16x3: the pixel-shuffled map must be [n, 4*cout, h/2, w/2]")
-    if epilogue == EPI_ADD_UP2 and (aux0 is None or tuple(aux0.shape[1:]) != (cout, h // 2, w // 2)):
-        raise ValueError("conv2d: the coarser map must be [n, cout, h/2, w/2]")
-    aux_stride = _batch_aux(aux0, n, "conv2d aux0")
-    cin = sum(s.shape[-3] for s in srcs)
-    chans = _int_array([s.shape[-3] for s in srcs])
-    work = lambda: {"flops": 2.0 * n * h * w * cin * cout * ks * ks, "bytes": 4.0 * n * h * w * (cin + cout)}
-    n_range = 0 if disp_range is None else disp_range.numel()
-    tail = (n, _long_array(istr), aux_stride, out0.stride(0) if n > 1 else 0, _stream())
+        out1 = torch.empty(shape if n is None else (n,) + shape, device=dev, dtype=torch.float32)
+    if epilogue in (EPI_ADD_SHUF2, EPI_NHWC_ADD_SHUF2) and (aux0 is None or tuple(aux0.shape[-3:]) != (4 * cout, h // 2, w // 2) or h % 2 or w % 2):
+        raise ValueError("conv2d_k3_bf16x3: the pixel-shuffled map must be [4*cout, h/2, w/2] ([n, ...] in a batch)")
+    if epilogue == EPI_ADD_UP2 and (aux0 is None or tuple(aux0.shape[-3:]) != (cout, h // 2, w // 2)):
+        raise ValueError("conv2d: the coarser map must be [cout, h/2, w/2] ([n, ...] in a batch)")
+    aux_stride = 0
+    if aux0 is not None:
+        if n is None:
+            _t(aux0, "conv2d aux0")
+        else:
+            m, aux_stride = _in(aux0, 3, "conv2d aux0")
+            if m != n:
+                raise ValueError(f"conv2d aux0: expected [n, ...] with n = {n}, got {tuple(aux0.shape)}")
+    chans, cin = _channels(srcs, -3)
+    reps, sfx = (1, "") if n is None else (n, "_batch")
+    work = lambda: {"flops": 2.0 * reps * h * w * cin * cout * ks * ks, "bytes": 4.0 * reps * h * w * (cin + cout)}
+    tail = lambda: (_long_array(istr), aux_stride, out0.stride(0) if n > 1 else 0)
     if split:
-        check(_call(f"conv2d_k3x3_nt{(cout + 15) // 16}_epi{epilogue}_batch", work, _x3("effi_conv2d_k3_bf16x3_f32_batch"), _ptr_array(srcs),
-                    chans, len(srcs), _p(wpack), _p(bias), cout, h, w, epilogue, act, _p(aux0), _p(aux1), None, 0, _p(out0), _p(out1),
-                    *tail), "effi_conv2d_k3_bf16x3_f32_batch")
+        _launch("effi_conv2d_k3_bf16x3_f32", (_ptr_array(srcs), chans, len(srcs), _p(wpack), _p(bias), cout, h, w, epilogue, act, _p(aux0),
+                                              _p(aux1), None, 0, _p(out0), _p(out1)), n, tail,
+                key=f"conv2d_k3x3_nt{(cout + 15) // 16}_epi{epilogue}{sfx}", work=work, x3=True)
     else:
-        check(_call(f"conv2d_k{ks}_nt{(cout + 15) // 16}_epi{epilogue}_batch", work, _lib.lib().effi_conv2d_f32_batch, _ptr_array(srcs),
-                    chans, len(srcs), _p(wpack), _p(bias), cout, ks, h, w, epilogue, act, _p(aux0), _p(aux1), _p(disp_range), n_range,
-                    _p(out0), _p(out1), *tail), "effi_conv2d_f32_batch")
+        n_range = 0 if disp_range is None else disp_range.numel()
+        _launch("effi_conv2d_f32", (_ptr_array(srcs), chans, len(srcs), _p(wpack), _p(bias), cout, ks, h, w, epilogue, act, _p(aux0),
+                                    _p(aux1), _p(disp_range), n_range, _p(out0), _p(out1)), n, tail,
+                key=f"conv2d_k{ks}_nt{(cout + 15) // 16}_epi{epilogue}{sfx}", work=work)
     return (out0, out1) if out1 is not None else out0
 
 
@@ -1728,42 +1546,11 @@ def conv2d(srcs, wpack, bias, cout, ks, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=N
     """2-D convolution (ks 1 or 3) of the concatenated planar sources [C,h,w].  Image batch: sources [n,C,h,w] (all the same n; a
     3-D source beside them is shared by all images), ``aux0`` [n,...], outputs [n,...] -- ONE launch, image i bitwise the 3-D call
     on image i (epilogues PLAIN, NHWC, ADD_UP2; the library reports UNSUPPORTED for the others when n > 1)."""
-    n, istr = _images(srcs, "conv2d input") if any(s.dim() == 4 for s in srcs) else (None, None)
-    if n is not None:
-        if hasattr(wpack, "w32"):
-            if _conv2d_takes_split(srcs, wpack, ks, epilogue):
-                return _conv2d_batch(n, istr, srcs, wpack.wx, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
-            wpack = wpack.w32
-        return _conv2d_batch(n, istr, srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, False)
-    for s in srcs:
-        _t(s, "conv2d input")
-    h, w = srcs[0].shape[-2:]
-    dev = srcs[0].device
-    if out0 is None:
-        if epilogue == EPI_GRU_ZR:
-            out0 = torch.empty(cout // 2, h, w, device=dev, dtype=torch.float32)
-        elif epilogue == EPI_HEAD:
-            out0 = torch.empty(1, h, w, device=dev, dtype=torch.float32)
-        elif epilogue == EPI_NHWC:
-            out0 = torch.empty(h, w, cout, device=dev, dtype=torch.float32)
-        else:
-            out0 = torch.empty(cout, h, w, device=dev, dtype=torch.float32)
-    if out1 is None and epilogue == EPI_GRU_ZR:
-        out1 = torch.empty(cout // 2, h, w, device=dev, dtype=torch.float32)
-    if out1 is None and epilogue == EPI_HEAD:
-        out1 = torch.empty(1, h, w, device=dev, dtype=torch.float32)
-    n_range = 0 if disp_range is None else disp_range.numel()
-    cin = sum(s.shape[0] for s in srcs)
     if hasattr(wpack, "w32"):                 # packing.Conv2dWeights: both operand orders, pick the arithmetic here
         if _conv2d_takes_split(srcs, wpack, ks, epilogue):
-            return conv2d_k3_bf16x3(srcs, wpack.wx, bias, cout, epilogue=epilogue, act=act, aux0=aux0, aux1=aux1,
-                                    out0=out0, out1=out1)
+            return _conv2d(srcs, wpack.wx, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
         wpack = wpack.w32
-    work = lambda: {"flops": 2.0 * h * w * cin * cout * ks * ks, "bytes": 4.0 * h * w * (cin + cout)}
-    check(_call(f"conv2d_k{ks}_nt{(cout + 15) // 16}_epi{epilogue}", work, _lib.lib().effi_conv2d_f32, _ptr_array(srcs),
-                _int_array([s.shape[0] for s in srcs]), len(srcs), _p(wpack), _p(bias), cout, ks, h, w, epilogue, act,
-                _p(aux0), _p(aux1), _p(disp_range), n_range, _p(out0), _p(out1), _stream()), "effi_conv2d_f32")
-    return (out0, out1) if out1 is not None else out0
+    return _conv2d(srcs, wpack, bias, cout, ks, epilogue, act, aux0, aux1, disp_range, out0, out1, False)
 
 
 def conv2d_k3_bf16x3(srcs, wpack, bias, cout, epilogue=EPI_PLAIN, act=ACT_NONE, aux0=None, aux1=None, out0=None, out1=None):
@@ -1771,32 +1558,7 @@ def conv2d_k3_bf16x3(srcs, wpack, bias, cout, epilogue=EPI_PLAIN, act=ACT_NONE, 
     ``packing.pack_conv2d_bf16x3``.  Same sources / epilogues as ``conv2d`` (PLAIN, NHWC, GRU_ZR, GRU_Q); w % 4 == 0 and every
     source but the last has a multiple of 8 channels (otherwise the library reports UNSUPPORTED).  Image batch as ``conv2d``
     (epilogues PLAIN, NHWC, ADD_SHUF2, NHWC_ADD_SHUF2 for n > 1)."""
-    if any(s.dim() == 4 for s in srcs):
-        n, istr = _images(srcs, "conv2d input")
-        return _conv2d_batch(n, istr, srcs, wpack, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
-    for s in srcs:
-        _t(s, "conv2d input")
-    h, w = srcs[0].shape[-2:]
-    dev = srcs[0].device
-    if out0 is None:
-        if epilogue == EPI_GRU_ZR:
-            out0 = torch.empty(cout // 2, h, w, device=dev, dtype=torch.float32)
-        elif epilogue in (EPI_NHWC, EPI_NHWC_ADD_SHUF2):
-            out0 = torch.empty(h, w, cout, device=dev, dtype=torch.float32)
-        else:
-            out0 = torch.empty(cout, h, w, device=dev, dtype=torch.float32)
-    if out1 is None and epilogue == EPI_GRU_ZR:
-        out1 = torch.empty(cout // 2, h, w, device=dev, dtype=torch.float32)
-    if epilogue in (EPI_ADD_SHUF2, EPI_NHWC_ADD_SHUF2):
-        _t(aux0, "coarser map")
-        if tuple(aux0.shape) != (4 * cout, h // 2, w // 2) or h % 2 or w % 2:
-            raise ValueError("conv2d_k3_bf16x3: the pixel-shuffled map must be [4*cout, h/2, w/2]")
-    cin = sum(s.shape[0] for s in srcs)
-    work = lambda: {"flops": 2.0 * h * w * cin * cout * 9, "bytes": 4.0 * h * w * (cin + cout)}
-    check(_call(f"conv2d_k3x3_nt{(cout + 15) // 16}_epi{epilogue}", work, _x3("effi_conv2d_k3_bf16x3_f32"), _ptr_array(srcs),
-                _int_array([s.shape[0] for s in srcs]), len(srcs), _p(wpack), _p(bias), cout, h, w, epilogue, act,
-                _p(aux0), _p(aux1), None, 0, _p(out0), _p(out1), _stream()), "effi_conv2d_k3_bf16x3_f32")
-    return (out0, out1) if out1 is not None else out0
+    return _conv2d(srcs, wpack, bias, cout, 3, epilogue, act, aux0, aux1, None, out0, out1, True)
 
 
 # =============================================================================================
@@ -2149,21 +1911,13 @@ def conv2d_k3_twice(x, w1, b1, w2, b2, cout, out=None):
     """relu(conv3x3(relu(conv3x3(x)))) with at most 8 channels into each layer (8 between them) in one kernel, the intermediate map
     in LDS (``packing.pack_conv2d_bf16x3_oct`` weights): the pyramid's full-resolution block.  x [cin<=8,h,w] -> [cout<=8,h,w], or
     an image batch [n,cin,h,w] -> [n,cout,h,w] in one launch (image i bitwise the 3-D call on image i)."""
-    if x.dim() == 4:
-        n, (istr,) = _images([x], "conv input")
-        _, cin, h, w = x.shape
-        out = _batch_out(out, (n, cout, h, w), x.device, "conv output")
-        work = lambda: {"flops": 2.0 * n * h * w * 9 * (cin * 8 + 8 * cout), "bytes": 4.0 * n * h * w * (cin + cout)}
-        check(_call("conv2d_k3_twice_batch", work, _x3("effi_conv2d_k3_twice_bf16x3_f32_batch"), _p(x), cin, _p(w1), _p(b1), _p(w2), _p(b2),
-                    cout, h, w, _p(out), n, istr, out.stride(0) if n > 1 else 0, _stream()), "effi_conv2d_k3_twice_bf16x3_f32_batch")
-        return out
-    _t(x, "conv input")
-    cin, h, w = x.shape
-    if out is None:
-        out = torch.empty(cout, h, w, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * h * w * 9 * (cin * 8 + 8 * cout), "bytes": 4.0 * h * w * (cin + cout)}
-    check(_call("conv2d_k3_twice", work, _x3("effi_conv2d_k3_twice_bf16x3_f32"), _p(x), cin, _p(w1), _p(b1), _p(w2), _p(b2), cout, h, w,
-                _p(out), _stream()), "effi_conv2d_k3_twice_bf16x3_f32")
+    n, istr = _in(x, 3, "conv input")
+    cin, h, w = x.shape[-3:]
+    out = _out(n, (cout, h, w), x.device, out, "conv output")
+    reps, sfx = (1, "") if n is None else (n, "_batch")
+    work = lambda: {"flops": 2.0 * reps * h * w * 9 * (cin * 8 + 8 * cout), "bytes": 4.0 * reps * h * w * (cin + cout)}
+    _launch("effi_conv2d_k3_twice_bf16x3_f32", (_p(x), cin, _p(w1), _p(b1), _p(w2), _p(b2), cout, h, w, _p(out)), n,
+            lambda: (istr, out.stride(0) if n > 1 else 0), key="conv2d_k3_twice" + sfx, work=work, x3=True)
     return out
 
 
@@ -2206,35 +1960,19 @@ def conv2d_k3_k1_up2x(srcs, wpack, bias, cout1, w2pack, bias2, inv_depth, disp_r
 def conv2d_k5s2(x, wpack, bias, cout, act=ACT_RELU):
     """5x5 stride-2 pad-2 convolution (+bias, activation): x planar [cin,hin,win] -> [cout,ceil(hin/2),ceil(win/2)], or an image
     batch [n,cin,hin,win] -> [n,cout,...] in one launch (image i bitwise the 3-D call on image i)."""
-    if x.dim() == 4:
-        n, (istr,) = _images([x], "conv input")
-        _, cin, hin, win = x.shape
-        ho, wo = (hin - 1) // 2 + 1, (win - 1) // 2 + 1
-        out = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
-        work = lambda: {"flops": 2.0 * n * ho * wo * cin * cout * 25, "bytes": 4.0 * n * (hin * win * cin + ho * wo * cout)}
-        tail = (cout, hin, win, act, _p(out), n, istr, out.stride(0) if n > 1 else 0, _stream())
-        if hasattr(wpack, "w32"):
-            if uses_split() and wpack.wx is not None and win % 4 == 0 and _PY_OPTS["k5s2_split"] != 0:
-                check(_call(f"conv2d_k5s2x3_nt{(cout + 15) // 16}_batch", work, _x3("effi_conv2d_k5s2_bf16x3_f32_batch"), _p(x), cin,
-                            _p(wpack.wx), _p(bias), *tail), "effi_conv2d_k5s2_bf16x3_f32_batch")
-                return out
-            wpack = wpack.w32
-        check(_call(f"conv2d_k5s2_nt{(cout + 15) // 16}_batch", work, _lib.lib().effi_conv2d_k5s2_f32_batch, _p(x), cin, _p(wpack), _p(bias),
-                    *tail), "effi_conv2d_k5s2_f32_batch")
-        return out
-    _t(x, "conv input")
-    cin, hin, win = x.shape
-    ho, wo = (hin - 1) // 2 + 1, (win - 1) // 2 + 1
-    out = torch.empty(cout, ho, wo, device=x.device, dtype=torch.float32)
-    work = lambda: {"flops": 2.0 * ho * wo * cin * cout * 25, "bytes": 4.0 * (hin * win * cin + ho * wo * cout)}
+    n, istr = _in(x, 3, "conv input")
+    cin, hin, win = x.shape[-3:]
+    ho, wo = _conv_out(hin, 2), _conv_out(win, 2)
+    out = _out(n, (cout, ho, wo), x.device, None, "conv output")
+    reps, sfx = (1, "") if n is None else (n, "_batch")
+    work = lambda: {"flops": 2.0 * reps * ho * wo * cin * cout * 25, "bytes": 4.0 * reps * (hin * win * cin + ho * wo * cout)}
+    split = False
     if hasattr(wpack, "w32"):                 # packing.Conv2dWeights: pick the arithmetic here
-        if uses_split() and wpack.wx is not None and win % 4 == 0 and _PY_OPTS["k5s2_split"] != 0:
-            check(_call(f"conv2d_k5s2x3_nt{(cout + 15) // 16}", work, _x3("effi_conv2d_k5s2_bf16x3_f32"), _p(x), cin, _p(wpack.wx), _p(bias),
-                        cout, hin, win, act, _p(out), _stream()), "effi_conv2d_k5s2_bf16x3_f32")
-            return out
-        wpack = wpack.w32
-    check(_call(f"conv2d_k5s2_nt{(cout + 15) // 16}", work, _lib.lib().effi_conv2d_k5s2_f32, _p(x), cin, _p(wpack), _p(bias), cout,
-                hin, win, act, _p(out), _stream()), "effi_conv2d_k5s2_f32")
+        split = uses_split() and wpack.wx is not None and win % 4 == 0 and _PY_OPTS["k5s2_split"] != 0
+        wpack = wpack.wx if split else wpack.w32
+    _launch("effi_conv2d_k5s2_bf16x3_f32" if split else "effi_conv2d_k5s2_f32", (_p(x), cin, _p(wpack), _p(bias), cout, hin, win, act, _p(out)),
+            n, lambda: (istr, out.stride(0) if n > 1 else 0), key=f"conv2d_k5s2{'x3' if split else ''}_nt{(cout + 15) // 16}{sfx}",
+            work=work, x3=split)
     return out
 
 
@@ -2570,7 +2308,7 @@ def getcost_bwd(gcost, x, disp_range, interval, Dcur, Dreg, dmin, dmax, nq, h, w
 def softargmin_bwd(logits, hyp, gdepth):
     D, h, w = logits.shape
     _t(logits, "logits"), _t(hyp, "hypotheses", contiguous=False), _t(gdepth, "grad")
-    hyp, dds, dps = _depth_strides(hyp, D, h, w)
+    hyp, dds, dps, _ = _depth_strides(hyp, None, D, h, w)
     gl = torch.empty_like(logits)
     check(_lib.lib().effi_softargmin_bwd_f32(_p(logits), _p(hyp), dds, dps, D, h * w, _p(gdepth), _p(gl), _stream()), "effi_softargmin_bwd_f32")
     return gl
