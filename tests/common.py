@@ -86,6 +86,31 @@ def conv_tol(precision, want, rtol, atol, layers=1):
     return dict(rtol=rtol, atol=atol)
 
 
+def _edge_cameras(h, w, N, kind):
+    """Camera rigs that stress the window logic of the stage-1 kernel: `rolled` = source views rotated about the optical
+    axis (slanted epipolar lines, windows taller than wide), `wide` = large baselines (windows that exceed the LDS budget:
+    chunks shrink, then fall back to global loads), `inside` = a source camera inside the depth range (Z <= 0 for part of
+    the volume: those chunks must take the global path), `far` = a view that looks away (every tap out of bounds)."""
+    import math
+    pm = synth.synth_cameras(h * 8, w * 8, N)["stage1"].clone()
+    for v in range(1, N):
+        E = pm[0, v, 0]
+        if kind == "rolled":
+            a = math.radians(25.0 * v)
+            Rz = torch.tensor([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1.0]])
+            E[:3, :3] = Rz @ E[:3, :3]
+            E[:3, 3] = Rz @ E[:3, 3]
+        elif kind == "wide":
+            E[:3, 3] = E[:3, 3] * (4.0 + v)
+        elif kind == "inside":
+            E[2, 3] = E[2, 3] - 600.0 - 40.0 * v          # camera centre moved into the scene
+        elif kind == "far":
+            a = math.radians(100.0)
+            Ry = torch.tensor([[math.cos(a), 0, math.sin(a)], [0, 1.0, 0], [-math.sin(a), 0, math.cos(a)]])
+            E[:3, :3] = Ry @ E[:3, :3]
+    return pm
+
+
 # ---- gradients too large to store in full (tests/golden/make_golden_reference.py, tests/test_oracle_vs_reference.py) ----------
 GRAD_FULL_MAX = 1024          # a gradient with at most this many elements is stored whole
 GRAD_SAMPLE = 512             # elements of a larger one stored at fixed positions
