@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EFFI_MVS_LIB") or os.path.join(_HERE, "libeffimvs_hip.so")   # override: A/B runs of two builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "effi_mvs_hip.h")
 
-_vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
+_vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
 # name -> argtypes (restype is int for all but effi_error_string)
 SIGNATURES = {
@@ -30,6 +30,13 @@ SIGNATURES = {
     "effi_fusion_compact_scan_tile": [],
     "effi_fusion_compact_count_u8": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_compact_scatter_f32": [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
+    # DTU evaluation of a fused cloud (csrc/dtu_eval.hip)
+    "effi_dtu_cell_keys_f32": [_vp, _l, _d, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "effi_dtu_reduce_blocks": [_l],
+    "effi_dtu_reduce_round_f32": [_vp, _vp, _l, _i, _i, _i, _d, _vp, _vp, _vp, _vp],
+    "effi_dtu_nn_capped_f32": [_vp, _l, _vp, _vp, _l, _d, _i, _i, _i, _i, _i, _i, _d, _vp, _vp],
+    "effi_dtu_obs_mask_f32": [_vp, _l, _d, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp],
+    "effi_dtu_above_plane_f32": [_vp, _l, _d, _d, _d, _d, _vp, _vp],
     "effi_fusion_vis_filter_f32": [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp],
     "effi_fusion_points_f32": [_i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_dtu_reproject_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],

@@ -1180,6 +1180,110 @@ def fusion_compact(mask, points, images, layout="hwc", pairs=None):
     return xyz, rgb, offsets
 
 
+# ---- DTU evaluation of a fused cloud (csrc/dtu_eval.hip; the driver is effi_mvs_plus_amd/dtu_eval.py) ----
+def _dtu_points(x, name, cols=3):
+    _t(x, name)
+    if x.dim() != 2 or x.shape[1] != cols or x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: [n,{cols}] fp32 with n < 2^31 expected, got {tuple(x.shape)}")
+    return x
+
+
+def _dtu_buffer(x, name, dtypes, n, like):
+    if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.device != like.device or not x.is_contiguous() or x.numel() != n:
+        raise TypeError(f"{name}: contiguous {' / '.join(str(d) for d in dtypes)} tensor of {n} elements on {like.device} expected")
+    return x
+
+
+def _dtu_grid(i0, dims):
+    i0, dims = [int(v) for v in i0], [int(v) for v in dims]
+    if len(i0) != 3 or len(dims) != 3:
+        raise ValueError("dtu grid: i0 and dims are three integers each")
+    return i0, dims
+
+
+def dtu_cell_keys(xyz, cell, i0, dims):
+    """Cell keys of a point set on the zero-anchored uniform grid (include/effi_mvs_hip.h, "DTU evaluation"): xyz [n,3]; cell index
+    floor(p / cell) - i0 per axis in fp64, key (x * ny + y) * nz + z -> int64 [n].  The neighbour grid of reducePts_haa.m:12,22 and
+    MaxDistCP.m:31-32 (their KD-trees)."""
+    _dtu_points(xyz, "xyz")
+    i0, dims = _dtu_grid(i0, dims)
+    n = xyz.shape[0]
+    keys = torch.empty(n, device=xyz.device, dtype=torch.int64)
+    if n:
+        work = lambda: {"flops": 0.0, "bytes": 20.0 * n}
+        check(_call("dtu_cell_keys", work, _lib.lib().effi_dtu_cell_keys_f32, _p(xyz), n, float(cell), *i0, *dims, _p(keys), _stream()),
+              "effi_dtu_cell_keys_f32")
+    return keys
+
+
+def dtu_reduce_blocks(n):
+    """Length of ``dtu_reduce_round``'s per-workgroup count for n points."""
+    return int(_lib.lib().effi_dtu_reduce_blocks(int(n)))
+
+
+def dtu_reduce_round(pts4, keys, dims, dst, state_in, state_out, block_undecided):
+    """One round of reducePts_haa.m:19-31 as a fixed point.  pts4 [n,4]: the points in key order, column 3 the
+    rank in the visiting order as int32 bits; keys [n] int64 sorted; state_in / state_out [n] uint8 (0 undecided, 1 kept, 2 removed),
+    distinct buffers; block_undecided [dtu_reduce_blocks(n)] int32 receives the undecided points left per workgroup."""
+    _dtu_points(pts4, "pts4", 4)
+    n = pts4.shape[0]
+    _, dims = _dtu_grid((0, 0, 0), dims)
+    _dtu_buffer(keys, "keys", (torch.int64,), n, pts4)
+    _dtu_buffer(state_in, "state_in", (torch.uint8,), n, pts4), _dtu_buffer(state_out, "state_out", (torch.uint8,), n, pts4)
+    _dtu_buffer(block_undecided, "block_undecided", (torch.int32,), dtu_reduce_blocks(n), pts4)
+    if state_in.data_ptr() == state_out.data_ptr():
+        raise ValueError("dtu_reduce_round: state_out must not alias state_in (a round reads the previous round's states only)")
+    if n:
+        work = lambda: {"flops": 0.0, "bytes": 26.0 * n}
+        check(_call("dtu_reduce_round", work, _lib.lib().effi_dtu_reduce_round_f32, _p(pts4), _p(keys), n, *dims, float(dst), _p(state_in),
+                    _p(state_out), _p(block_undecided), _stream()), "effi_dtu_reduce_round_f32")
+
+
+def dtu_nn_capped(src, to4, keys, cell, i0, dims, cap):
+    """MaxDistCP.m:31-33 without its blocks: src [n,3]; to4 [m,4] the target points in key order (column 3 unused) with their sorted
+    keys [m] int64 on the grid (cell, i0, dims) -> fp64 [n] = min(cap^2, min_j d^2(src_i, to_j)); m = 0 gives cap^2."""
+    _dtu_points(src, "src"), _dtu_points(to4, "to4", 4)
+    n, m = src.shape[0], to4.shape[0]
+    _dtu_buffer(keys, "keys", (torch.int64,), m, src)
+    i0, dims = _dtu_grid(i0, dims) if m else ((0, 0, 0), (1, 1, 1))
+    out = torch.empty(n, device=src.device, dtype=torch.float64)
+    if n:
+        work = lambda: {"flops": 0.0, "bytes": 20.0 * n + 24.0 * m}
+        check(_call("dtu_nn_capped", work, _lib.lib().effi_dtu_nn_capped_f32, _p(src), n, _p(to4) if m else _p(None),
+                    _p(keys) if m else _p(None), m, float(cell), *i0, *dims, float(cap), _p(out), _stream()), "effi_dtu_nn_capped_f32")
+    return out
+
+
+def dtu_obs_mask(xyz, obs_mask, bb0, res):
+    """PointCompareMain.m:32-40: xyz [n,3]; obs_mask [X,Y,Z] bool / uint8 on the device; bb0 = BB(1,:) (three floats); res ->
+    bool [n]: every index round((q - bb0) / res + 1) (halves away from zero) lies in 1..size and the mask is set there."""
+    _dtu_points(xyz, "xyz")
+    if not isinstance(obs_mask, torch.Tensor) or obs_mask.dim() != 3:
+        raise TypeError("dtu_obs_mask: obs_mask [X,Y,Z] expected")
+    _dtu_buffer(obs_mask, "obs_mask", (torch.bool, torch.uint8), obs_mask.numel(), xyz)
+    n = xyz.shape[0]
+    out = torch.empty(n, device=xyz.device, dtype=torch.bool)
+    if n:
+        b = [float(v) for v in bb0]
+        work = lambda: {"flops": 0.0, "bytes": 14.0 * n}
+        check(_call("dtu_obs_mask", work, _lib.lib().effi_dtu_obs_mask_f32, _p(xyz), n, b[0], b[1], b[2], float(res), _p(obs_mask),
+                    *[int(s) for s in obs_mask.shape], _p(out), _stream()), "effi_dtu_obs_mask_f32")
+    return out
+
+
+def dtu_above_plane(xyz, plane):
+    """PointCompareMain.m:52: xyz [n,3], plane = P (four floats) -> bool [n] = ((p0 x + p1 y) + p2 z) + p3 > 0 in fp64."""
+    _dtu_points(xyz, "xyz")
+    n = xyz.shape[0]
+    out = torch.empty(n, device=xyz.device, dtype=torch.bool)
+    if n:
+        p = [float(v) for v in plane]
+        work = lambda: {"flops": 0.0, "bytes": 13.0 * n}
+        check(_call("dtu_above_plane", work, _lib.lib().effi_dtu_above_plane_f32, _p(xyz), n, p[0], p[1], p[2], p[3], _p(out), _stream()),
+              "effi_dtu_above_plane_f32")
+    return out
+
+
 def image_prepare(img_u8, dst_h, dst_w, out=None):
     """Scope row n4: decoded image [h,w,3] (or [h,w]) uint8 on the device -> [3,dst_h,dst_w] fp32 = cv2-style bilinear resize of
     img / 255, channel-first (datasets/general_eval.py:83-117,189)."""

@@ -874,6 +874,37 @@ int effi_fusion_compact_scatter_f32(const unsigned char* mask, const float* poin
                                     long pix_stride, long ch_stride, int n_ref, int h, int w, const int* block_base, float* xyz,
                                     unsigned char* rgb, effi_stream_t stream);
 
+/* ---- The DTU evaluation of a fused cloud (evaluations/dtu/BaseEvalMain_web.m:57,69-78 -> PointCompareMain.m -> reducePts_haa.m,
+ * MaxDistCP.m), csrc/dtu_eval.hip.  MATLAB works in double: every decision is made in fp64 on the fp32 coordinates converted to fp64,
+ * and a squared distance is always (dx*dx + dy*dy) + dz*dz, unfused.  Point sets are [n][3] fp32.  The uniform grid of a set is
+ * anchored at zero: cell index floor(p / cell) per axis minus (i0x, i0y, i0z), the smallest index of the set, nx x ny x nz cells
+ * (nx, ny <= 2^21, nz <= 2^20, |i0| <= 2^30), key (x * ny + y) * nz + z.  The CALLER sorts the set by key and passes the sorted
+ * points as [n][4] fp32 rows (x, y, z, w) with the sorted keys; sets hold fewer than 2^31 points.  No atomics anywhere: results are
+ * bitwise reproducible.
+ * effi_dtu_cell_keys_f32: xyz [n][3] -> keys [n] (int64).
+ * effi_dtu_reduce_round_f32: one round of the greedy thinning of reducePts_haa.m:19-31 (a point alive in visiting order removes
+ *   every point within dst, d <= dst inclusive) as a fixed point over a state byte per point (0 undecided, 1 kept, 2 removed) in key
+ *   order: w of pts4 is the point's rank in the visiting order as int32 bits; an undecided point becomes removed if a neighbour of
+ *   smaller rank is kept in state_in, kept if all of them are removed, and stays undecided otherwise.  state_out must not alias
+ *   state_in; block_undecided [effi_dtu_reduce_blocks(n)] receives the undecided points left per workgroup.  The caller repeats the
+ *   call with the buffers swapped until the sum is zero: the kept set is then the sequential loop's, whatever the scheduling.
+ * effi_dtu_nn_capped_f32: MaxDistCP.m:31-33 without its blocks: out_d2 [n_src] (fp64) = min(cap^2, min_j d^2(src_i, to_j)) over the
+ *   gridded set to4 / keys [n_to]; independent of the cell size.  n_to = 0 gives cap^2 (to4 / keys may then be NULL).
+ * effi_dtu_obs_mask_f32: PointCompareMain.m:32-40: Qv = round((q - BB(1,:)) / Res + 1) with halves away from zero; out[i] = 1 iff every
+ *   index is in 1..size and obs_mask[Qv - 1] != 0 (obs_mask [size_x][size_y][size_z] bytes, row-major).
+ * effi_dtu_above_plane_f32: PointCompareMain.m:52: out[i] = ((p0 x + p1 y) + p2 z) + p3 > 0. */
+int effi_dtu_cell_keys_f32(const float* xyz, long n, double cell, int i0x, int i0y, int i0z, int nx, int ny, int nz, long long* keys,
+                           effi_stream_t stream);
+int effi_dtu_reduce_blocks(long n);
+int effi_dtu_reduce_round_f32(const float* pts4, const long long* keys, long n, int nx, int ny, int nz, double dst,
+                              const unsigned char* state_in, unsigned char* state_out, int* block_undecided, effi_stream_t stream);
+int effi_dtu_nn_capped_f32(const float* src, long n_src, const float* to4, const long long* keys, long n_to, double cell, int i0x,
+                           int i0y, int i0z, int nx, int ny, int nz, double cap, double* out_d2, effi_stream_t stream);
+int effi_dtu_obs_mask_f32(const float* xyz, long n, double bb0x, double bb0y, double bb0z, double res, const unsigned char* obs_mask,
+                          int size_x, int size_y, int size_z, unsigned char* out, effi_stream_t stream);
+int effi_dtu_above_plane_f32(const float* xyz, long n, double p0, double p1, double p2, double p3, unsigned char* out,
+                             effi_stream_t stream);
+
 /* ---- tuning / A-B switches.  A table of named integers, initialised ONCE per process from the environment (variable EFFI_<NAME in
  * upper case>) and changed afterwards only through effi_set_option; no entry point reads the environment.  Names: warp_lds_kb
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =
