@@ -17,6 +17,48 @@ def stage1_case(kind, h, w, D, N, C=32):
     return feats, pm, samples
 
 
+def dense_grad(S, D, h, w, seed=0):
+    """Upstream gradient of the similarities, dense Gaussian [S,D,h,w]."""
+    return torch.randn(S, D, h, w, generator=torch.Generator().manual_seed(4000 + 10 * h + D + seed))
+
+
+def seam_lattice(h, w):
+    """Rows / columns on both sides of every 16 x 8 tile seam: set a = the last row / column of every tile (y = 7, 15, ..; x = 15, 31,
+    ..) with the first and last of the map (its four corners), set b = the first of every tile but the first (y = 8, 16, ..; x = 16,
+    32, ..) -> (ya, xa), (yb, xb).  Inside a set no two rows / columns are adjacent."""
+    xa = sorted({0, w - 1} | set(range(15, w, 16)))
+    ya = sorted({0, h - 1} | set(range(7, h, 8)))
+    return (ya, xa), (list(range(8, h, 8)), list(range(16, w, 16)))
+
+
+def sparse_grad(S, D, h, w, seed=0):
+    """Upstream gradient [S,D,h,w] that is non-zero only at hypotheses {0, D - 1}, on a lattice of isolated pixels: plane 0 carries
+    rows a x columns a of `seam_lattice` (the map's corners among them), plane D - 1 rows b x columns b, values of either sign with
+    0.5 <= |g| < 1.5.  A stray add to a wrong pixel, view or (padded) hypothesis lands where the reference pins an exact 0."""
+    g = torch.Generator().manual_seed(4100 + h + D + seed)
+    G = torch.zeros(S, D, h, w)
+    val = 0.5 + torch.rand(S, D, h, w, generator=g)
+    val = val * (1.0 - 2.0 * (torch.rand(S, D, h, w, generator=g) < 0.5).float())
+    for d, (ys, xs) in zip((0, D - 1), seam_lattice(h, w)):
+        iy, ix = torch.meshgrid(torch.tensor(ys), torch.tensor(xs), indexing="ij")
+        G[:, d, iy, ix] = val[:, d, iy, ix]
+    return G
+
+
+def lookup_bwd_case(Dp, nq, h, w, per_pixel, twice, seed=0):
+    """`lookup_case` with an upstream gradient [nq,h,w]; twice: the query map at twice the volume's resolution, [nq,2h+1,2w+1] (odd:
+    the last row / column is never read), the case's queries on its even pixels and another valid depth everywhere else, so that a
+    read of the wrong pixel shows."""
+    vol, q, dmin, dmax = lookup_case(Dp, nq, h, w, per_pixel, seed)
+    g = torch.Generator().manual_seed(4200 + Dp + nq + h + seed)
+    gout = torch.randn(nq, h, w, generator=g)
+    if twice:
+        q2 = 425.0 + 510.0 * torch.rand(nq, 2 * h + 1, 2 * w + 1, generator=g)
+        q2[:, 0:2 * h:2, 0:2 * w:2] = q
+        q = q2.contiguous()
+    return vol, q, dmin, dmax, gout
+
+
 def dyn_cameras(h, w, N, kind):
     """The stage-3 ring of cameras with the intrinsics set for an h x w map (test_warpcorr_dyn_window_form_is_bitwise_the_gather_form),
     and the edge rigs built on it like `_edge_cameras`: `rolled` = sources rotated about the optical axis, `inside` = a source camera

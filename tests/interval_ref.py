@@ -260,6 +260,17 @@ def lookup_position(query, dmin, dmax, Dp):
     return (1.0 / q - 1.0 / hi) / den * (Dp - 1), den
 
 
+def lookup_box(query, dmin, dmax, Dp, n_round=LOOKUP_ROUNDINGS):
+    """-> (t, delta_t): the float64 position of every query and what an fp32 evaluation of it can be off by (the formula derived in
+    lookup_interval; shared with the backward's hat ranges, tests/scatter_ref.py)."""
+    t, den = lookup_position(query, dmin, dmax, Dp)
+    q, lo, hi = query.double(), torch.as_tensor(dmin).double(), torch.as_tensor(dmax).double()
+    dm1 = float(Dp - 1)
+    rel_den = ((1.0 / lo).abs() + (1.0 / hi).abs()) / den
+    dt = K * U * (n_round * dm1 * ((1.0 / q).abs() + (1.0 / hi).abs()) / den + rel_den * t.abs()) + 8.0 * U * (t.abs() + Dp)
+    return t, dt
+
+
 def lookup_interval(vol, query, dmin, dmax, n_round=LOOKUP_ROUNDINGS):
     """Interval of the zero-padded 1-D look-up (pro_bilinear_sampler): vol [Dp,h,w], query [nq,h,w] (fp32 depths, or float64 depths
     rebuilt from the module's formula for getcost), dmin / dmax scalar or [h,w] -> Interval of [nq,h,w].
@@ -275,11 +286,7 @@ def lookup_interval(vol, query, dmin, dmax, n_round=LOOKUP_ROUNDINGS):
     tol = 4u (|v0| + |v1|): the two weights (one subtraction each, exact or 1 rounding), two products, one add."""
     vol = vol.double()
     Dp = vol.shape[0]
-    t, den = lookup_position(query, dmin, dmax, Dp)
-    q, lo, hi = query.double(), torch.as_tensor(dmin).double(), torch.as_tensor(dmax).double()
-    dm1 = float(Dp - 1)
-    rel_den = ((1.0 / lo).abs() + (1.0 / hi).abs()) / den
-    dt = K * U * (n_round * dm1 * ((1.0 / q).abs() + (1.0 / hi).abs()) / den + rel_den * t.abs()) + 8.0 * U * (t.abs() + Dp)
+    t, dt = lookup_box(query, dmin, dmax, Dp, n_round)
     pts = [t - dt, t + dt, torch.minimum(torch.maximum(torch.round(t), t - dt), t + dt)]
     vals = torch.stack([_lerp_padded(vol, p) for p in pts])
     i0 = torch.floor(torch.nan_to_num(t, nan=-2.0).clamp(-2.0, Dp + 1.0)).long()
