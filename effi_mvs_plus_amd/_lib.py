@@ -37,6 +37,11 @@ SIGNATURES = {
     "effi_dtu_nn_capped_f32": [_vp, _l, _vp, _vp, _l, _d, _i, _i, _i, _i, _i, _i, _d, _vp, _vp],
     "effi_dtu_obs_mask_f32": [_vp, _l, _d, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp],
     "effi_dtu_above_plane_f32": [_vp, _l, _d, _d, _d, _d, _vp, _vp],
+    # training loss and depth metrics (csrc/metrics.hip); effi_metrics_scratch_bytes returns long: bound in lib()
+    "effi_metrics_blocks": [_l],
+    "effi_mvs_loss_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "effi_mvs_loss_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "effi_depth_metrics_f32": [_vp, _vp, _vp, _i, _l, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "effi_fusion_vis_filter_f32": [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp],
     "effi_fusion_points_f32": [_i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_dtu_reproject_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
@@ -175,7 +180,8 @@ for _n in BF16X3_ENTRIES:
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 
 # entry points whose return type is not the int status code (bound explicitly in lib())
-NON_STATUS_SYMBOLS = ("effi_error_string", "effi_workspace_bytes", "effi_get_workspace", "effi_get_option", "effi_option_unset")
+NON_STATUS_SYMBOLS = ("effi_error_string", "effi_workspace_bytes", "effi_get_workspace", "effi_get_option", "effi_option_unset",
+                      "effi_metrics_scratch_bytes")
 
 _lock = threading.Lock()
 _lib = None
@@ -213,6 +219,8 @@ def lib():
         handle.effi_get_option.restype = _l
         handle.effi_option_unset.argtypes = []
         handle.effi_option_unset.restype = _l
+        handle.effi_metrics_scratch_bytes.argtypes = [_l, _i, _i]
+        handle.effi_metrics_scratch_bytes.restype = _l
         _lib = handle
     return _lib
 

@@ -629,3 +629,41 @@ def warp_correlate(ref_fea, src_feas, pairs, depth_values, with_entropy=False):
 
 def warp_correlate_dyn(ref_fea, src_feas, view_w, pairs, cur_depth, interval, D):
     return _WarpCorrDyn.apply(ref_fea, view_w, pairs, cur_depth.detach(), interval, D, *src_feas)
+
+
+# =============================================================================================
+# the training loss
+# =============================================================================================
+class _MvsLoss(torch.autograd.Function):
+    """mvs_loss over the K outputs of the cascade (models/module.py:526-552): forward = effi_mvs_loss_f32 (two launches), backward =
+    effi_mvs_loss_bwd_f32 (one launch for the K gradients).  Saved besides the inputs: the K valid-pixel counts only; the backward
+    kernel recomputes d = est - gt.  Returns the [K + 1] vector (l_0 .. l_{K-1}, total); gradients reach the estimates through the
+    total only (the per-output entries are read-outs, as the reference's scalar_outputs are)."""
+
+    @staticmethod
+    def forward(ctx, weights, K, *tensors):
+        ests, gts, masks = [_c(t_) for t_ in tensors[:K]], [_c(t_) for t_ in tensors[K:2 * K]], [_c(t_) for t_ in tensors[2 * K:]]
+        out, count = ops.mvs_loss(ests, gts, masks, weights)
+        ctx.save_for_backward(count, *ests, *gts, *masks)
+        ctx.weights, ctx.K = tuple(weights), K
+        total, per_output = out[K], out[:K]
+        ctx.mark_non_differentiable(per_output)
+        ctx.set_materialize_grads(False)          # no zeros [K] filled for the read-outs' gradient: the backward is ONE launch
+        return total, per_output
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_per_output):
+        K = ctx.K
+        if grad_total is None:
+            return (None,) * (2 + 3 * K)
+        count, *tensors = ctx.saved_tensors
+        ests, gts, masks = tensors[:K], tensors[K:2 * K], tensors[2 * K:]
+        grads = ops.mvs_loss_bwd(ests, gts, masks, ctx.weights, count, _c(grad_total))
+        return (None, None, *grads) + (None,) * (2 * K)
+
+
+def mvs_loss(ests, gts, masks, weights):
+    """ests / gts / masks: K tensors each ([B,H,W]; outputs of one stage pass the same gt / mask), weights: K floats ->
+    (total 0-dim, per_output [K]), both views of one device vector; differentiable w.r.t. the estimates."""
+    K = len(ests)
+    return _MvsLoss.apply(tuple(float(w) for w in weights), K, *ests, *gts, *masks)

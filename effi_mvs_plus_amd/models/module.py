@@ -586,6 +586,26 @@ def mvs_loss_static(inputs, depth_gt_ms, mask_ms, dloss, depth_values=[425, 935]
     return total, per_output
 
 
+@ops.on_tensor_device
+def mvs_loss_fused(inputs, depth_gt_ms, mask_ms, dloss, depth_values=[425, 935], loss_rate=0.9):
+    """``mvs_loss`` on the HIP kernels of csrc/metrics.hip: all outputs in two launches forward (effi_mvs_loss_f32) and one backward
+    (effi_mvs_loss_bwd_f32) instead of ~10 torch launches per output each way; no host sync, no data-dependent shape, so it can
+    be captured (``GraphedTrainStep(loss_fn=mvs_loss_fused)``).  Same signature and return as ``mvs_loss``: the per-output entries
+    and the total are views of one device vector.  Valid pixels are selected (``mask > 0.5`` for a float mask, set bits for a bool
+    one), sums are fp64 in a fixed order: each l_i is the correctly rounded quotient up to one fp32 rounding."""
+    total, per = _mvs_loss_fused_vector(inputs, depth_gt_ms, mask_ms, dloss, loss_rate)
+    return total, {"l{}".format(i): per[i] for i in range(len(inputs))}
+
+
+def _mvs_loss_fused_vector(inputs, depth_gt_ms, mask_ms, dloss, loss_rate=0.9):
+    """``mvs_loss_fused`` with the per-output losses as one [K] device vector: -> (total, per_output)."""
+    from .. import autograd as _ag
+    n = len(inputs)
+    keys = ["stage{}".format(dloss[i]) for i in range(n)]
+    weights = [1.0 if i == 0 else loss_rate ** (n - i - 1) for i in range(n)]
+    return _ag.mvs_loss(list(inputs), [depth_gt_ms[k] for k in keys], [mask_ms[k] for k in keys], weights)
+
+
 def mvs_loss(inputs, depth_gt_ms, mask_ms, dloss, depth_values=[425, 935], loss_rate=0.9):
     """Smooth-L1 over the cascade's outputs with geometric weights (reference: models/module.py:526-552).
     Training-side consumer of the path's outputs; plain tensor algebra."""

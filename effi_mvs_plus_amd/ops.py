@@ -1284,6 +1284,108 @@ def dtu_above_plane(xyz, plane):
     return out
 
 
+# ---- training loss and depth metrics (csrc/metrics.hip; the callers are autograd.mvs_loss and effi_mvs_plus_amd/metrics.py) ----
+LOSS_MAX_OUTPUTS, METRICS_MAX_THRES, METRICS_MAX_BANDS = 16, 8, 8
+
+
+def metrics_blocks(n):
+    """Workgroups (= scratch rows) the loss / metrics kernels use for n elements."""
+    return int(_lib.lib().effi_metrics_blocks(int(n)))
+
+
+def _metrics_scratch(blocks, n_thres, n_bands, device):
+    nbytes = int(_lib.lib().effi_metrics_scratch_bytes(int(blocks), int(n_thres), int(n_bands)))
+    if nbytes <= 0:
+        raise ValueError(f"metrics scratch: {blocks} rows with {n_thres} thresholds / {n_bands} bands is out of range")
+    return torch.empty(nbytes // 8, device=device, dtype=torch.int64)
+
+
+def _mask_form(mask, name, like):
+    """fp32 mask (valid where > 0.5) -> 0, bool / uint8 mask (valid where set) -> 1; same element count and device as ``like``."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise TypeError(f"{name}: fp32, bool or uint8 tensor expected")
+    if mask.device != like.device or not mask.is_contiguous() or mask.numel() != like.numel():
+        raise ValueError(f"{name}: contiguous, {like.numel()} elements on {like.device} expected, got {tuple(mask.shape)} on {mask.device}")
+    return 0 if mask.dtype == torch.float32 else 1
+
+
+def _loss_inputs(ests, gts, masks, weights):
+    K = len(ests)
+    if not (1 <= K <= LOSS_MAX_OUTPUTS) or len(gts) != K or len(masks) != K or len(weights) != K:
+        raise ValueError(f"mvs_loss: 1..{LOSS_MAX_OUTPUTS} outputs with one gt, mask and weight each expected")
+    forms = set()
+    for i in range(K):
+        _t(ests[i], f"est[{i}]"), _t(gts[i], f"gt[{i}]")
+        if gts[i].numel() != ests[i].numel() or ests[i].numel() < 1:
+            raise ValueError(f"mvs_loss: est[{i}] {tuple(ests[i].shape)} and gt[{i}] {tuple(gts[i].shape)} differ in size (or are empty)")
+        forms.add(_mask_form(masks[i], f"mask[{i}]", ests[i]))
+    if len(forms) != 1:
+        raise TypeError("mvs_loss: the masks of one call are all fp32 or all bool / uint8")
+    n = [int(e.numel()) for e in ests]
+    return K, forms.pop(), n, _ptr_array(ests), _ptr_array(gts), _ptr_array(masks), (C.c_long * K)(*n), (C.c_double * K)(*[float(w) for w in weights])
+
+
+def mvs_loss(ests, gts, masks, weights):
+    """mvs_loss forward (models/module.py:526-552) over K <= 16 outputs: two launches.  ests / gts / masks: lists of K tensors of
+    equal size per output (outputs of one stage pass the same gt / mask objects); weights: K floats.  -> (out [K + 1] fp32 with
+    out[:K] the per-output means over the valid pixels and out[K] the weighted total, count [K] int64)."""
+    K, u8, n, pe, pg, pm, pn, pw = _loss_inputs(ests, gts, masks, weights)
+    dev = ests[0].device
+    out = torch.empty(K + 1, device=dev, dtype=torch.float32)
+    count = torch.empty(K, device=dev, dtype=torch.int64)
+    scratch = _metrics_scratch(sum(metrics_blocks(v) for v in n), 0, 0, dev)
+    work = lambda: {"flops": 6.0 * sum(n), "bytes": 12.0 * sum(n)}
+    check(_call("mvs_loss", work, _lib.lib().effi_mvs_loss_f32, pe, pg, pm, pn, K, u8, pw, _p(out), _p(count),
+                C.c_void_p(out.data_ptr() + 4 * K), _p(scratch), _stream()), "effi_mvs_loss_f32")
+    return out, count
+
+
+def mvs_loss_bwd(ests, gts, masks, weights, count, grad_total):
+    """Gradients of ``mvs_loss``'s total w.r.t. the K estimates in one launch: count [K] int64 from the forward, grad_total a 0-dim
+    fp32 DEVICE tensor.  -> list of K tensors shaped like the estimates (exactly 0 at the masked pixels)."""
+    K, u8, n, pe, pg, pm, pn, pw = _loss_inputs(ests, gts, masks, weights)
+    _t(grad_total, "grad_total")
+    if grad_total.numel() != 1:
+        raise ValueError("mvs_loss_bwd: grad_total is one fp32 scalar on the device")
+    _dtu_buffer(count, "count", (torch.int64,), K, ests[0])
+    grads = [torch.empty_like(e) for e in ests]
+    work = lambda: {"flops": 4.0 * sum(n), "bytes": 16.0 * sum(n)}
+    check(_call("mvs_loss_bwd", work, _lib.lib().effi_mvs_loss_bwd_f32, pe, pg, pm, pn, K, u8, pw, _p(count), _p(grad_total),
+                _ptr_array(grads), _stream()), "effi_mvs_loss_bwd_f32")
+    return grads
+
+
+def depth_metrics(est, gt, mask, thresholds=(), bands=(), acc=None):
+    """Thres_metrics / AbsDepthError_metrics (utils.py:139-160) for all thresholds and bands in one pass (two launches): est / gt /
+    mask [B,H,W]; thresholds: up to 8 numbers; bands: up to 8 (lo, hi) pairs, both ends inclusive.  -> (scalars [1 + T + R] fp32 =
+    [abs_mean, thres.., band..] averaged over the per-image values, counts [B, 1 + T + R] int64, sums [B, 1 + R] fp64); acc
+    (optional fp64 [1 + T + R] on the device) += scalars."""
+    _t(est, "est"), _t(gt, "gt")
+    if est.dim() < 2 or gt.shape != est.shape or est.numel() < 1:
+        raise ValueError(f"depth_metrics: est and gt [B,H,W] of one shape expected, got {tuple(est.shape)} / {tuple(gt.shape)}")
+    u8 = _mask_form(mask, "mask", est)
+    B = int(est.shape[0])
+    n = est.numel() // B
+    thr = [float(v) for v in thresholds]
+    lo, hi = [float(b[0]) for b in bands], [float(b[1]) for b in bands]
+    T, R = len(thr), len(lo)
+    if T > METRICS_MAX_THRES or R > METRICS_MAX_BANDS:
+        raise ValueError(f"depth_metrics: at most {METRICS_MAX_THRES} thresholds and {METRICS_MAX_BANDS} bands per call")
+    S = 1 + T + R
+    if acc is not None:
+        _dtu_buffer(acc, "acc", (torch.float64,), S, est)
+    dev = est.device
+    scalars = torch.empty(S, device=dev, dtype=torch.float32)
+    counts = torch.empty((B, S), device=dev, dtype=torch.int64)
+    sums = torch.empty((B, 1 + R), device=dev, dtype=torch.float64)
+    scratch = _metrics_scratch(B * metrics_blocks(n), T, R, dev)
+    fa = lambda v: (C.c_float * max(1, len(v)))(*v)
+    work = lambda: {"flops": (4.0 + T + 3 * R) * B * n, "bytes": 12.0 * B * n}
+    check(_call("depth_metrics", work, _lib.lib().effi_depth_metrics_f32, _p(est), _p(gt), _p(mask), B, n, u8, fa(thr), T, fa(lo), fa(hi), R,
+                _p(counts), _p(sums), _p(scalars), _p(acc), _p(scratch), _stream()), "effi_depth_metrics_f32")
+    return scalars, counts, sums
+
+
 def image_prepare(img_u8, dst_h, dst_w, out=None):
     """Scope row n4: decoded image [h,w,3] (or [h,w]) uint8 on the device -> [3,dst_h,dst_w] fp32 = cv2-style bilinear resize of
     img / 255, channel-first (datasets/general_eval.py:83-117,189)."""

@@ -10,7 +10,8 @@ What makes the step capturable:
   * the depth range (``depth_values[:, 0]``, ``[:, -1]``) enters two kernels by value: it is fixed at capture time
     (``model.static_depth_range``).  DTU training uses one range for every sample (datasets/dtu_yao.py: 425 mm + 192 x 2.5 mm);
   * the loss is ``mvs_loss_static`` (mean over the valid pixels as sum x mask / count: the reference's boolean indexing has a
-    data-dependent shape and synchronises);
+    data-dependent shape and synchronises), or ``mvs_loss_fused``: the same loss as two HIP launches forward and one backward
+    instead of ~250 small torch launches (csrc/metrics.hip; 26.5 -> 25.8 ms per replayed step at 640x512, DESIGN.md 2.4);
   * the optimizer must be constructed with ``capturable=True`` (its step counter lives on the device);
   * the learning rate must be a TENSOR: a Python-float ``lr`` would be baked into the captured kernels' arguments and every replay
     would train at the capture-time rate, whatever a scheduler sets afterwards (the reference steps ``OneCycleLR`` after every
@@ -34,7 +35,9 @@ from typing import Callable, Dict, Sequence
 
 import torch
 
-from .models.module import mvs_loss_static  # noqa: F401  (re-exported: the loss a graphed step uses)
+from . import metrics as _metrics
+from .graph import ReplayGraph
+from .models.module import mvs_loss_fused, _mvs_loss_fused_vector, mvs_loss_static  # noqa: F401  (re-exported: the losses a graphed step uses)
 
 DLOSS = (1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4)            # train.py:246: stage of each of the 13 depth maps
 
@@ -43,12 +46,13 @@ class GraphedTrainStep:
     """``step = GraphedTrainStep(model, optimizer, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms)`` captures the step on
     the given sample (its tensors fix shapes and the depth range); ``loss = step(imgs, proj_matrices, depth_values, depth_gt_ms,
     mask_ms)`` copies a new sample into the captured buffers and replays.  Returns the loss tensor of the captured graph (valid
-    until the next call).  ``warmup`` eager steps run first on a side stream (allocator and lazy initialisation; PyTorch's recipe
+    until the next call; with ``scalars=metrics.TRAIN_SCALARS`` the step's metrics are in ``step.scalars``, a device vector in the
+    order of ``scalars.keys``).  ``warmup`` eager steps run first on a side stream (allocator and lazy initialisation; PyTorch's recipe
     for whole-network capture) -- model and optimizer state are restored afterwards, so the first replay is step 1."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, imgs: torch.Tensor, proj_matrices: Dict[str, torch.Tensor],
                  depth_values: torch.Tensor, depth_gt_ms: Dict[str, torch.Tensor], mask_ms: Dict[str, torch.Tensor],
-                 dloss: Sequence[int] = DLOSS, loss_fn: Callable = mvs_loss_static, warmup: int = 2):
+                 dloss: Sequence[int] = DLOSS, loss_fn: Callable = mvs_loss_static, warmup: int = 2, scalars=None):
         for grp in optimizer.param_groups:
             if not grp.get("capturable", False):
                 raise ValueError("GraphedTrainStep: construct the optimizer with capturable=True")
@@ -60,6 +64,9 @@ class GraphedTrainStep:
         if not model.training:
             raise ValueError("GraphedTrainStep: model.train() first")
         self.model, self.optimizer, self.dloss, self.loss_fn = model, optimizer, tuple(dloss), loss_fn
+        # scalars=metrics.TRAIN_SCALARS: the captured step also computes the metrics train_sample logs (train.py:268-271) on its last
+        # depth map (self.depth_est) against stage4, in one metrics call; self.scalars is their device vector (keys: scalars.keys)
+        self.scalar_set, self.scalars, self.depth_est = scalars, None, None
         clone = lambda t: t.detach().clone()                      # noqa: E731
         self.imgs, self.depth_values = clone(imgs), clone(depth_values)
         self.proj = {k: clone(v) for k, v in proj_matrices.items()}
@@ -125,6 +132,10 @@ class GraphedTrainStep:
         loss, _ = self.loss_fn(out["depth"], self.gt, self.mask, self.dloss)
         loss.backward()
         self.optimizer.step()
+        if self.scalar_set is not None:
+            self.depth_est = out["depth"][-1].detach()
+            self.scalars = _metrics.depth_scalars(out["depth"][-1], self.gt["stage4"], self.mask["stage4"], self.scalar_set.thresholds,
+                                                  self.scalar_set.bands)
         return loss
 
     def load_sample(self, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms):
@@ -163,3 +174,50 @@ class GraphedTrainStep:
         from . import ops
         ops.drop_pack_cache()              # the replay updated the weights on the device without bumping their version counters
         return self.loss
+
+
+class GraphedTestStep:
+    """The body of the reference's ``test_sample_depth`` (train.py:293-353) -- eval-mode forward, ``mvs_loss_fused`` forward and the
+    ``TEST_SCALARS`` metrics of the last depth map against stage4 -- captured once (``graph.ReplayGraph``) and replayed per sample,
+    its scalars added on the device into a ``DeviceAverageMeter`` that carries ``loss``, ``depth_loss``, the metrics and
+    ``l0 .. l{K-1}``.  ``step(imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms)`` copies the sample into the captured buffers
+    and replays: no host synchronisation per sample.  ``step.mean()`` returns the dictionary ``test()`` prints (train.py:226; without
+    its wall-clock ``time``), and is the only sync.  ``step.outputs`` are the captured forward's outputs (valid until the next call);
+    ``step.loss`` / ``step.per_output`` [K] / ``step.scalars`` are the total, l0 .. l{K-1} and the metrics of the last replay.  As in
+    ``GraphedTrainStep`` the eval-mode forward reads the depth range from ``depth_values`` on the device, so any range replays."""
+
+    def __init__(self, model: torch.nn.Module, imgs: torch.Tensor, proj_matrices: Dict[str, torch.Tensor], depth_values: torch.Tensor,
+                 depth_gt_ms: Dict[str, torch.Tensor], mask_ms: Dict[str, torch.Tensor], dloss: Sequence[int] = DLOSS,
+                 loss_rate: float = 0.9):
+        if model.training:
+            raise ValueError("GraphedTestStep: model.eval() first")
+        self.model, self.dloss, self.loss_rate, self.scalar_set = model, tuple(dloss), float(loss_rate), _metrics.TEST_SCALARS
+        K = len(self.dloss)
+        self.loss_keys = ("loss",) + tuple("l{}".format(i) for i in range(K))
+        self.meter = _metrics.DeviceAverageMeter(("depth_loss",) + tuple(self.scalar_set.keys) + self.loss_keys, device=imgs.device)
+        self._graph = ReplayGraph(self._body, (imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms))
+        self.meter.data.zero_()                                   # the warm-up and capture passes added their sample
+        self.outputs, self.loss, self.per_output, self.scalars = self._graph.outputs[0]
+
+    def _body(self, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms):
+        out = self.model(imgs, proj_matrices, depth_values)
+        K = len(self.dloss)
+        if len(out["depth"]) != K:
+            raise ValueError("GraphedTestStep: dloss names {} outputs, the model returns {}".format(K, len(out["depth"])))
+        total, per = _mvs_loss_fused_vector(out["depth"], depth_gt_ms, mask_ms, self.dloss, loss_rate=self.loss_rate)
+        sc = _metrics.depth_scalars(out["depth"][-1], depth_gt_ms["stage4"], mask_ms["stage4"], self.scalar_set.thresholds,
+                                    self.scalar_set.bands, acc=self.meter.slots(self.scalar_set.keys[0], len(self.scalar_set.keys)))
+        self.meter.slots("l0", K).add_(per)                       # fp32 values added into the fp64 sums
+        self.meter.slots("depth_loss", 1).add_(per[K - 1:])       # train.py:319: depth_loss = l{iters}, the last output's
+        self.meter.slots("loss", 1).add_(total.reshape(1))
+        return out, total, per, sc
+
+    def __call__(self, imgs=None, proj_matrices=None, depth_values=None, depth_gt_ms=None, mask_ms=None):
+        if imgs is not None:
+            self._graph.load(0, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms)
+        self._graph.replay(0)
+        self.meter.tick()
+        return self.loss
+
+    def mean(self) -> Dict[str, float]:
+        return self.meter.mean()

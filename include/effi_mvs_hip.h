@@ -905,6 +905,41 @@ int effi_dtu_obs_mask_f32(const float* xyz, long n, double bb0x, double bb0y, do
 int effi_dtu_above_plane_f32(const float* xyz, long n, double p0, double p1, double p2, double p3, unsigned char* out,
                              effi_stream_t stream);
 
+/* ---- The scalar side of train.py: training loss and depth metrics, csrc/metrics.hip.  The reference selects the valid pixels by
+ * boolean indexing (a data-dependent shape, one host sync per call) and reads every scalar back (utils.py tensor2float); these
+ * entries select in registers, keep every scalar on the device and read nothing from the host, so they can be captured.  Masks are
+ * either fp32 (valid where > 0.5: train.py:268 `mask > 0.5`) or bytes / bool storage (valid where != 0), chosen by mask_u8.  An
+ * estimate at a masked pixel is never read into a sum (Inf / NaN there is dropped as the indexing drops it).  Per-pixel arithmetic
+ * is fp32, sums are fp64, counts are integers.  No atomics: a workgroup reduces 2048 elements into one row of 8-byte slots of the
+ * caller's scratch and a finishing launch adds the rows in ascending order -- results are bitwise repeatable.
+ * effi_metrics_blocks(n): workgroups (= scratch rows) of n elements (0: n < 1 or n >= 2^40).
+ * effi_metrics_scratch_bytes(blocks, n_thres, n_bands): bytes of `blocks` rows; the loss uses (sum of effi_metrics_blocks(n[i]), 0, 0),
+ *   the metrics (B * effi_metrics_blocks(n), n_thres, n_bands).  scratch is 8-byte aligned.
+ * effi_mvs_loss_f32: mvs_loss forward (models/module.py:526-552) over K <= 16 outputs in one launch + the finishing launch.  est /
+ *   gt / mask / n / w are HOST arrays of K device pointers, element counts (batch included) and weights (w[0] = 1,
+ *   w[i] = loss_rate^(K-1-i): module.py:548-550); outputs of one stage pass the same gt / mask.  Per valid pixel d = est - gt,
+ *   z = |d|, term = z < 1 ? (0.5f z) z : z - 0.5f (ATen's smooth-L1, beta = 1).  l[i] = fl32(sum_i / count_i) (NaN for an output with no
+ *   valid pixel, as the reference's mean of an empty selection), count[i] (int64), total[0] = fl32(sum_i w[i] l[i]).
+ * effi_mvs_loss_bwd_f32: one launch: grad[i][p] = s_i c(d_p) at the valid pixels with s_i = fl32(grad_total[0] w[i] / count[i]) and
+ *   c(d) = d for |d| <= 1, else sign(d); exactly 0 at the masked ones, whatever est holds there and also when count[i] = 0.
+ *   count is the forward's; grad_total is a DEVICE pointer.
+ * effi_depth_metrics_f32: Thres_metrics / AbsDepthError_metrics (utils.py:139-160) for n_thres <= 8 thresholds and n_bands <= 8
+ *   bands (HOST arrays) in one pass over est / gt / mask [B][n] + the finishing launch.  e = |est - gt|.  Per image: counts
+ *   [B][1 + n_thres + n_bands] (int64) = n_valid, #{e > thres_t}, #{lo_r <= e <= hi_r} (both ends inclusive, utils.py:157); sums
+ *   [B][1 + n_bands] (fp64) = sum e, sum of e per band.  scalars [1 + n_thres + n_bands] (fp32) = [abs_mean, thres.., band..]: each
+ *   per-image value rounded to fp32 (sum_abs / n_valid and n_over / n_valid: NaN without a valid pixel; sum_band / n_band: 0 for an
+ *   empty band, utils.py:158-159), then averaged over the B images (utils.py:126-134).  A NaN error at a valid pixel is in no
+ *   threshold and no band and makes abs_mean NaN.  acc (optional, fp64, same length): acc[k] += scalars[k]. */
+int effi_metrics_blocks(long n);
+long effi_metrics_scratch_bytes(long blocks, int n_thres, int n_bands);
+int effi_mvs_loss_f32(const float* const* est, const float* const* gt, const void* const* mask, const long* n, int K, int mask_u8,
+                      const double* w, float* l, long long* count, float* total, void* scratch, effi_stream_t stream);
+int effi_mvs_loss_bwd_f32(const float* const* est, const float* const* gt, const void* const* mask, const long* n, int K, int mask_u8,
+                          const double* w, const long long* count, const float* grad_total, float* const* grad, effi_stream_t stream);
+int effi_depth_metrics_f32(const float* est, const float* gt, const void* mask, int B, long n, int mask_u8, const float* thres,
+                           int n_thres, const float* band_lo, const float* band_hi, int n_bands, long long* counts, double* sums,
+                           float* scalars, double* acc, void* scratch, effi_stream_t stream);
+
 /* ---- tuning / A-B switches.  A table of named integers, initialised ONCE per process from the environment (variable EFFI_<NAME in
  * upper case>) and changed afterwards only through effi_set_option; no entry point reads the environment.  Names: warp_lds_kb
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =
