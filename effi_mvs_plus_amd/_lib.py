@@ -84,6 +84,9 @@ SIGNATURES = {
     "effi_warpcorr_views_bwd_f32": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "effi_image_prepare_u8_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "effi_resize_linear_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    # training input (csrc/train_input.hip)
+    "effi_images_prepare_batch_u8_f32": [_vp, _i, _i, _i, _vp, _vp],
+    "effi_gt_pyramid_f32": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_encoder_inputs_f32": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp,
                                 _i, _vp, _vp, _vp],
     "effi_encoder_inputs_bf16x3_f32": [_vp, _vp, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp,

@@ -1414,6 +1414,72 @@ def resize_planar(x, dst_h, dst_w, out=None):
     return out
 
 
+# ---- training input (csrc/train_input.hip; the callers are datasets/dtu_yao.py, datasets/blend.py and GraphedTrainStep) ----
+GT_STAGES = ("stage1", "stage2", "stage3", "stage4")
+
+
+def _train_out(out, shape, dev, name):
+    if out is None:
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev \
+            or tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name}: contiguous fp32 {tuple(shape)} on {dev} expected")
+    return out
+
+
+def images_prepare(imgs_u8, out=None):
+    """Decoded training images [V,h,w,3] (or [B,N,h,w,3]) uint8 on the device -> [V,3,h,w] ([B,N,3,h,w]) fp32 = x / 255, channel-first,
+    all views in one launch (datasets/dtu_yao.py:70-74,186; datasets/blend.py:97-101,222; training images are never resized).
+    Bitwise ``np.float32(x) / 255`` and bitwise ``image_prepare`` of every view at its own size."""
+    if not isinstance(imgs_u8, torch.Tensor) or imgs_u8.dtype != torch.uint8 or not imgs_u8.is_contiguous() \
+            or imgs_u8.dim() not in (4, 5) or imgs_u8.shape[-1] != 3 or imgs_u8.numel() < 1:
+        raise TypeError("images_prepare: contiguous uint8 tensor [V,h,w,3] or [B,N,h,w,3] expected")
+    if not imgs_u8.is_cuda:
+        raise _lib.EffiLibraryError("effi_images_prepare_batch_u8_f32 needs a tensor on the GPU (there is no CPU fallback)")
+    lead, (h, w) = tuple(imgs_u8.shape[:-3]), imgs_u8.shape[-3:-1]
+    V = 1
+    for v in lead:
+        V *= int(v)
+    out = _train_out(out, lead + (3, h, w), imgs_u8.device, "images_prepare: out")
+    work = lambda: {"flops": 0.0, "bytes": 15.0 * V * h * w}
+    check(_call("images_prepare", work, _lib.lib().effi_images_prepare_batch_u8_f32, C.c_void_p(imgs_u8.data_ptr()), V, h, w, _p(out),
+                _stream()), "effi_images_prepare_batch_u8_f32")
+    return out
+
+
+def gt_pyramid(depth, mask_u8=None, depth_range=None, thresh=10, out=None):
+    """The ground truth of a sample batch as the loss reads it, one launch: depth [B,h,w] fp32 (h, w multiples of 8) ->
+    (depth_ms, mask_ms), dictionaries stage1 .. stage4 of [B, h >> (4-k), w >> (4-k)] fp32.  stage4 is a copy of ``depth``, the
+    others cv2's INTER_NEAREST (source pixel (f y, f x)).  Exactly one mask source: ``mask_u8`` [B,h,w] uint8 (DTU,
+    datasets/dtu_yao.py:93-106: byte > thresh) or ``depth_range`` [B,2] fp32 on the device (BlendedMVS, datasets/blend.py:215-220:
+    depth_min <= d <= depth_max on each level's own depth).  ``out=(depth_ms, mask_ms)`` writes into given tensors."""
+    _t(depth, "gt_pyramid: depth")
+    if depth.dim() != 3 or depth.numel() < 1:
+        raise ValueError(f"gt_pyramid: depth [B,h,w] expected, got {tuple(depth.shape)}")
+    B, h, w = (int(v) for v in depth.shape)
+    dev = depth.device
+    if mask_u8 is not None:
+        if not isinstance(mask_u8, torch.Tensor) or mask_u8.dtype != torch.uint8 or not mask_u8.is_contiguous() \
+                or mask_u8.device != dev or mask_u8.shape != depth.shape:
+            raise TypeError(f"gt_pyramid: mask_u8 is a contiguous uint8 tensor {tuple(depth.shape)} on {dev}")
+    if depth_range is not None:
+        _t(depth_range, "gt_pyramid: depth_range")
+        if depth_range.device != dev or tuple(depth_range.shape) != (B, 2):
+            raise ValueError(f"gt_pyramid: depth_range [{B},2] (depth_min, depth_max per sample) on {dev} expected")
+    outs = []
+    for i, ms in enumerate(out if out is not None else (None, None)):
+        what = ("depth", "mask")[i]
+        outs.append({k: _train_out(None if ms is None else ms[k], (B, h >> (3 - j), w >> (3 - j)), dev, f"gt_pyramid: out {what}[{k}]")
+                     for j, k in enumerate(GT_STAGES)})
+    depth_ms, mask_ms = outs
+    work = lambda: {"flops": 0.0, "bytes": (4.0 + (1.0 if mask_u8 is not None else 0.0) + 8.0 * 85 / 64) * B * h * w}
+    # the library refuses h % 8, w % 8 and both / neither mask source before it launches anything
+    check(_call("gt_pyramid", work, _lib.lib().effi_gt_pyramid_f32, _p(depth), _p(mask_u8), int(thresh), _p(depth_range), B, h, w,
+                _ptr_array([depth_ms[k] for k in GT_STAGES]), _ptr_array([mask_ms[k] for k in GT_STAGES]), _stream()),
+          "effi_gt_pyramid_f32")
+    return depth_ms, mask_ms
+
+
 def softmax_regress_conf(logits, depth, disp_range=None, conf_up=0):
     """logits [D,h,w]; depth [D] / [D,h,w] -> (depth [h,w], confidence [h,w]) and, with ``disp_range``, also the regressed
     depth as normalised inverse depth (``depth_to_inv`` of it, written by the same kernel).  ``conf_up`` = f > 0: the result

@@ -142,13 +142,7 @@ class GraphedTrainStep:
         """Copy a sample into the captured buffers (asynchronous device copies on the current stream).  The depth range of the
         sample must be the captured one (two kernels hold it by value): a host tensor is checked here and refused; a device tensor
         is checked on the device without a sync -- ``check_ranges()`` reads the count."""
-        lo, hi = depth_values[:, 0], depth_values[:, -1]
-        if not depth_values.is_cuda:
-            if not (bool((lo == self.depth_range[0]).all()) and bool((hi == self.depth_range[1]).all())):
-                raise ValueError(f"GraphedTrainStep: sample depth range ({float(lo[0])}, {float(hi[0])}) differs from the captured "
-                                 f"{self.depth_range}; capture a step per range (datasets/dtu_yao.py uses one)")
-        else:
-            self.range_mismatches += ((lo != self.depth_range[0]) | (hi != self.depth_range[1])).any().to(torch.int64)
+        self._check_range(depth_values)
         self.imgs.copy_(imgs, non_blocking=True)
         self.depth_values.copy_(depth_values, non_blocking=True)
         for k in self.proj:
@@ -156,6 +150,29 @@ class GraphedTrainStep:
         for k in self.gt:
             self.gt[k].copy_(depth_gt_ms[k], non_blocking=True)
             self.mask[k].copy_(mask_ms[k], non_blocking=True)
+
+    def _check_range(self, depth_values):
+        lo, hi = depth_values[:, 0], depth_values[:, -1]
+        if not depth_values.is_cuda:
+            if not (bool((lo == self.depth_range[0]).all()) and bool((hi == self.depth_range[1]).all())):
+                raise ValueError(f"GraphedTrainStep: sample depth range ({float(lo[0])}, {float(hi[0])}) differs from the captured "
+                                 f"{self.depth_range}; capture a step per range (datasets/dtu_yao.py uses one)")
+        else:
+            self.range_mismatches += ((lo != self.depth_range[0]) | (hi != self.depth_range[1])).any().to(torch.int64)
+
+    def load_raw_sample(self, sample):
+        """``load_sample`` for a host-mode sample of the training datasets (``datasets.dtu_yao`` / ``datasets.blend`` with
+        ``device="host"`` or out of DataLoader workers; one sample or a default-collated batch): the decoded bytes go to the device
+        and the two kernels of csrc/train_input.hip write ``imgs`` and the depth / mask pyramid straight into the captured buffers;
+        ``proj_matrices`` and ``depth_values`` are copied.  The depth range is checked as in ``load_sample`` (a BlendedMVS sample
+        with another range is refused the same way).  ``step.load_raw_sample(s); step()`` is the loop body."""
+        from .datasets.train_sample import train_arrays
+        dv = sample["depth_values"]
+        self._check_range(dv if dv.dim() == 2 else dv.unsqueeze(0))
+        train_arrays(sample, self.imgs.device, out=(self.imgs, self.gt, self.mask))
+        self.depth_values.copy_(dv, non_blocking=True)                   # an unbatched sample broadcasts over the batch of one
+        for k in self.proj:
+            self.proj[k].copy_(sample["proj_matrices"][k], non_blocking=True)
 
     def check_ranges(self):
         """Synchronises; raises if any device-resident sample loaded so far had another depth range than the captured one."""

@@ -638,6 +638,26 @@ int effi_image_prepare_u8_f32(const unsigned char* img_hwc, int src_h, int src_w
 int effi_resize_linear_f32(const float* in_chw, int channels, int src_h, int src_w, int dst_h, int dst_w, float* out_chw,
                            effi_stream_t stream);
 
+/* ---- n4, training half: the array part of the training datasets' __getitem__ for a whole sample batch, two launches
+ * (csrc/train_input.hip).
+ * effi_images_prepare_batch_u8_f32: datasets/dtu_yao.py:70-74,186 and datasets/blend.py:97-101,222 (training images are never
+ * resized).  imgs_vhwc [n_views][h][w][3] uint8 -> out_vchw [n_views][3][h][w] fp32 = x / 255 with an IEEE division: bitwise
+ * np.float32(x) / 255 and bitwise n_views calls of effi_image_prepare_u8_f32 at dst == src.  n_views = samples x views, <= 65535. */
+int effi_images_prepare_batch_u8_f32(const unsigned char* imgs_vhwc, int n_views, int h, int w, float* out_vchw,
+                                     effi_stream_t stream);
+/* effi_gt_pyramid_f32: the per-stage ground truth the loss reads (datasets/dtu_yao.py:93-125, datasets/blend.py:208-220).
+ * depth [n_smp][h][w] = the stage-4 depth map; depth_out / mask_out: HOST arrays of 4 device pointers, stage1 .. stage4, stage k
+ * [n_smp][h >> (4-k)][w >> (4-k)] fp32, contiguous, caller-owned; masks hold 0 or 1.  stage4 = depth (a copy); for f = 2, 4, 8
+ * stage(4 - log2 f)[b][y][x] = depth[b][f y][f x], which is cv2.resize(..., INTER_NEAREST) to (w / f, h / f) when h and w are
+ * multiples of 8 (OpenCV: sx = min(floor(x * 1 / (dst / src)), src - 1) in double; the ratio is an exact power of two).  Exactly
+ * one mask source: mask_u8 [n_smp][h][w] (DTU: mask = byte > thresh at the depth's source addresses) or range [n_smp][2] on the
+ * device (BlendedMVS: mask = depth_min <= d && d <= depth_max on each level's own value, in fp32; NaN -> 0).  Both or neither:
+ * EFFI_ERR_BADARG.  h % 8 or w % 8 != 0 (cv2's rounding is not pinned there), n_smp > 65535, depth / outputs not 16-byte or mask_u8
+ * not 8-byte aligned: EFFI_ERR_UNSUPPORTED.  PARITY WITH cv2 ITSELF UNPINNED (cv2 is absent from the build image): checked against
+ * a numpy restatement of the rule above. */
+int effi_gt_pyramid_f32(const float* depth, const unsigned char* mask_u8, int thresh, const float* range, int n_smp, int h, int w,
+                        float* const* depth_out, float* const* mask_out, effi_stream_t stream);
+
 /* ==== scope row n2: what makes the path trainable (train.py:229-263: model.train() -> forward -> loss.backward()) =============
  * The reference gets these from torch autograd through nn.Conv2d / nn.Conv3d / nn.ConvTranspose3d / nn.BatchNorm / F.grid_sample;
  * here every one is an explicit kernel.  Input gradients of the convolutions reuse the forward entries above with re-arranged
