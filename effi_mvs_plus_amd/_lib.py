@@ -161,6 +161,8 @@ SIGNATURES = {
     "effi_bn_apply_f32": [_vp, _i, _i, _l, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "effi_bn_bwd_f32": [_vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "effi_pointwise_f32": [_i, _vp, _vp, _vp, _vp, _f, _f, _l, _l, _i, _vp, _vp, _vp, _vp],
+    "effi_inv_to_depth_ranged_f32": [_vp, _vp, _i, _i, _l, _vp, _vp],
+    "effi_inv_to_depth_ranged_bwd_f32": [_vp, _vp, _vp, _i, _i, _l, _vp, _vp],
     "effi_vol_lookup1d_bwd_f32": [_vp, _l, _l, _i, _vp, _l, _l, _l, _i, _vp, _vp, _l, _i, _i, _vp, _vp],
     "effi_getcost_bwd_f32": [_vp, _vp, _i, _i, _vp, _vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp, _vp],
     "effi_softargmin_bwd_f32": [_vp, _vp, _l, _l, _i, _i, _vp, _vp, _vp],

@@ -389,6 +389,26 @@ def inv_to_depth(inv, lo, hi):
     return _InvToDepth.apply(inv, float(lo), float(hi))
 
 
+class _InvToDepthRanged(torch.autograd.Function):
+    """``_InvToDepth`` with the range of every sample read on the device from ``depth_values`` [B,n_range] (first / last entry): no
+    host value enters the launch, so batches of samples with their own ranges (datasets/blend.py) and captured steps can use it."""
+
+    @staticmethod
+    def forward(ctx, inv, depth_values):
+        inv, depth_values = _c(inv), _c(depth_values.detach())
+        ctx.save_for_backward(inv, depth_values)
+        return ops.inv_to_depth_ranged(inv, depth_values)
+
+    @staticmethod
+    def backward(ctx, g):
+        inv, depth_values = ctx.saved_tensors
+        return ops.inv_to_depth_ranged_bwd(_c(g), inv, depth_values), None
+
+
+def inv_to_depth_ranged(inv, depth_values):
+    return _InvToDepthRanged.apply(inv, depth_values)
+
+
 class _ScaleChannels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, factors):

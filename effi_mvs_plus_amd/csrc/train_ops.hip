@@ -364,6 +364,15 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------
 // element-wise pieces of the GRU block / heads (models/update.py:20-27,40-49,86-99; Effi_MVS_plus.py:138-148)
 // ------------------------------------------------------------------------------------------------
+// gradient of effi_inv_to_depth (common.hpp) w.r.t. inv: d(1/s)/d inv = -(max_disp - min_disp) / s^2 with the forward's s, 0 where
+// the forward clamped (s <= 1e-4).  One body for the by-value case of pointwise_kernel and inv_to_depth_ranged_bwd_kernel.
+__device__ __forceinline__ float inv_to_depth_bwd(float g, float inv, float lo, float hi) {
+    const float max_depth = 1.0f / lo, min_depth = 1.0f / hi;
+    const float min_disp = 1.0f / max_depth, max_disp = 1.0f / min_depth;
+    const float s = min_disp + (max_disp - min_disp) * inv;
+    return (s > 1e-4f) ? -g * (max_disp - min_disp) / (s * s) : 0.0f;
+}
+
 struct PwArgs {
     const float* a; const float* b; const float* c; const float* d;
     float* o0; float* o1; float* o2;
@@ -391,15 +400,61 @@ __global__ __launch_bounds__(TPB) void pointwise_kernel(int op, PwArgs p) {
                 p.o2[i] = g * z;                      // d/dq
             } break;
             case EFFI_PW_INV_TO_DEPTH: p.o0[i] = effi_inv_to_depth(p.a[i], p.s0, p.s1); break;                      // s0 = lo, s1 = hi
-            case EFFI_PW_INV_TO_DEPTH_BWD: {                                                                       // a = g, b = inv
-                const float max_depth = 1.0f / p.s0, min_depth = 1.0f / p.s1;
-                const float min_disp = 1.0f / max_depth, max_disp = 1.0f / min_depth;
-                const float s = min_disp + (max_disp - min_disp) * p.b[i];
-                p.o0[i] = (s > 1e-4f) ? -p.a[i] * (max_disp - min_disp) / (s * s) : 0.0f;
-            } break;
+            case EFFI_PW_INV_TO_DEPTH_BWD: p.o0[i] = inv_to_depth_bwd(p.a[i], p.b[i], p.s0, p.s1); break;           // a = g, b = inv
             case EFFI_PW_SCALE_CH: p.o0[i] = p.a[i] * p.b[(i / p.inner) % p.C]; break;                              // b = per-channel factor
             default: break;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// scale_inv_depth over a batch whose samples each have their own depth range (models/Effi_MVS_plus.py:138-148,423 with the
+// depth_values of datasets/blend.py): map [B][n], the range of sample b = depth_values[b * n_range] and [b * n_range + n_range - 1],
+// read on the device (as effi_stage1_hypotheses_block does), so a captured training step replays any range.  grid (chunks of a map,
+// B): the sample is blockIdx.y -- no division per element, both range loads uniform per workgroup.  Per element the arithmetic is
+// effi_inv_to_depth / inv_to_depth_bwd: the same bits as the by-value cases of pointwise_kernel given the same (lo, hi).
+// 8 B (12 B backward) of traffic per element and nothing else: VEC = 16-byte accesses when n % 4 == 0 and every pointer is 16-byte
+// aligned (then every sample's row is too), else one float per access for the whole map.
+// ------------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void inv_to_depth_ranged_kernel(const float* __restrict__ inv, const float* __restrict__ depth_values,
+                                                                  int n_range, long n, float* __restrict__ out) {
+    const long b = blockIdx.y;
+    const float lo = depth_values[b * n_range], hi = depth_values[b * n_range + n_range - 1];
+    const long base = b * n;
+    if (VEC) {
+        const float4* __restrict__ i4 = reinterpret_cast<const float4*>(inv + base);
+        float4* __restrict__ o4 = reinterpret_cast<float4*>(out + base);
+        for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < (n >> 2); i += (long)gridDim.x * TPB) {
+            const float4 v = i4[i];
+            o4[i] = make_float4(effi_inv_to_depth(v.x, lo, hi), effi_inv_to_depth(v.y, lo, hi), effi_inv_to_depth(v.z, lo, hi),
+                                effi_inv_to_depth(v.w, lo, hi));
+        }
+    } else {
+        for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
+            out[base + i] = effi_inv_to_depth(inv[base + i], lo, hi);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void inv_to_depth_ranged_bwd_kernel(const float* __restrict__ g, const float* __restrict__ inv,
+                                                                      const float* __restrict__ depth_values, int n_range, long n,
+                                                                      float* __restrict__ out) {
+    const long b = blockIdx.y;
+    const float lo = depth_values[b * n_range], hi = depth_values[b * n_range + n_range - 1];
+    const long base = b * n;
+    if (VEC) {
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + base);
+        const float4* __restrict__ i4 = reinterpret_cast<const float4*>(inv + base);
+        float4* __restrict__ o4 = reinterpret_cast<float4*>(out + base);
+        for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < (n >> 2); i += (long)gridDim.x * TPB) {
+            const float4 gv = g4[i], v = i4[i];
+            o4[i] = make_float4(inv_to_depth_bwd(gv.x, v.x, lo, hi), inv_to_depth_bwd(gv.y, v.y, lo, hi),
+                                inv_to_depth_bwd(gv.z, v.z, lo, hi), inv_to_depth_bwd(gv.w, v.w, lo, hi));
+        }
+    } else {
+        for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
+            out[base + i] = inv_to_depth_bwd(g[base + i], inv[base + i], lo, hi);
     }
 }
 
@@ -717,6 +772,43 @@ extern "C" int effi_pointwise_f32(int op, const float* a, const float* b, const 
     if (!a || !o0 || n < 1 || op < 0 || op >= EFFI_PW_COUNT) return EFFI_ERR_BADARG;
     PwArgs p{a, b, c, d, o0, o1, o2, s0, s1, n, inner > 0 ? inner : 1, C > 0 ? C : 1};
     hipLaunchKernelGGL(pointwise_kernel, dim3((unsigned)min((n + TPB - 1) / TPB, 16384L)), dim3(TPB), 0, effi_s(stream), op, p);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+// the ranged conversions' grid: x-chunks of one sample's map (TPB accesses each) by B samples, at most 16384 workgroups in all as
+// effi_pointwise_f32 (the grid-stride loops cover the rest); vec: 16-byte accesses are possible for every sample's row
+static dim3 inv_to_depth_ranged_grid(int B, long n, uintptr_t pointer_bits, bool& vec) {
+    vec = (n % 4 == 0) && (pointer_bits & 15) == 0;
+    const long units = vec ? n / 4 : n;
+    return dim3((unsigned)min((units + TPB - 1) / TPB, max(1L, 16384L / B)), (unsigned)B);
+}
+
+extern "C" int effi_inv_to_depth_ranged_f32(const float* inv, const float* depth_values, int n_range, int B, long n, float* out,
+                                            effi_stream_t stream) {
+    if (!inv || !depth_values || !out || B < 1 || n < 1 || n_range < 2) return EFFI_ERR_BADARG;
+    if (B > 65535) return EFFI_ERR_UNSUPPORTED;
+    bool vec;
+    const dim3 grid = inv_to_depth_ranged_grid(B, n, reinterpret_cast<uintptr_t>(inv) | reinterpret_cast<uintptr_t>(out), vec);
+    if (vec)
+        hipLaunchKernelGGL(inv_to_depth_ranged_kernel<true>, grid, dim3(TPB), 0, effi_s(stream), inv, depth_values, n_range, n, out);
+    else
+        hipLaunchKernelGGL(inv_to_depth_ranged_kernel<false>, grid, dim3(TPB), 0, effi_s(stream), inv, depth_values, n_range, n, out);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_inv_to_depth_ranged_bwd_f32(const float* g, const float* inv, const float* depth_values, int n_range, int B, long n,
+                                                float* out, effi_stream_t stream) {
+    if (!g || !inv || !depth_values || !out || B < 1 || n < 1 || n_range < 2) return EFFI_ERR_BADARG;
+    if (B > 65535) return EFFI_ERR_UNSUPPORTED;
+    bool vec;
+    const dim3 grid = inv_to_depth_ranged_grid(B, n, reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(inv) |
+                                                         reinterpret_cast<uintptr_t>(out), vec);
+    if (vec)
+        hipLaunchKernelGGL(inv_to_depth_ranged_bwd_kernel<true>, grid, dim3(TPB), 0, effi_s(stream), g, inv, depth_values, n_range, n, out);
+    else
+        hipLaunchKernelGGL(inv_to_depth_ranged_bwd_kernel<false>, grid, dim3(TPB), 0, effi_s(stream), g, inv, depth_values, n_range, n, out);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }

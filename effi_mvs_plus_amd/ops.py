@@ -2545,6 +2545,51 @@ def pointwise(op, a, b=None, c=None, d=None, s0=0.0, s1=0.0, inner=1, C=1, n_out
     return outs[0] if n_out == 1 else outs
 
 
+def _ranged_args(what, inv, depth_values, g=None, out=None):
+    for t_, name in ((inv, "inv"), (depth_values, "depth_values"), (g, "grad"), (out, "out")):
+        if t_ is None:
+            continue
+        if not isinstance(t_, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a tensor")
+        if t_.device != inv.device:
+            raise ValueError(f"{what}: {name} lives on {t_.device}, inv on {inv.device}")
+    if inv.dim() < 1 or depth_values.dim() != 2 or depth_values.shape[0] != inv.shape[0] or depth_values.shape[1] < 2:
+        raise ValueError(f"{what}: inv [B,...] and depth_values [B,n_range >= 2] expected, got {tuple(inv.shape)} and "
+                         f"{tuple(depth_values.shape)}")
+    if inv.numel() == 0:
+        raise ValueError(f"{what}: empty map")
+    for t_, name in ((g, "grad"), (out, "out")):
+        if t_ is not None and t_.shape != inv.shape:
+            raise ValueError(f"{what}: {name} {tuple(t_.shape)} must be shaped like inv {tuple(inv.shape)}")
+    _t(inv, "inv"), _t(depth_values, "depth_values")
+    if g is not None:
+        _t(g, "grad")
+    if out is not None:
+        _t(out, "out")
+    B = inv.shape[0]
+    return B, inv.numel() // B, depth_values.shape[1]
+
+
+def inv_to_depth_ranged(inv, depth_values, out=None):
+    """``scale_inv_depth`` with a depth range per sample: inv [B,...] normalised inverse depths, depth_values [B,n_range] (first / last
+    = the ends of sample b's range, read on the device) -> depths shaped like ``inv`` (written to ``out`` when given).  The bits of
+    ``pointwise(PW_INV_TO_DEPTH, inv[b], s0=lo_b, s1=hi_b)`` per sample."""
+    B, n, n_range = _ranged_args("inv_to_depth_ranged", inv, depth_values, out=out)
+    out = torch.empty_like(inv) if out is None else out
+    check(_lib.lib().effi_inv_to_depth_ranged_f32(_p(inv), _p(depth_values), n_range, B, n, _p(out), _stream()),
+          "effi_inv_to_depth_ranged_f32")
+    return out
+
+
+def inv_to_depth_ranged_bwd(g, inv, depth_values, out=None):
+    """Gradient of ``inv_to_depth_ranged`` w.r.t. ``inv`` given ``g`` = the gradient of its output (both shaped like ``inv``)."""
+    B, n, n_range = _ranged_args("inv_to_depth_ranged_bwd", inv, depth_values, g=g, out=out)
+    out = torch.empty_like(inv) if out is None else out
+    check(_lib.lib().effi_inv_to_depth_ranged_bwd_f32(_p(g), _p(inv), _p(depth_values), n_range, B, n, _p(out), _stream()),
+          "effi_inv_to_depth_ranged_bwd_f32")
+    return out
+
+
 def vol_lookup1d_bwd(gout, Dp, query, dmin, dmax, h, w):
     """Gradient of ``vol_lookup1d`` w.r.t. a planar [Dp,h,w] volume: gout [nq,h,w] -> [Dp,h,w]."""
     _t(gout, "grad"), _t(query, "query")

@@ -7,8 +7,16 @@ per-launch host work: the step takes what its kernels take.
 
 What makes the step capturable:
   * every operator of the path launches on torch's current stream through the C ABI and never synchronises (include/effi_mvs_hip.h);
-  * the depth range (``depth_values[:, 0]``, ``[:, -1]``) enters two kernels by value: it is fixed at capture time
-    (``model.static_depth_range``).  DTU training uses one range for every sample (datasets/dtu_yao.py: 425 mm + 192 x 2.5 mm);
+  * the depth range (``depth_values[:, 0]``, ``[:, -1]``): two modes, ``depth_range=``.
+    ``"static"`` (the default): the 12 inverse-depth -> depth conversions of the step and their backward take the range BY VALUE
+    (``EFFI_PW_INV_TO_DEPTH`` / ``_BWD`` of ``effi_pointwise_f32``), so it is fixed at capture time (``model.static_depth_range``
+    while the constructor runs) and every replayed sample must have it.  DTU training uses one range for every sample
+    (datasets/dtu_yao.py: 425 mm + 192 x 2.5 mm).
+    ``"sample"``: the conversions read every sample's range on the device from the captured ``depth_values`` buffer
+    (``effi_inv_to_depth_ranged_f32`` / ``_bwd``: the same arithmetic, bit for bit) -- as every other operator of the step already
+    does -- so any range replays and the samples of a batch may each have their own: BlendedMVS (datasets/blend.py), whose samples
+    carry the range of their reference view (the reference's finetune, train.py --mode finetune, batch_size 4).  Nothing is set on
+    the model; what is checked per sample is only that the range is usable (0 < first < last < inf);
   * the loss is ``mvs_loss_static`` (mean over the valid pixels as sum x mask / count: the reference's boolean indexing has a
     data-dependent shape and synchronises), or ``mvs_loss_fused``: the same loss as two HIP launches forward and one backward
     instead of ~250 small torch launches (csrc/metrics.hip; 26.5 -> 25.8 ms per replayed step at 640x512, DESIGN.md 2.4);
@@ -52,7 +60,11 @@ class GraphedTrainStep:
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, imgs: torch.Tensor, proj_matrices: Dict[str, torch.Tensor],
                  depth_values: torch.Tensor, depth_gt_ms: Dict[str, torch.Tensor], mask_ms: Dict[str, torch.Tensor],
-                 dloss: Sequence[int] = DLOSS, loss_fn: Callable = mvs_loss_static, warmup: int = 2, scalars=None):
+                 dloss: Sequence[int] = DLOSS, loss_fn: Callable = mvs_loss_static, warmup: int = 2, scalars=None,
+                 depth_range: str = "static"):
+        if depth_range not in ("static", "sample"):
+            raise ValueError(f"GraphedTrainStep: depth_range must be 'static' or 'sample', got {depth_range!r}")
+        self.range_mode = depth_range
         for grp in optimizer.param_groups:
             if not grp.get("capturable", False):
                 raise ValueError("GraphedTrainStep: construct the optimizer with capturable=True")
@@ -72,13 +84,21 @@ class GraphedTrainStep:
         self.proj = {k: clone(v) for k, v in proj_matrices.items()}
         self.gt = {k: clone(v) for k, v in depth_gt_ms.items()}
         self.mask = {k: clone(v) for k, v in mask_ms.items()}
+        self._betas = [tuple(grp.get("betas", ())) for grp in optimizer.param_groups]
+        # samples on the device whose range differs from the captured one ("static") or is unusable ("sample") are counted here (no
+        # host sync per step): check_ranges()
+        self.range_mismatches = torch.zeros((), dtype=torch.int64, device=imgs.device)
+        if depth_range == "sample":
+            # the step reads each sample's range from self.depth_values: nothing is captured by value, nothing is set on the model
+            self.depth_range = None
+            if not bool(self._usable(depth_values).all()):
+                raise ValueError("GraphedTrainStep: unusable depth range in the capture batch (0 < first < last < inf expected)")
+            self._build(model, optimizer, imgs, warmup)
+            return
         lo, hi = depth_values[:, 0], depth_values[:, -1]
         if not (bool((lo == lo[0]).all()) and bool((hi == hi[0]).all())):
             raise NotImplementedError("GraphedTrainStep: the samples of a batch must share their depth range")
         self.depth_range = (float(lo[0]), float(hi[0]))
-        self._betas = [tuple(grp.get("betas", ())) for grp in optimizer.param_groups]
-        # samples on the device whose range differs from the captured one are counted here (no host sync per step): check_ranges()
-        self.range_mismatches = torch.zeros((), dtype=torch.int64, device=imgs.device)
         # the range is a constant of the CAPTURED step only: the attribute lives on the model while this constructor runs its eager
         # and captured steps and is removed again, so later eager train-mode forwards of the model read their own sample's range
         model.static_depth_range = self.depth_range
@@ -139,9 +159,10 @@ class GraphedTrainStep:
         return loss
 
     def load_sample(self, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms):
-        """Copy a sample into the captured buffers (asynchronous device copies on the current stream).  The depth range of the
-        sample must be the captured one (two kernels hold it by value): a host tensor is checked here and refused; a device tensor
-        is checked on the device without a sync -- ``check_ranges()`` reads the count."""
+        """Copy a sample into the captured buffers (asynchronous device copies on the current stream).  ``"static"`` mode: the depth
+        range of the sample must be the captured one (two kernels hold it by value); ``"sample"`` mode: it must be usable (0 < first
+        < last < inf).  A host tensor is checked here and refused before anything is written; a device tensor is checked on the device
+        without a sync -- ``check_ranges()`` reads the count."""
         self._check_range(depth_values)
         self.imgs.copy_(imgs, non_blocking=True)
         self.depth_values.copy_(depth_values, non_blocking=True)
@@ -151,8 +172,24 @@ class GraphedTrainStep:
             self.gt[k].copy_(depth_gt_ms[k], non_blocking=True)
             self.mask[k].copy_(mask_ms[k], non_blocking=True)
 
+    @staticmethod
+    def _usable(depth_values):
+        """Per sample: 0 < first < last < inf (NaN fails every comparison)."""
+        lo, hi = depth_values[:, 0], depth_values[:, -1]
+        return (lo > 0) & (lo < hi) & (hi < float("inf"))
+
     def _check_range(self, depth_values):
         lo, hi = depth_values[:, 0], depth_values[:, -1]
+        if self.range_mode == "sample":
+            ok = self._usable(depth_values)
+            if not depth_values.is_cuda:
+                if not bool(ok.all()):
+                    b = int((~ok).nonzero()[0])
+                    raise ValueError(f"GraphedTrainStep: unusable depth range ({float(lo[b])}, {float(hi[b])}) in sample {b} of the "
+                                     "batch: 0 < first < last < inf expected")
+            else:
+                self.range_mismatches += (~ok).any().to(torch.int64)
+            return
         if not depth_values.is_cuda:
             if not (bool((lo == self.depth_range[0]).all()) and bool((hi == self.depth_range[1]).all())):
                 raise ValueError(f"GraphedTrainStep: sample depth range ({float(lo[0])}, {float(hi[0])}) differs from the captured "
@@ -164,8 +201,9 @@ class GraphedTrainStep:
         """``load_sample`` for a host-mode sample of the training datasets (``datasets.dtu_yao`` / ``datasets.blend`` with
         ``device="host"`` or out of DataLoader workers; one sample or a default-collated batch): the decoded bytes go to the device
         and the two kernels of csrc/train_input.hip write ``imgs`` and the depth / mask pyramid straight into the captured buffers;
-        ``proj_matrices`` and ``depth_values`` are copied.  The depth range is checked as in ``load_sample`` (a BlendedMVS sample
-        with another range is refused the same way).  ``step.load_raw_sample(s); step()`` is the loop body."""
+        ``proj_matrices`` and ``depth_values`` are copied.  The depth range is checked as in ``load_sample`` (in ``"static"`` mode a
+        BlendedMVS sample with another range is refused the same way; ``"sample"`` mode takes it).  ``step.load_raw_sample(s);
+        step()`` is the loop body (``train_epoch``)."""
         from .datasets.train_sample import train_arrays
         dv = sample["depth_values"]
         self._check_range(dv if dv.dim() == 2 else dv.unsqueeze(0))
@@ -175,8 +213,11 @@ class GraphedTrainStep:
             self.proj[k].copy_(sample["proj_matrices"][k], non_blocking=True)
 
     def check_ranges(self):
-        """Synchronises; raises if any device-resident sample loaded so far had another depth range than the captured one."""
+        """Synchronises; raises if any device-resident sample loaded so far had another depth range than the captured one
+        (``"sample"`` mode: an unusable one)."""
         n = int(self.range_mismatches.item())
+        if n and self.range_mode == "sample":
+            raise ValueError(f"GraphedTrainStep: {n} loaded batch(es) had an unusable depth range (0 < first < last < inf expected)")
         if n:
             raise ValueError(f"GraphedTrainStep: {n} replayed sample(s) had a depth range other than the captured {self.depth_range}")
 
@@ -191,6 +232,22 @@ class GraphedTrainStep:
         from . import ops
         ops.drop_pack_cache()              # the replay updated the weights on the device without bumping their version counters
         return self.loss
+
+
+def train_epoch(step, loader, scheduler=None):
+    """One epoch of the reference's loop (train.py:115-127) on a captured step: for every batch of a host-mode dataset
+    ``step.load_raw_sample(batch)``, ``step()``, ``scheduler.step()``; the losses are added on the device (no host sync per step).
+    Ends with ``step.check_ranges()`` (the one sync) and returns (mean loss, number of steps)."""
+    total, steps = None, 0
+    for batch in loader:
+        step.load_raw_sample(batch)
+        loss = step()
+        if scheduler is not None:
+            scheduler.step()
+        total = loss.detach().clone() if total is None else total.add_(loss.detach())
+        steps += 1
+    step.check_ranges()
+    return (float(total) / steps if steps else float("nan")), steps
 
 
 class GraphedTestStep:

@@ -174,14 +174,15 @@ def hot_path(model, features, cnet_depth, proj_matrices, depth_values):
     """Training-mode ``forward_hot``: same interface and outputs."""
     B, n_range = depth_values.shape
     lo, hi = depth_values[:, 0], depth_values[:, -1]
-    if B > 1 and getattr(model, "static_depth_range", None) is None and (not torch.equal(lo, lo[:1].expand_as(lo))
-                                                                         or not torch.equal(hi, hi[:1].expand_as(hi))):
-        raise NotImplementedError("training path: the samples of a batch must share their depth range (DTU training does)")
+    # the 12 inverse-depth -> depth conversions: every sample's range read on the device from depth_values (any mix of ranges, no host
+    # sync), unless a step captured in GraphedTrainStep's "static" mode holds one range for all samples as a constant
     static_range = getattr(model, "static_depth_range", None)
-    if static_range is not None:        # graph capture (train_graph.GraphedTrainStep): the range is a constant of the captured step
+    if static_range is not None:
         lo_f, hi_f = static_range
+        to_depth = lambda inv: A.inv_to_depth(inv, lo_f, hi_f)                     # noqa: E731
     else:
-        lo_f, hi_f = float(lo[0]), float(hi[0])
+        depth_values = depth_values.contiguous()
+        to_depth = lambda inv: A.inv_to_depth_ranged(inv, depth_values)            # noqa: E731
     d_nums = model.depth_stage_nums
     base_itv = (hi - lo) / n_range                                                  # :424
     hyp1, _ = zip(*[ops.stage1_hypotheses(depth_values[b].contiguous(), d_nums[0]) for b in range(B)])
@@ -233,8 +234,8 @@ def hot_path(model, features, cnet_depth, proj_matrices, depth_values):
 
         _, masks, invs = update_block(model.update_block[s], hidden[s], cost_fn, inv_cur, inp[s], model.seq_len[s])
         for inv_i in invs:
-            preds.append(A.inv_to_depth(inv_i, lo_f, hi_f).squeeze(1))
+            preds.append(to_depth(inv_i).squeeze(1))
         up = A.convex_upsample(invs[-1], masks[-1]).unsqueeze(1)
-        preds.append(A.inv_to_depth(up, lo_f, hi_f).squeeze(1))
+        preds.append(to_depth(up).squeeze(1))
         dmin_prev, dmax_prev = dmin_cur, dmax_cur
     return {"depth": preds, "photometric_confidence": conf}

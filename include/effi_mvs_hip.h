@@ -735,6 +735,16 @@ int effi_bn_bwd_f32(const float* gy, const float* y, const float* x, int B, int 
 #define EFFI_PW_COUNT            13
 int effi_pointwise_f32(int op, const float* a, const float* b, const float* c, const float* d, float s0, float s1, long n, long inner,
                        int C, float* o0, float* o1, float* o2, effi_stream_t stream);
+/* scale_inv_depth for a batch whose samples each have their own depth range (models/Effi_MVS_plus.py:138-148,423 under train.py's
+ * finetune on BlendedMVS, batch_size 4): inv / out [B][n]; the range of sample b is read ON THE DEVICE from
+ * depth_values[b * n_range] and depth_values[b * n_range + n_range - 1] (depth_values [B][n_range], n_range >= 2), so a captured
+ * training step replays any range.  Per element the arithmetic of EFFI_PW_INV_TO_DEPTH / _BWD: the same bits given the same (lo, hi).
+ * _bwd: out = gradient w.r.t. inv given g = gradient of the depth (0 where the forward clamped).  16-byte accesses when n % 4 == 0 and
+ * inv, g, out are 16-byte aligned, else element-wise.  B <= 65535.  Runs on the caller's stream; never synchronises. */
+int effi_inv_to_depth_ranged_f32(const float* inv, const float* depth_values, int n_range, int B, long n, float* out,
+                                 effi_stream_t stream);
+int effi_inv_to_depth_ranged_bwd_f32(const float* g, const float* inv, const float* depth_values, int n_range, int B, long n, float* out,
+                                     effi_stream_t stream);
 
 /* Backward of effi_vol_lookup1d_f32 w.r.t. the looked-up volume (pro_bilinear_sampler, models/Effi_MVS_plus.py:102-134; the query
  * coordinates come from detached depths): gvol (layout as the forward's vol) is ACCUMULATED without atomics (a thread owns a pixel). */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One training step (forward in train mode -> mvs_loss -> backward -> AdamW step, train.py:229-263) at a DTU training shape:
 the HIP training path of this package against torch autograd through the oracle's op sequence with stock PyTorch-ROCm operators
-(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B]"""
+(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B]
+Environment: BENCH_TRAIN_NO_GRAPH, BENCH_TRAIN_HIP_ONLY, BENCH_TRAIN_DEPTH_RANGE=static|sample (the graphed step's mode)."""
 import os
 import sys
 import time
@@ -65,9 +66,12 @@ def main():
         # the same step (static loss, capturable AdamW) captured into one HIP graph and replayed: no per-launch host work
         from effi_mvs_plus_amd import train_graph
         opt_g = torch.optim.AdamW(net.parameters(), lr=1e-5, capturable=True)
-        step = train_graph.GraphedTrainStep(net, opt_g, imgs, pm, dv, gt, mask)
+        # BENCH_TRAIN_DEPTH_RANGE=sample: the step that reads every sample's depth range on the device (profiles/train_range_ab.txt)
+        mode = os.environ.get("BENCH_TRAIN_DEPTH_RANGE", "static")
+        step = train_graph.GraphedTrainStep(net, opt_g, imgs, pm, dv, gt, mask, depth_range=mode)
         graph_ms = timed(lambda: step(), 10)
-        print(f"HIP training step, graph replay (train_graph.GraphedTrainStep): {graph_ms:.1f} ms  ({B * 1e3 / graph_ms:.1f} samples/s)")
+        print(f"HIP training step, graph replay (train_graph.GraphedTrainStep, depth_range={mode!r}): {graph_ms:.2f} ms  "
+              f"({B * 1e3 / graph_ms:.1f} samples/s)")
         del step
 
     if os.environ.get("BENCH_TRAIN_HIP_ONLY"):
