@@ -20,6 +20,7 @@ SIGNATURES = {
     "effi_version": [],
     "effi_set_workspace": [_i, _vp, _l],
     "effi_set_option": [C.c_char_p, _l],
+    "effi_launch_form": [_i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "effi_fusion_dynamic_filter_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp],
     "effi_fusion_dtu_filter_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

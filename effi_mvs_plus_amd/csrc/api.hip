@@ -1,5 +1,6 @@
 // Library-level entry points of the C ABI (version, error strings, workspace registry, tuning options).
 #include "common.hpp"
+#include "launch_form.hpp"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -84,6 +85,32 @@ extern "C" long effi_get_option(const char* name) {
 }
 
 extern "C" long effi_option_unset(void) { return EFFI_OPT_UNSET; }
+
+// ---- host-only query of the launch rules (launch_form.hpp): what the launcher would pick for these sizes under the current options.
+// Launches nothing and makes no GPU call.
+extern "C" int effi_launch_form(int launcher, int nt, int h, int w, int planes, int count, int cout, int flags, int* form) {
+    if (!form || nt < 1 || h < 1 || w < 1 || planes < 1 || count < 1 || cout < 1) return EFFI_ERR_BADARG;
+    const bool sr = flags & EFFI_LF_FLAG_SR, zb = flags & EFFI_LF_FLAG_ZB, k1 = flags & EFFI_LF_FLAG_K1, s2 = flags & EFFI_LF_FLAG_S2;
+    const EffiFormOpts o = effi_form_opts();
+    EffiForm f;
+    switch (launcher) {
+        case EFFI_LF_X3: f = effi_pick_x3(nt, h, w, zb ? planes : 1, zb, sr, o); break;
+        case EFFI_LF_X3_BATCH: f = effi_pick_x3_batch(nt, h, w, count, o); break;
+        case EFFI_LF_X3_ZB_BATCH: f = effi_pick_x3_zb_batch(nt, h, w, (long)planes * count, o); break;
+        case EFFI_LF_X3_PAIR: f = effi_pick_x3_pair(nt, h, w, sr, o); break;
+        case EFFI_LF_CONV2D: f = effi_pick_generic(k1 ? 1 : 3, h, w, count); break;
+        case EFFI_LF_PLANES3D: f = effi_pick_planes(h, w, (long)planes * count, s2 ? 2 : 4); break;
+        case EFFI_LF_K5S2: f = effi_pick_planes(h, w, count, 2); break;
+        case EFFI_LF_S2_X3: f = effi_pick_s2_x3(h, w, nt == 1 ? 1 : (nt + 1) / 2, (long)planes * count); break;
+        case EFFI_LF_ROLL: f = effi_pick_roll((flags & EFFI_LF_FLAG_OCT2) ? 2 : 1, nt, cout, h, w, planes, count, o); break;
+        case EFFI_LF_DECONV_X3: f = effi_pick_deconv_x3(cout, h, w, planes, count, o); break;
+        case EFFI_LF_C3_PLANES: f = effi_pick_c3_planes(h, w, planes, count); break;
+        case EFFI_LF_DECONV_K3: f = effi_pick_deconv_k3(cout, h, w, planes, count); break;
+        default: return EFFI_ERR_BADARG;
+    }
+    form[0] = f.rows, form[1] = f.cols, form[2] = f.waves, form[3] = f.planes, form[4] = f.variant;
+    return EFFI_OK;
+}
 
 // ---- diagnostics: fill the LDS of every CU with a pattern (tools/stress_c8_corun.py: what a kernel reads from LDS without having written
 // it is whatever the previous workgroup on that CU left there; after this launch that is `pattern`) ----

@@ -1741,14 +1741,8 @@ int launch2d_v2(const Conv2dArgs& a, hipStream_t st) {
 
 template <int KS, int NT, int EPI>
 int launch2d(const Conv2dArgs& a, hipStream_t st) {
-    if ((a.w & 3) == 0) {
-        // rows per wave: the largest of {4, 2, 1} that still yields >= 2 workgroups per CU (256 CUs)
-        const long cols = effi_cdiv(a.w, 16);
-        int mr;
-        if (cols * effi_cdiv(a.h, 16) >= 512 || (KS == 1 && cols * effi_cdiv(a.h, 16) >= 256)) mr = 4;
-        else if (cols * effi_cdiv(a.h, 8) >= 512 || KS == 1) mr = 2;
-        else mr = 1;
-        if (KS == 1 && mr == 1) mr = 2;
+    const int mr = effi_pick_generic(KS, a.h, a.w, 1).rows;          // (launch_form.hpp; 0: rows of w % 4 != 0)
+    if (mr != 0) {
         if (mr == 4) return launch2d_v2<KS, NT, 4, EPI>(a, st);
         if (mr == 2) return launch2d_v2<KS, NT, 2, EPI>(a, st);
         return launch2d_v2<KS, NT, (KS == 3 ? 1 : 2), EPI>(a, st);
@@ -1770,13 +1764,8 @@ int launch2d_v2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
 
 template <int KS, int NT, int EPI>
 int launch2d_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    if ((a.w & 3) == 0) {
-        const long cols = effi_cdiv(a.w, 16);
-        const long t4 = cols * effi_cdiv(a.h, 16) * b.n_img, t2 = cols * effi_cdiv(a.h, 8) * b.n_img;
-        int mr;
-        if (t4 >= 512 || (KS == 1 && t4 >= 256)) mr = 4;
-        else if (t2 >= 512 || KS == 1) mr = 2;
-        else mr = 1;
+    const int mr = effi_pick_generic(KS, a.h, a.w, b.n_img).rows;
+    if (mr != 0) {
         if (mr == 4) return launch2d_v2_batch<KS, NT, 4, EPI>(a, b, st);
         if (mr == 2) return launch2d_v2_batch<KS, NT, 2, EPI>(a, b, st);
         return launch2d_v2_batch<KS, NT, (KS == 3 ? 1 : 2), EPI>(a, b, st);
@@ -1846,11 +1835,11 @@ static int launch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch*
 // (batched: the rule on the workgroups of all samples; a pixel's accumulation order does not depend on the rows per wave)
 template <int NT>
 static int dispatch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * (bt ? bt->n_img : 1);
+    const long planes = (long)a.zcount * (bt ? bt->n_img : 1);
     const bool al = (a.w & 3) == 0;
-    // rows per wave: keep >= 2 workgroups per CU over all planes
-    if (cols * effi_cdiv(a.h, 16) * planes >= 512) return al ? launch3d_planes<NT, 4, true>(a, st, bt) : launch3d_planes<NT, 4, false>(a, st, bt);
-    if (cols * effi_cdiv(a.h, 8) * planes >= 512) return al ? launch3d_planes<NT, 2, true>(a, st, bt) : launch3d_planes<NT, 2, false>(a, st, bt);
+    const int mr = effi_pick_planes(a.h, a.w, planes, 4).rows;       // (launch_form.hpp)
+    if (mr == 4) return al ? launch3d_planes<NT, 4, true>(a, st, bt) : launch3d_planes<NT, 4, false>(a, st, bt);
+    if (mr == 2) return al ? launch3d_planes<NT, 2, true>(a, st, bt) : launch3d_planes<NT, 2, false>(a, st, bt);
     return al ? launch3d_planes<NT, 1, true>(a, st, bt) : launch3d_planes<NT, 1, false>(a, st, bt);
 }
 
@@ -1922,9 +1911,9 @@ static int launch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBat
 
 template <int NT>
 static int dispatch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * (bt ? bt->n_img : 1);
+    const long planes = (long)a.zcount * (bt ? bt->n_img : 1);
     const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (cols * effi_cdiv(a.h, 8) * planes >= 512) return al ? launch3d_planes_s2<NT, 2, true>(a, st, bt) : launch3d_planes_s2<NT, 2, false>(a, st, bt);
+    if (effi_pick_planes(a.h, a.w, planes, 2).rows == 2) return al ? launch3d_planes_s2<NT, 2, true>(a, st, bt) : launch3d_planes_s2<NT, 2, false>(a, st, bt);
     return al ? launch3d_planes_s2<NT, 1, true>(a, st, bt) : launch3d_planes_s2<NT, 1, false>(a, st, bt);
 }
 
@@ -2117,9 +2106,8 @@ static int launch_k5s2(const Conv2dArgs& a, hipStream_t st) {
 
 template <int NT>
 static int dispatch_k5s2(const Conv2dArgs& a, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
     const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (cols * effi_cdiv(a.h, 8) >= 512) return al ? launch_k5s2<NT, 2, true>(a, st) : launch_k5s2<NT, 2, false>(a, st);
+    if (effi_pick_planes(a.h, a.w, 1, 2).rows == 2) return al ? launch_k5s2<NT, 2, true>(a, st) : launch_k5s2<NT, 2, false>(a, st);
     return al ? launch_k5s2<NT, 1, true>(a, st) : launch_k5s2<NT, 1, false>(a, st);
 }
 
@@ -2134,9 +2122,8 @@ static int launch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_
 
 template <int NT>
 static int dispatch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
     const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (cols * effi_cdiv(a.h, 8) * b.n_img >= 512) return al ? launch_k5s2_batch<NT, 2, true>(a, b, st) : launch_k5s2_batch<NT, 2, false>(a, b, st);
+    if (effi_pick_planes(a.h, a.w, b.n_img, 2).rows == 2) return al ? launch_k5s2_batch<NT, 2, true>(a, b, st) : launch_k5s2_batch<NT, 2, false>(a, b, st);
     return al ? launch_k5s2_batch<NT, 1, true>(a, b, st) : launch_k5s2_batch<NT, 1, false>(a, b, st);
 }
 
@@ -2377,7 +2364,7 @@ static int launch_s2_x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, int ng
     const int cols = effi_cdiv(a.w, 16);
     const long planes = (long)a.zcount * b.n_img;
     if (planes > 65535) return EFFI_ERR_UNSUPPORTED;
-    if ((long)cols * effi_cdiv(a.h, 8) * ngroups * planes >= 400) {
+    if (effi_pick_s2_x3(a.h, a.w, ngroups, planes).rows == 2) {
         const int ntiles = cols * effi_cdiv(a.h, 8);
         hipLaunchKernelGGL((conv3d_s2_bf16x3_batch_kernel<NT, 2>), dim3(ntiles, ngroups, (unsigned)planes), dim3(256), 0, st, a, b, cols, ntiles);
     } else {
@@ -2391,7 +2378,7 @@ template <int KS, int NT, bool ZB>
 static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st) {
     const int cols = effi_cdiv(a.w, 16);
     const unsigned planes = ZB ? (unsigned)a.zcount : 1u;
-    if ((long)cols * effi_cdiv(a.h, 8) * ngroups * planes >= 400) {
+    if (effi_pick_s2_x3(a.h, a.w, ngroups, planes).rows == 2) {
         const int ntiles = cols * effi_cdiv(a.h, 8);
         hipLaunchKernelGGL((conv2d_s2_bf16x3_kernel<KS, NT, 2, ZB>), dim3(ntiles, ngroups, planes), dim3(256), 0, st, a, cols, ntiles);
     } else {
@@ -2406,7 +2393,7 @@ static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st) {
 template <int KS, int NT>
 static int launch_s2_x3_batch(const Conv2dArgs& a, const ConvBatch& b, int ngroups, hipStream_t st) {
     const int cols = effi_cdiv(a.w, 16);
-    if ((long)cols * effi_cdiv(a.h, 8) * ngroups * b.n_img >= 400) {
+    if (effi_pick_s2_x3(a.h, a.w, ngroups, b.n_img).rows == 2) {
         const int ntiles = cols * effi_cdiv(a.h, 8);
         hipLaunchKernelGGL((conv2d_s2_bf16x3_batch_kernel<KS, NT, 2>), dim3(ntiles, ngroups, b.n_img), dim3(256), 0, st, a, b, cols, ntiles);
     } else {
@@ -3107,29 +3094,11 @@ extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32_batch)(const float* const* sr
 
 template <int NOCT, int NT>
 static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pair = nullptr, const ConvBatch* bt = nullptr) {
-    // Rows per wave (MR) and planes per workgroup (ZT) from a small cost model fitted to sweeps at the cfg3 shapes
-    // (tools/sweep_roll.sh): the chip holds 256 * occ workgroups at a time (occ from the LDS image / register count of the
-    // instantiation), a launch takes ceil(workgroups / that) rounds, and a workgroup costs (ZT + 3) plane steps (3 ~ filling
-    // the window), 1.3x as much with 4 rows per wave as with 2.  E.g. 8->8 at 48x148x200: MR 4 / ZT 6 (1040 workgroups, 3
-    // rounds) 74 us, MR 2 / ZT 16 (741 workgroups, 1 round) 55 us.
+    // rows per wave (MR), planes per workgroup (ZT) and the row-pair operand: the rounds model of launch_form.hpp (effi_pick_roll)
     const int cols = effi_cdiv(a.w, 16), D = a.zcount;
-    const bool rp = NT == 1 && a.cout <= 8 && effi_option(EFFI_OPT_ROLL_RP) != 0;      // row-pair operand (see conv3d_roll_rp_bf16x3_body)
-    int mr = 2, zt = D;
-    double best = 1e30;
-    for (int m = 2; m <= 4; m += 2) {
-        // (row-pair kernels, weights in registers: 3 workgroups per CU with 8 input channels, 2 with 16, whatever MR)
-        const int occ = rp ? (NOCT == 1 ? 3 : 2) : (NOCT == 1 && NT == 1) ? (m == 2 ? 3 : 2) : (NOCT == 1 ? 2 : (NT == 1 && m == 2 ? 2 : 1));
-        const long tiles_m = (long)cols * effi_cdiv(a.h, 4 * m), slots = 256L * occ;
-        for (int nz = 1; nz <= D; ++nz) {
-            const int z = effi_cdiv(D, nz);
-            const long wgs = tiles_m * effi_cdiv(D, z) * (pair ? 2 : (bt ? bt->n_img : 1));     // (batched: the workgroups of all samples)
-            const double cost = (double)effi_cdiv(wgs, slots) * (z + 3) * (m == 4 ? 1.3 : 1.0);
-            if (cost < best - 1e-9) { best = cost; mr = m; zt = z; }
-        }
-    }
-    const long fm = effi_option(EFFI_OPT_ROLL_MR), fz = effi_option(EFFI_OPT_ROLL_ZT);       // A/B overrides of the rounds model
-    if (fm != EFFI_OPT_UNSET) mr = (int)fm;
-    if (fz != EFFI_OPT_UNSET) zt = (int)fz;
+    const EffiForm f = effi_pick_roll(NOCT, NT, a.cout, a.h, a.w, D, pair ? 2 : (bt ? bt->n_img : 1), effi_form_opts());
+    const int mr = f.rows, zt = f.planes;
+    const bool rp = f.variant != 0;
     const long tiles = (long)cols * effi_cdiv(a.h, 4 * mr);
     const dim3 grid((unsigned)tiles, (unsigned)effi_cdiv(D, zt), pair ? 2 : (bt ? bt->n_img : 1));
     // (option roll_rp = 0, with packing.py: the one-row-per-tile operand, A/B runs)
@@ -3279,14 +3248,7 @@ static int deconv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf1
     const int tiles_x = effi_cdiv(w, 16);
     const bool al = (w & 3) == 0, half = cout <= 8;       // cout <= 8: packing with 9 fragments per chunk (see the kernel)
     hipStream_t st = effi_s(stream);
-    // rows per wave from the same rounds model as launch_roll: 256 * occ workgroups at a time (occ 5 / 3 with cout <= 8, 3 / 2
-    // otherwise, for 1 / 2 rows per wave), a workgroup costs (rows per wave + 2); measured 16->8 into 48x148x200: 57 -> 43 us
-    // (the batched unaligned-row instantiation with cout <= 8 holds 4 workgroups per CU, not 5: 88 registers against 80)
-    const int occ1 = half ? ((n_smp > 1 && !al) ? 4 : 5) : 3, occ2 = half ? 3 : 2;
-    const long wg1 = (long)tiles_x * effi_cdiv(h, 4) * D * n_smp, wg2 = (long)tiles_x * effi_cdiv(h, 8) * D * n_smp;   // (all samples)
-    bool mr2 = effi_cdiv(wg2, 256L * occ2) * 4 < effi_cdiv(wg1, 256L * occ1) * 3;
-    const long fdm = effi_option(EFFI_OPT_DECONV_MR);
-    if (fdm != EFFI_OPT_UNSET) mr2 = fdm == 2;
+    const bool mr2 = effi_pick_deconv_x3(cout, h, w, D, n_smp, effi_form_opts()).rows == 2;     // (launch_form.hpp: the rounds model)
     const dim3 grid(tiles_x * effi_cdiv(h, mr2 ? 8 : 4), D, n_smp);
 #define EFFI_DC(MRV, ALV, HFV)                                                                                                     \
     do {                                                                                                                           \

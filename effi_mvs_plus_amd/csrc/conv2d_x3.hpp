@@ -3,6 +3,7 @@
 // Included once per translation unit; everything lives in an anonymous namespace (each unit instantiates what it launches).
 #pragma once
 #include "common.hpp"
+#include "launch_form.hpp"
 
 // This file is compiled twice (csrc/Makefile): as it stands, and with -DEFFI_BF16_ONLY, which keeps only the *_bf16x3_* entry points,
 // appends _bf16 to their names and drops the two lo terms of every split product (hi*hi only: plain bf16 operands, fp32
@@ -1120,33 +1121,17 @@ __global__ __launch_bounds__(256) void conv2d_k3_bf16x3_encgen_pair_kernel(const
 }
 
 // ---- split-bf16 3x3 convolution entry --------------------------------------------------------------------------
-// Thresholds of the rows-per-wave choice below (workgroup counts); the environment overrides are for A/B runs of the rule
-// (with several views in flight the chip is filled by other views' kernels, which favours the larger tiles earlier).
-static long effi_opt_or(int id, long dflt) {
-    const long v = effi_option(id);
-    return v == EFFI_OPT_UNSET ? dflt : v;
-}
-static long effi_mr4_min() { return effi_opt_or(EFFI_OPT_MR4_MIN, 400); }
-static long effi_mr4_nt2_max() { return effi_opt_or(EFFI_OPT_MR4_NT2_MAX, 1024); }
-static long effi_mr2_min() { return effi_opt_or(EFFI_OPT_MR2_MIN, 400); }
-// Rows per wave (MR): 4 rows amortise the B fragments best, but the grid must still cover the 256 CUs (>= ~400 workgroups),
-// and with two N-tiles the 4-row variant drops to 2 workgroups per CU where the 2-row one keeps 4: on large maps the latter
-// wins.  (Persistent workgroups with cross-tile prefetch were built and measured twice: no gain, more registers.)
+// The rows-per-wave, wide-tile and eight-wave rules are the pick functions of launch_form.hpp (effi_pick_x3 and its twins); the
+// environment overrides of their thresholds are for A/B runs of the rule (with several views in flight the chip is filled by other
+// views' kernels, which favours the larger tiles earlier).  (Persistent workgroups with cross-tile prefetch were built and measured
+// twice: no gain, more registers.)
 template <int NT, int EPI, bool ZB = false, bool SR = false>
 static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
     const long cols = effi_cdiv(a.w, 16);
     const long planes = ZB ? a.zcount : 1;
-    const long t4 = cols * effi_cdiv(a.h, 16) * planes, t2 = cols * effi_cdiv(a.h, 8) * planes;
-    int mr;
-    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
-    else if (t2 >= effi_mr2_min()) mr = 2;
-    else mr = 1;
-    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
-    if (force) mr = (int)force;
-    // wide tiles (4 rows x 64 columns) pay off on the large maps only (measured with an HBM-cold working set, 592x800:
-    // 16->16 23.8 -> 22.6 us, 32->12 33.3 -> 30.7, 32->16 GRU update 41.9 -> 38.6; 296x400: 38 -> 49 us for 64->64)
-    const long wide_env = effi_opt_or(EFFI_OPT_WIDE_TILES, -1);
-    const bool wide = wide_env >= 0 ? wide_env != 0 : (mr == 4 && a.w >= 512 && !ZB);
+    const EffiForm f = effi_pick_x3(NT, a.h, a.w, planes, ZB, SR, effi_form_opts());
+    const int mr = f.rows;
+    const bool wide = f.variant != 0;
     if (wide) {
         const int tiles_x = effi_cdiv(a.w, 16 * mr), ntiles = tiles_x * effi_cdiv(a.h, 4);
         const dim3 grid(ntiles, (unsigned)planes);
@@ -1156,13 +1141,7 @@ static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
         return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
     }
     if constexpr (SR) {
-        // eight waves per workgroup: the tile of 4-row waves' workgroup at half the rows per wave, twice the pixels behind one copy of
-        // the weight fragments.  Rule (option sr_waves unset): one row per wave AND six N-tiles -- the stage-1 z | r layer, whose 61 KB
-        // of weight fragments per chunk and 64-pixel workgroup are what its launch moves (84.7-87.0 -> 78.4-79.0 us per view,
-        // profiles/r04_ai_sr_waves_ab2.txt); every other layer is equal or slower with eight waves (stage-3 z | r: +12 us).
-        // sr_waves = 8: wherever the rule picks 1 or 2 rows per wave (A/B); sr_waves = 4: never.
-        const long srw = effi_option(EFFI_OPT_SR_WAVES);
-        if ((srw == 8 && mr <= 2) || (srw == EFFI_OPT_UNSET && mr == 1 && NT >= 6)) {
+        if (f.waves == 8) {               // eight waves per workgroup (launch_form.hpp: effi_pick_x3)
             const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 8 * mr);
             const dim3 grid(ntiles, 1);
             if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, false, false, true, 8>), grid, dim3(512), 0, st, a, tiles_x, ntiles);
@@ -1184,16 +1163,10 @@ static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
 template <int NT, int EPI>
 static int launch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
     const long cols = effi_cdiv(a.w, 16);
-    const long t4 = cols * effi_cdiv(a.h, 16) * b.n_img, t2 = cols * effi_cdiv(a.h, 8) * b.n_img;
-    int mr;
-    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
-    else if (t2 >= effi_mr2_min()) mr = 2;
-    else mr = 1;
-    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
-    if (force) mr = (int)force;
+    const EffiForm f = effi_pick_x3_batch(NT, a.h, a.w, b.n_img, effi_form_opts());
+    const int mr = f.rows;
     if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
-    const long wide_env = effi_opt_or(EFFI_OPT_WIDE_TILES, -1);
-    const bool wide = wide_env >= 0 ? wide_env != 0 : (mr == 4 && a.w >= 512);
+    const bool wide = f.variant != 0;
     const int tiles_x = wide ? effi_cdiv(a.w, 16 * mr) : (int)cols, ntiles = tiles_x * effi_cdiv(a.h, wide ? 4 : 4 * mr);
     const dim3 grid(ntiles, (unsigned)b.n_img);
     if (wide) {
@@ -1219,13 +1192,7 @@ __global__ __launch_bounds__(256) void conv3d_k3_bf16x3_zb_batch_kernel(const Co
 template <int NT>
 static int launch_bf16x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
     const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * b.n_img;
-    const long t4 = cols * effi_cdiv(a.h, 16) * planes, t2 = cols * effi_cdiv(a.h, 8) * planes;
-    int mr;
-    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
-    else if (t2 >= effi_mr2_min()) mr = 2;
-    else mr = 1;
-    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
-    if (force) mr = (int)force;
+    const int mr = effi_pick_x3_zb_batch(NT, a.h, a.w, planes, effi_form_opts()).rows;
     if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
     const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 4 * mr);
     const dim3 grid(ntiles, (unsigned)a.zcount, (unsigned)b.n_img);
@@ -1277,20 +1244,15 @@ static int dispatch_bf16x3(const Conv2dArgs& a, int nt, hipStream_t st) {
 template <int NT, bool SR = false>
 static int launch_bf16x3_pair(const Conv2dArgs& a0, const Conv2dArgs& a1, hipStream_t st) {
     const long cols = effi_cdiv(a0.w, 16);
-    const long t4 = cols * effi_cdiv(a0.h, 16) * 2, t2 = cols * effi_cdiv(a0.h, 8) * 2;
-    int mr;
-    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
-    else if (t2 >= effi_mr2_min()) mr = 2;
-    else mr = 1;
-    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
-    if (force) mr = (int)force;
-    if (mr == 4 && a0.w >= 512) {
+    const EffiForm f = effi_pick_x3_pair(NT, a0.h, a0.w, SR, effi_form_opts());
+    const int mr = f.rows;
+    if (f.variant != 0) {
         const int tiles_x = effi_cdiv(a0.w, 64), ntiles = tiles_x * effi_cdiv(a0.h, 4);
         hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 4, true, SR>), dim3(ntiles, 2), dim3(256), 0, st, a0, a1, tiles_x, ntiles);
         return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
     }
     if constexpr (SR) {
-        if (effi_option(EFFI_OPT_SR_WAVES) == 8 && mr <= 2) {
+        if (f.waves == 8) {
             const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a0.h, 8 * mr);
             const dim3 grid(ntiles, 2);
             if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 2, false, true, 8>), grid, dim3(512), 0, st, a0, a1, tiles_x, ntiles);
@@ -1310,13 +1272,7 @@ static int launch_bf16x3_pair(const Conv2dArgs& a0, const Conv2dArgs& a1, hipStr
 template <int NT>
 static int launch_bf16x3_encgen_pair(const Conv2dArgs& a0, const Conv2dArgs& a1, const EncGenArgs& g, hipStream_t st) {
     const long cols = effi_cdiv(a0.w, 16);
-    const long t4 = cols * effi_cdiv(a0.h, 16) * 2, t2 = cols * effi_cdiv(a0.h, 8) * 2;
-    int mr;
-    if (t4 >= effi_mr4_min() && !(NT == 2 && t4 >= effi_mr4_nt2_max())) mr = 4;
-    else if (t2 >= effi_mr2_min()) mr = 2;
-    else mr = 1;
-    const long force = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
-    if (force) mr = (int)force;
+    int mr = effi_pick_x3_rows(NT, a0.h, a0.w, 2, effi_form_opts());
     // always 16-column tiles: the generated image pays per STAGED pixel (24 volume taps each), and a 4 x 64 tile stages 1.55 x its
     // pixels against 1.27 x for 16 x 16 (592x800, hd 16: 55 us per launch with wide tiles, 47 us without; the loaded form gains 5 %
     // from wide tiles)

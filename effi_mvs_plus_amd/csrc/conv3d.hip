@@ -9,13 +9,10 @@
 // arrive through the scalar cache as SGPR operands of v_fma.  Planar [C][D][h][w] layout: lanes run
 // along x, so tile loads and output stores are coalesced.
 #include "common.hpp"
+#include "launch_form.hpp"          // (defines the tile EFFI_C3_TX x EFFI_C3_TY of these kernels, which its rules count)
 
 namespace {
 
-#ifndef EFFI_C3_TX
-#define EFFI_C3_TX 32          // tile of the vector-ALU kernels (A/B builds: -DEFFI_C3_TX=64 -DEFFI_C3_TY=4)
-#define EFFI_C3_TY 8
-#endif
 constexpr int TX = EFFI_C3_TX, TY = EFFI_C3_TY;
 static_assert(TX * TY == 256, "one thread per tile pixel");
 
@@ -369,7 +366,7 @@ int launch_c1to8(const C1Call& a, const C1Call* b, int D, int h, int w, int sxy,
     if ((long)D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input volume
     const int ho = (h - 1) / sxy + 1, wo = (w - 1) / sxy + 1;
     const long tiles = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY), ncall = b ? 2 : n_smp;
-    const bool z8 = tiles * effi_cdiv(D, 8) * ncall >= 512;
+    const bool z8 = effi_pick_c3_planes(ho, wo, D, ncall).planes == 8;
     const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
     const C1Call& bb = b ? *b : a;
 #define EFFI_C1(SXYV, ZV)                                                                                                             \
@@ -595,7 +592,7 @@ int launch_c8to1(const C8Call& a, const C8Call* b, int D, int h, int w, int relu
                  long out_ss = 0) {
     if (8L * D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input tensor
     const long tiles = (long)effi_cdiv(w, TX) * effi_cdiv(h, TY), ncall = b ? 2 : n_smp;
-    const bool z8 = tiles * effi_cdiv(D, 8) * ncall >= 512;
+    const bool z8 = effi_pick_c3_planes(h, w, D, ncall).planes == 8;
     const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
     if (n_smp > 1) {
         if (z8) hipLaunchKernelGGL((conv3d_c8to1_batch_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, relu);
@@ -916,7 +913,7 @@ static int deconv3d_k3_impl(const float* in, int cin, const float* weight, const
                                skip, out);                                                                                            \
     } while (0)
     if (sz == 2 && cout % 8 == 0) {
-        if ((long)tiles * D * (cout / 8) * n_smp >= 512) EFFI_DK(8, 2, tiles * D * (cout / 8));
+        if (effi_pick_deconv_k3(cout, h, w, D, n_smp).planes == 8) EFFI_DK(8, 2, tiles * D * (cout / 8));
         else EFFI_DK(4, 2, tiles * D * (cout / 4));   // low-resolution level: split the output channels finer so the grid covers the chip
     } else if (sz == 1 && cout == 1 && cin == 8 && !skip && c3_lean(1)) {
         const C8Call c{in, weight, bias, out};

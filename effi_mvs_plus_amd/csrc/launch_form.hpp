@@ -1,0 +1,183 @@
+// The launch rules of the convolution kernels as pure host functions: sizes, N-tile count, image / sample / pair counts and a snapshot
+// of the tuning options go in, the tile form comes out.  Every launcher calls the pick function of its rule and launches what it
+// returns; effi_launch_form (api.hip) calls the same functions without launching anything, so that a test can assert the form a case
+// is written for (tests/conv_cases.py: FORMS) and sweep the forms the workloads take.  There is no second copy of a rule.
+#pragma once
+#include "common.hpp"
+
+#ifndef EFFI_C3_TX
+#define EFFI_C3_TX 32          // tile of the vector-ALU 3-D kernels (A/B builds: -DEFFI_C3_TX=64 -DEFFI_C3_TY=4)
+#define EFFI_C3_TY 8
+#endif
+
+struct EffiFormOpts {           // the options a rule reads, defaults of the thresholds resolved
+    long force_mr;              // 0 = the rule
+    long mr4_min, mr4_nt2_max, mr2_min;
+    long wide_tiles;            // -1 = the rule
+    long sr_waves, roll_mr, roll_zt, roll_rp, deconv_mr;        // EFFI_OPT_UNSET = the rule
+};
+
+static inline long effi_opt_or(int id, long dflt) {
+    const long v = effi_option(id);
+    return v == EFFI_OPT_UNSET ? dflt : v;
+}
+
+static inline EffiFormOpts effi_form_opts() {
+    EffiFormOpts o;
+    o.force_mr = effi_opt_or(EFFI_OPT_FORCE_MR, 0);
+    o.mr4_min = effi_opt_or(EFFI_OPT_MR4_MIN, 400);
+    o.mr4_nt2_max = effi_opt_or(EFFI_OPT_MR4_NT2_MAX, 1024);
+    o.mr2_min = effi_opt_or(EFFI_OPT_MR2_MIN, 400);
+    o.wide_tiles = effi_opt_or(EFFI_OPT_WIDE_TILES, -1);
+    o.sr_waves = effi_option(EFFI_OPT_SR_WAVES);
+    o.roll_mr = effi_option(EFFI_OPT_ROLL_MR);
+    o.roll_zt = effi_option(EFFI_OPT_ROLL_ZT);
+    o.roll_rp = effi_option(EFFI_OPT_ROLL_RP);
+    o.deconv_mr = effi_option(EFFI_OPT_DECONV_MR);
+    return o;
+}
+
+struct EffiForm {
+    int rows;       // rows per wave (the kernels' MR); 0 = the 16 x 16 kernel of the generic convolution on unaligned rows
+    int cols;       // columns of a workgroup's tile
+    int waves;      // waves per workgroup
+    int planes;     // planes per workgroup (rolling window), planes per thread (1 -> 8 / 8 -> 1 kernels), output channels per thread
+                    // (vector transposed convolution); 1 elsewhere
+    int variant;    // 1 = the 4 x 64 "wide" instantiation (split 3x3) / the row-pair operand kernel (rolling window)
+};
+
+// ---- split-precision 3x3 (conv2d_x3.hpp) ------------------------------------------------------------------------------------------
+// Rows per wave (MR): 4 rows amortise the B fragments best, but the grid must still cover the 256 CUs (>= ~400 workgroups), and with
+// two N-tiles the 4-row variant drops to 2 workgroups per CU where the 2-row one keeps 4: on large maps the latter wins.  ``count``:
+// the planes (z-batched form), images, samples x planes or the 2 of a pair whose tiles the rule counts.
+static inline int effi_pick_x3_rows(int nt, int h, int w, long count, const EffiFormOpts& o) {
+    const long cols = effi_cdiv(w, 16);
+    const long t4 = cols * effi_cdiv(h, 16) * count, t2 = cols * effi_cdiv(h, 8) * count;
+    int mr;
+    if (t4 >= o.mr4_min && !(nt == 2 && t4 >= o.mr4_nt2_max)) mr = 4;
+    else if (t2 >= o.mr2_min) mr = 2;
+    else mr = 1;
+    if (o.force_mr) mr = (int)o.force_mr;
+    return mr;
+}
+
+// launch_bf16x3: wide tiles (4 rows x 64 columns) pay off on the large maps only (measured with an HBM-cold working set, 592x800:
+// 16->16 23.8 -> 22.6 us, 32->12 33.3 -> 30.7, 32->16 GRU update 41.9 -> 38.6; 296x400: 38 -> 49 us for 64->64).
+// Eight waves per workgroup (split-resident maps): the tile of 4-row waves' workgroup at half the rows per wave, twice the pixels
+// behind one copy of the weight fragments.  Rule (option sr_waves unset): one row per wave AND six N-tiles -- the stage-1 z | r
+// layer, whose 61 KB of weight fragments per chunk and 64-pixel workgroup are what its launch moves (84.7-87.0 -> 78.4-79.0 us per
+// view, profiles/r04_ai_sr_waves_ab2.txt); every other layer is equal or slower with eight waves (stage-3 z | r: +12 us).
+// sr_waves = 8: wherever the rule picks 1 or 2 rows per wave (A/B); sr_waves = 4: never.
+static inline EffiForm effi_pick_x3(int nt, int h, int w, long planes, bool zb, bool sr, const EffiFormOpts& o) {
+    const int mr = effi_pick_x3_rows(nt, h, w, planes, o);
+    const bool wide = o.wide_tiles >= 0 ? o.wide_tiles != 0 : (mr == 4 && w >= 512 && !zb);
+    if (wide) return EffiForm{mr, 16 * mr, 4, 1, 1};
+    if (sr && ((o.sr_waves == 8 && mr <= 2) || (o.sr_waves == EFFI_OPT_UNSET && mr == 1 && nt >= 6))) return EffiForm{mr, 16, 8, 1, 0};
+    return EffiForm{mr, 16, 4, 1, 0};
+}
+
+// launch_bf16x3_batch: the rule of launch_bf16x3 on the tile count of ALL images
+static inline EffiForm effi_pick_x3_batch(int nt, int h, int w, long n_img, const EffiFormOpts& o) {
+    const int mr = effi_pick_x3_rows(nt, h, w, n_img, o);
+    const bool wide = o.wide_tiles >= 0 ? o.wide_tiles != 0 : (mr == 4 && w >= 512);
+    return wide ? EffiForm{mr, 16 * mr, 4, 1, 1} : EffiForm{mr, 16, 4, 1, 0};
+}
+
+// launch_bf16x3_zb_batch: the tiles of all planes of all samples; never the wide tiles
+static inline EffiForm effi_pick_x3_zb_batch(int nt, int h, int w, long planes, const EffiFormOpts& o) {
+    return EffiForm{effi_pick_x3_rows(nt, h, w, planes, o), 16, 4, 1, 0};
+}
+
+// launch_bf16x3_pair: tile shape chosen as launch_bf16x3 does for two planes (eight waves only with sr_waves = 8)
+static inline EffiForm effi_pick_x3_pair(int nt, int h, int w, bool sr, const EffiFormOpts& o) {
+    const int mr = effi_pick_x3_rows(nt, h, w, 2, o);
+    if (mr == 4 && w >= 512) return EffiForm{4, 64, 4, 1, 1};
+    if (sr && o.sr_waves == 8 && mr <= 2) return EffiForm{mr, 16, 8, 1, 0};
+    return EffiForm{mr, 16, 4, 1, 0};
+}
+
+// ---- generic fp32 MFMA convolution (conv2d.hip: launch2d, launch2d_batch) ---------------------------------------------------------
+// rows per wave: the largest of {4, 2, 1} that still yields >= 2 workgroups per CU (256 CUs) over the tiles of all images; a 1x1
+// convolution takes at least two rows (and four from 256 tiles); rows of w % 4 != 0 take the 16 x 16 kernel
+static inline EffiForm effi_pick_generic(int ks, int h, int w, long n_img) {
+    if (w & 3) return EffiForm{0, 16, 4, 1, 0};
+    const long cols = effi_cdiv(w, 16);
+    const long t4 = cols * effi_cdiv(h, 16) * n_img, t2 = cols * effi_cdiv(h, 8) * n_img;
+    int mr;
+    if (t4 >= 512 || (ks == 1 && t4 >= 256)) mr = 4;
+    else if (t2 >= 512 || ks == 1) mr = 2;
+    else mr = 1;
+    return EffiForm{mr, 16, 4, 1, 0};
+}
+
+// ---- fp32 z-batched 3-D forms (dispatch3d_planes, dispatch3d_planes_s2), 5x5 stride 2 (dispatch_k5s2) ------------------------------
+// rows per wave: keep >= 2 workgroups per CU over all planes (of all samples) / all images; the stride-2 forms stop at two rows
+static inline EffiForm effi_pick_planes(int h, int w, long planes, int max_rows) {
+    const long cols = effi_cdiv(w, 16);
+    if (max_rows >= 4 && cols * effi_cdiv(h, 16) * planes >= 512) return EffiForm{4, 16, 4, 1, 0};
+    if (cols * effi_cdiv(h, 8) * planes >= 512) return EffiForm{2, 16, 4, 1, 0};
+    return EffiForm{1, 16, 4, 1, 0};
+}
+
+// ---- split-precision stride-2 forms (launch_s2_x3, _batch, _zb_batch) -------------------------------------------------------------
+// two rows per wave from 400 workgroups: tiles x N-tile groups x planes (of all samples) or images
+static inline EffiForm effi_pick_s2_x3(int h, int w, int ngroups, long planes) {
+    const int cols = effi_cdiv(w, 16);
+    return EffiForm{(long)cols * effi_cdiv(h, 8) * ngroups * planes >= 400 ? 2 : 1, 16, 4, 1, 0};
+}
+
+// ---- rolling-window 3-D convolution (launch_roll) ---------------------------------------------------------------------------------
+// Rows per wave (MR) and planes per workgroup (ZT) from a small cost model fitted to sweeps at the cfg3 shapes
+// (tools/sweep_roll.sh): the chip holds 256 * occ workgroups at a time (occ from the LDS image / register count of the
+// instantiation), a launch takes ceil(workgroups / that) rounds, and a workgroup costs (ZT + 3) plane steps (3 ~ filling
+// the window), 1.3x as much with 4 rows per wave as with 2.  E.g. 8->8 at 48x148x200: MR 4 / ZT 6 (1040 workgroups, 3
+// rounds) 74 us, MR 2 / ZT 16 (741 workgroups, 1 round) 55 us.  ``mult``: 2 for a pair, the samples of a batch, else 1.
+static inline EffiForm effi_pick_roll(int noct, int nt, int cout, int h, int w, int D, long mult, const EffiFormOpts& o) {
+    const int cols = effi_cdiv(w, 16);
+    const bool rp = nt == 1 && cout <= 8 && o.roll_rp != 0;      // row-pair operand (see conv3d_roll_rp_bf16x3_body)
+    int mr = 2, zt = D;
+    double best = 1e30;
+    for (int m = 2; m <= 4; m += 2) {
+        // (row-pair kernels, weights in registers: 3 workgroups per CU with 8 input channels, 2 with 16, whatever MR)
+        const int occ = rp ? (noct == 1 ? 3 : 2) : (noct == 1 && nt == 1) ? (m == 2 ? 3 : 2) : (noct == 1 ? 2 : (nt == 1 && m == 2 ? 2 : 1));
+        const long tiles_m = (long)cols * effi_cdiv(h, 4 * m), slots = 256L * occ;
+        for (int nz = 1; nz <= D; ++nz) {
+            const int z = effi_cdiv(D, nz);
+            const long wgs = tiles_m * effi_cdiv(D, z) * mult;     // (batched: the workgroups of all samples)
+            const double cost = (double)effi_cdiv(wgs, slots) * (z + 3) * (m == 4 ? 1.3 : 1.0);
+            if (cost < best - 1e-9) { best = cost; mr = m; zt = z; }
+        }
+    }
+    if (o.roll_mr != EFFI_OPT_UNSET) mr = (int)o.roll_mr;       // A/B overrides of the rounds model
+    if (o.roll_zt != EFFI_OPT_UNSET) zt = (int)o.roll_zt;
+    return EffiForm{mr, 16, 4, zt, rp ? 1 : 0};
+}
+
+// ---- split-precision transposed 3-D convolution (deconv3d_k3s2_x3_impl) -----------------------------------------------------------
+// rows per wave from the same rounds model as launch_roll: 256 * occ workgroups at a time (occ 5 / 3 with cout <= 8, 3 / 2
+// otherwise, for 1 / 2 rows per wave), a workgroup costs (rows per wave + 2); measured 16->8 into 48x148x200: 57 -> 43 us
+// (the batched unaligned-row instantiation with cout <= 8 holds 4 workgroups per CU, not 5: 88 registers against 80)
+static inline EffiForm effi_pick_deconv_x3(int cout, int h, int w, int D, long n_smp, const EffiFormOpts& o) {
+    const int tiles_x = effi_cdiv(w, 16);
+    const bool al = (w & 3) == 0, half = cout <= 8;
+    const int occ1 = half ? ((n_smp > 1 && !al) ? 4 : 5) : 3, occ2 = half ? 3 : 2;
+    const long wg1 = (long)tiles_x * effi_cdiv(h, 4) * D * n_smp, wg2 = (long)tiles_x * effi_cdiv(h, 8) * D * n_smp;   // (all samples)
+    bool mr2 = effi_cdiv(wg2, 256L * occ2) * 4 < effi_cdiv(wg1, 256L * occ1) * 3;
+    if (o.deconv_mr != EFFI_OPT_UNSET) mr2 = o.deconv_mr == 2;
+    return EffiForm{mr2 ? 2 : 1, 16, 4, 1, 0};
+}
+
+// ---- vector-ALU 3-D kernels (conv3d.hip) ------------------------------------------------------------------------------------------
+// 1 -> 8 and 8 -> 1 channels: 8 planes per thread when the grid still covers the chip twice (h, w: the OUTPUT map; ncall: the two
+// calls of a pair or the samples of a batch)
+static inline EffiForm effi_pick_c3_planes(int h, int w, int D, long ncall) {
+    const long tiles = (long)effi_cdiv(w, EFFI_C3_TX) * effi_cdiv(h, EFFI_C3_TY);
+    return EffiForm{1, EFFI_C3_TX, 4, tiles * effi_cdiv(D, 8) * ncall >= 512 ? 8 : 4, 0};
+}
+
+// transposed convolution, stride 2, cout % 8 == 0: 8 output channels per thread, 4 on the low-resolution level (the output channels
+// split finer so that the grid covers the chip)
+static inline EffiForm effi_pick_deconv_k3(int cout, int h, int w, int D, long n_smp) {
+    const int tiles = effi_cdiv(w, EFFI_C3_TX) * effi_cdiv(h, EFFI_C3_TY);
+    return EffiForm{1, EFFI_C3_TX, 4, (long)tiles * D * (cout / 8) * n_smp >= 512 ? 8 : 4, 0};
+}

@@ -7,6 +7,7 @@ unbatched call on element i.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 import os
@@ -159,6 +160,24 @@ class options:
         for k, v in self.before.items():
             set_option(k, v)
         return False
+
+
+# launcher ids and flags of effi_launch_form (include/effi_mvs_hip.h: EFFI_LF_*)
+LAUNCHERS = {"x3": 0, "x3_batch": 1, "x3_zb_batch": 2, "x3_pair": 3, "conv2d": 4, "planes3d": 5, "k5s2": 6, "s2_x3": 7, "roll": 8,
+             "deconv_x3": 9, "c3_planes": 10, "deconv_k3": 11}
+LaunchForm = collections.namedtuple("LaunchForm", "rows cols waves planes variant")
+
+
+def launch_form(launcher, h, w, nt=1, planes=1, count=1, cout=1, sr=False, zb=False, k1=False, s2=False, oct2=False):
+    """The tile form the launch rule of ``launcher`` (a key of LAUNCHERS) picks for these sizes under the CURRENT options, as
+    LaunchForm(rows per wave, tile columns, waves per workgroup, planes per workgroup or thread, variant): effi_launch_form.  Host
+    only: launches nothing, makes no GPU call.  ``h, w``: the map whose tiles the rule counts (the output map of a strided
+    convolution, the input map of a transposed one); ``planes``: D; ``count``: images / samples of a batch, 2 for a pair."""
+    form = (C.c_int * 5)()
+    flags = (1 if sr else 0) | (2 if zb else 0) | (4 if k1 else 0) | (8 if s2 else 0) | (16 if oct2 else 0)
+    check(_lib.lib().effi_launch_form(LAUNCHERS[launcher], nt, h, w, planes, count, cout, flags, C.addressof(form)),
+          "effi_launch_form")
+    return LaunchForm(*form)
 
 
 def set_profile(p):

@@ -982,6 +982,31 @@ int effi_set_option(const char* name, long value);
 long effi_get_option(const char* name);
 long effi_option_unset(void);
 
+/* ---- host-only query of the launch rules: the tile form a convolution launcher picks for the given sizes under the CURRENT options.
+ * Launches nothing and makes no GPU call (tests assert the form a case is written for, and sweep the forms the workloads take).
+ * launcher: EFFI_LF_*; nt = N-tiles of 16 output channels; h, w = the map the rule counts tiles of (the OUTPUT map of a strided
+ * form); planes = D of a 3-D form (1 otherwise); count = images / samples of a batched launch, 2 for a pair launch, else 1; flags =
+ * EFFI_LF_FLAG_*.  form[0..4] = rows per wave (0 = the 16 x 16 kernel the generic convolution takes for w % 4 != 0), columns of a
+ * workgroup's tile, waves per workgroup, planes per workgroup (rolling window) / planes per thread (EFFI_LF_C3_PLANES) / output
+ * channels per thread (EFFI_LF_DECONV_K3) -- 1 elsewhere --, and the variant: 1 = the 4 x 64 "wide" kernel (split 3x3) or the row-pair
+ * operand kernel (rolling window). */
+enum {
+    EFFI_LF_X3 = 0,          /* split 3x3, every epilogue, planar / split-resident (EFFI_LF_FLAG_SR) / z-batched (EFFI_LF_FLAG_ZB, planes) */
+    EFFI_LF_X3_BATCH = 1,    /* its image batch (count) */
+    EFFI_LF_X3_ZB_BATCH = 2, /* sample batch (count) of the z-batched form (planes) */
+    EFFI_LF_X3_PAIR = 3,     /* pair launch, planar / split-resident */
+    EFFI_LF_CONV2D = 4,      /* generic fp32 convolution, 3x3 or (EFFI_LF_FLAG_K1) 1x1, count images */
+    EFFI_LF_PLANES3D = 5,    /* fp32 z-batched 3-D convolution, stride 1 or (EFFI_LF_FLAG_S2) 2, count samples */
+    EFFI_LF_K5S2 = 6,        /* fp32 5x5 stride 2, count images */
+    EFFI_LF_S2_X3 = 7,       /* split-precision stride-2 forms: 5x5 2-D (planes 1, count images), 3x3x3 (planes, count samples) */
+    EFFI_LF_ROLL = 8,        /* rolling-window 3-D convolution: cout, planes, count (2 = pair), EFFI_LF_FLAG_OCT2 = 16 input channels */
+    EFFI_LF_DECONV_X3 = 9,   /* split-precision transposed 3-D convolution: cout, planes, count samples; h, w = the INPUT map */
+    EFFI_LF_C3_PLANES = 10,  /* 1 -> 8 / 8 -> 1 channel 3-D kernels: planes, count = calls of a pair / samples */
+    EFFI_LF_DECONV_K3 = 11   /* vector-ALU transposed 3-D convolution, stride 2: cout, planes, count samples; h, w = the INPUT map */
+};
+enum { EFFI_LF_FLAG_SR = 1, EFFI_LF_FLAG_ZB = 2, EFFI_LF_FLAG_K1 = 4, EFFI_LF_FLAG_S2 = 8, EFFI_LF_FLAG_OCT2 = 16 };
+int effi_launch_form(int launcher, int nt, int h, int w, int planes, int count, int cout, int flags, int* form);
+
 /* ================================================================================================================
  * Split-resident ("SR") activation maps of the GRU update block, models/update.py:33-49,69-99,109-141.
  * In split precision every 3x3 convolution reads an fp32 value x as hi = bf16(x), lo = bf16(x - hi).  The layers of the update

@@ -275,3 +275,45 @@ def test_mutants(dims, cin):
               f"   present check: {'ACCEPTS' if acc else 'rejects'}")
     if dims == 2 and cin in (48, 96):
         assert accepted[(1, cin)][0], "the present tolerance was measured to accept mutant 1 at cin = 48 and 96"
+
+
+# ---------------------------------------------------------------------------------------------
+# tile forms of the launch rules (conv_cases.FORM_CASES; host only: ops.launch_form launches nothing)
+# ---------------------------------------------------------------------------------------------
+def test_every_form_case_reaches_its_form():
+    """Each case of the table gets the form it is written for from the product's own rule under the options it sets; where an option
+    forces the form, the rule alone picks another one on that map (the case is not a second copy of an existing one)."""
+    from effi_mvs_plus_amd import ops
+    cases = CC.form_cases()
+    assert len(cases) >= 60
+    for c in cases:
+        with ops.options(**c.options):
+            got = tuple(ops.launch_form(**c.query))
+        assert got == tuple(c.form), f"{c.row}: {c.how}: the rule gives {got}, the case is written for {c.form}"
+        if any(k in c.options for k in ("force_mr", "roll_mr", "roll_zt", "deconv_mr")):
+            assert tuple(ops.launch_form(**c.query)) != tuple(c.form), f"{c.row}: {c.how}: the rule picks this form unaided"
+    # what stays out of the table: forms only an option can force
+    table = CC.forms()
+    assert (1, 16, 4, 1, 1) not in table["x3 planar"] and (2, 32, 4, 1, 1) not in table["x3 planar"]         # wide with MR 1 / 2
+    assert all(f[2] == 4 or f == CC.W8 for f in table["x3 sr"]) and all(f[2] == 4 for f in table["x3_pair sr"])
+    assert CC.WIDE not in table["x3 z-batched"] and CC.WIDE not in table["x3_zb_batch"]
+
+
+def test_workloads_take_only_forms_of_the_table():
+    """The launch rule over the stage maps of the workloads bench.py names (cfg1-cfg5 at 1/8, 1/4, 1/2 and full resolution, D in 48 / 32 /
+    8, 1-5 images or samples, every N-tile count): every form it returns has a bound case.  A form the workloads can take and no case
+    covers fails here, without a GPU."""
+    from effi_mvs_plus_amd import ops
+    table, seen, missing = CC.forms(), {}, set()
+    for row, query, D in CC.workload_queries():
+        key = CC.table_form(row, ops.launch_form(**query), D)
+        seen.setdefault(row, set()).add(key)
+        if key not in table[row]:
+            missing.add((row, key, tuple(sorted(query.items()))))
+    assert not missing, f"forms the workloads take that no bound case launches: {sorted(missing)[:8]}"
+    assert set(seen) == set(table)
+    for row in table:
+        print(f"[forms] {row}: the workloads take {len(seen[row])} of the table's {len(table[row])} forms")
+    # the forms this work is about are ones the workloads do take: stage 2 runs 4 rows per wave, stage 3 the wide tile (2 rows with NT 2)
+    assert tuple(ops.launch_form("x3", 296, 400, nt=1)) == CC.MR4 and tuple(ops.launch_form("x3", 592, 800, nt=1)) == CC.WIDE
+    assert tuple(ops.launch_form("x3", 592, 800, nt=2)) == CC.MR2 and tuple(ops.launch_form("x3", 74, 100, nt=6, sr=True)) == CC.W8

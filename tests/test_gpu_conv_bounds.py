@@ -114,6 +114,7 @@ def test_split_3x3_every_element_bounded(idx):
     row = f"split 3x3 {epi} act={ACTS[act]} ({mode})"
     left_finer = False
     with precision_(mode), ops.options(force_mr=mr):
+        assert ops.launch_form("x3", h, w, nt=(cout + 15) // 16).rows == mr
         for k, x in enumerate(fam.members):
             got = launch(key, lambda: ops.conv2d_k3_bf16x3(dev_srcs(fam, x), wp, bp, cout, epilogue=epilogue, act=act))
             if epi == "nhwc":
@@ -142,6 +143,7 @@ def test_split_3x3_gru_epilogues_bounded(cins, cout, hw, mr, q, bias):
     hp_d, z_d = t(hprev, DEV), t(z, DEV)
     nt = (cout + 15) // 16
     with precision_("split"), ops.options(force_mr=mr):
+        assert ops.launch_form("x3", h, w, nt=nt).rows == mr
         for k, x in enumerate(fam.members):
             iv = CB.conv_interval(x, None, wt, b, mode="split")
             if q:
@@ -613,7 +615,7 @@ def _vol_interval(i, x, wf, shift, mode, skip):
 
 
 @pytest.mark.parametrize("mode", ["fp32", "split", "bf16"])
-@pytest.mark.parametrize("i", range(len(CC.VOL_CASES)))
+@pytest.mark.parametrize("i", range(CC.N_VOL_BRANCH_CASES))
 def test_conv3d_every_branch_bounded(i, mode):
     """Seams: the union over all 3-D forms (z: every second plane -- 2, 4, 8 planes per thread and the rolling window's runs; y: 4, 8,
     16; x: 16, 32).  The launch key asserts the branch of Conv3d.run / Deconv3d.run the case is written for; the bf16 entries share
@@ -653,3 +655,475 @@ def test_conv3d_family_as_one_batch():
         got = launch(CC.VOL_KEYS[i][0], lambda: m.run([xb[:, :8].contiguous(), xb[:, 8:].contiguous()]))
     for k, x in enumerate(members):
         bounded("conv3d roll, family as one batch", f"conv3d batch member {k}", got[k], _vol_interval(i, x, wf, shift, "split", None))
+
+
+# ---------------------------------------------------------------------------------------------
+# Tile forms of the launch rules: the forms the rules pick on the LARGE maps of the workloads (conv_cases.FORM_CASES), each reached on
+# a small map -- by its option, by a 528-wide map, by a batch or a narrow map that crosses the rule's threshold.  Per case: the
+# form is asserted through ops.launch_form (and, where an option forces it, that the rule alone picks another); every element of
+# every member is bounded by the SAME intervals as above (a pixel's accumulation order does not depend on the tile shape); and the
+# result is bitwise the one of the rule's own form on that member -- the equality the sources claim.
+# ---------------------------------------------------------------------------------------------
+def reach(query, options, form):
+    """The options of a form case, after asserting the form it reaches."""
+    from effi_mvs_plus_amd import ops
+    with ops.options(**options):
+        got = tuple(ops.launch_form(**query))
+    assert got == tuple(form), f"the rule gives {got} for {query} under {options}; the case is written for {form}"
+    if options:
+        assert tuple(ops.launch_form(**query)) != tuple(form), f"{options} force the form the rule picks anyway: {form}"
+    return ops.options(**options)
+
+
+def same_bits(name, a, b):
+    assert a.shape == b.shape and torch.equal(a, b), f"{name}: the forced form's bits differ from the rule's form in {int((a != b).sum())} elements"
+
+
+def _x3_runner(epi, sr, hw, mode="split", q4s=(False, True)):
+    """(row, members, run) of an X3 case: run(member) -> [(label, output, interval)] of ONE launch of the epilogue on that member."""
+    from effi_mvs_plus_amd import ops, packing
+    h, w = hw
+    d = lambda v: None if v is None else v.to(DEV)       # noqa: E731
+    cins, cout = CC.x3_channels(epi)
+    nt = (cout + 15) // 16
+    kind = ("split-resident" if sr else "split") + f" 3x3 {epi.replace('96', '')}, tile forms"
+    g = torch.Generator().manual_seed(len(epi) + h)
+    if "shuf2" in epi:
+        co, f, ci, (h2, w2) = 8, 32, 8, (h // 2, w // 2)
+        tops, l1s = CC.form_family((f,), (h2, w2)), CC.form_family((ci,), hw)
+        w_out, w_in, b_in = CB.he_weights((co, f, 3, 3), 9 * f, g), CB.he_weights((f, ci, 1, 1), ci, g), torch.randn(f, generator=g)
+        (wu, bu), (wl, bl) = packing.pack_fpn_head_split(d(w_out), d(w_in), d(b_in))
+        ones = torch.ones(1, h2, w2, device=DEV)
+        epilogue = ops.EPI_NHWC_ADD_SHUF2 if epi == "nhwc_shuf2" else ops.EPI_ADD_SHUF2
+        zt, zl = torch.zeros_like(tops.members[0]), torch.zeros_like(l1s.members[0])
+        n = max(len(tops.members), len(l1s.members))
+        pairs = [(tops.members[k % len(tops.members)], l1s.members[k % len(l1s.members)]) for k in range(n)]
+        members = [(tp, zl) if k % 3 == 0 else (zt, l1) if k % 3 == 1 else (tp, l1) for k, (tp, l1) in enumerate(pairs)]
+
+        def run(m):
+            top, l1 = m
+            u = launch(f"conv2d_k3x3_nt{(4 * co + 15) // 16}_epi0", lambda: ops.conv2d_k3_bf16x3([t(top, DEV), ones], wu, bu, 4 * co))
+            got = launch(f"conv2d_k3x3_nt1_epi{epilogue}", lambda: ops.conv2d_k3_bf16x3([t(l1, DEV)], wl, bl, co, epilogue=epilogue, aux0=u))
+            return [("FPN head", got.permute(2, 0, 1) if epi == "nhwc_shuf2" else got, _fpn_interval(top, l1, w_out, w_in, b_in))]
+        return kind, members, run
+    fam = CC.form_family(cins, hw)
+    fam.assert_full()
+    srcs_of = (lambda x: [ops.sr_from_planar(s_) for s_ in dev_srcs(fam, x)]) if sr else (lambda x: dev_srcs(fam, x))
+    if epi in ("plain", "nhwc"):
+        wt, b = CC.weights(cout, sum(cins), 3, seed=4000 + h, bias=True)
+        wp, bp = packing.pack_conv2d_bf16x3(d(wt), d(b))
+        epilogue = ops.EPI_NHWC if epi == "nhwc" else ops.EPI_PLAIN
+
+        def run(x):
+            a = CB.act_interval(*CB.conv_interval(x, None, wt, b, mode=mode), "relu")
+            if sr:
+                out0, out_sr = launch(f"conv2d_k3x3_nt{nt}_epi0", lambda: ops.conv2d_k3_sr(
+                    srcs_of(x), wp, bp, cout, act=ops.ACT_RELU, out0=torch.empty(cout, h, w, device=DEV)))
+                return [("sr plain", out0, a), ("sr plain (SR map)", sr_value(out_sr), widen_sr(a))]
+            got = launch(f"conv2d_k3x3_nt{nt}_epi{epilogue}", lambda: ops.conv2d_k3_bf16x3(srcs_of(x), wp, bp, cout, epilogue=epilogue,
+                                                                                            act=ops.ACT_RELU))
+            return [(epi, got.permute(2, 0, 1) if epi == "nhwc" else got, a)]
+        return kind, fam.members, run
+    if epi.startswith("gru"):
+        q = epi == "gru_q"
+        wt, b = CC.weights(cout, sum(cins), 3, seed=4100 + cout + h, bias=True)
+        wp, bp = packing.pack_conv2d_bf16x3(d(wt), d(b))
+        hd = cout if q else cout // 2
+        hprev, z = torch.tanh(torch.randn(hd, h, w, generator=g)), torch.rand(hd, h, w, generator=g)
+        epilogue = ops.EPI_GRU_Q if q else ops.EPI_GRU_ZR
+        key = f"conv2d_k3x3_nt{nt}_epi{epilogue}"
+
+        def run(x):
+            iv = CB.conv_interval(x, None, wt, b, mode="split")
+            iq = CB.act_interval(*iv, "gru_q", "split", h=hprev, z=z) if q else None
+            iz = None if q else CB.act_interval(iv.mid[:hd], iv.half[:hd], "gru_z", "split")
+            irh = None if q else CB.act_interval(iv.mid[hd:], iv.half[hd:], "gru_rh", "split", h=hprev)
+            out = []
+            if not sr:
+                if q:
+                    return [("GRU_Q", launch(key, lambda: ops.conv2d_k3_bf16x3(srcs_of(x), wp, bp, cout, epilogue=epilogue, aux0=t(hprev, DEV),
+                                                                               aux1=t(z, DEV))), iq)]
+                gz, grh = launch(key, lambda: ops.conv2d_k3_bf16x3(srcs_of(x), wp, bp, cout, epilogue=epilogue, aux0=t(hprev, DEV)))
+                return [("GRU z", gz, iz), ("GRU r*h", grh, irh)]
+            for q4 in q4s:                     # planar and / or q4 auxiliaries
+                lay = (lambda v: ops.q4_from_planar(t(v, DEV))) if q4 else (lambda v: t(v, DEV))
+                back = (lambda v, c: ops.q4_to_planar(v.view(c // 4, h, w, 4), c)) if q4 else (lambda v, c: v)
+                if q:
+                    hn, _ = launch(key, lambda: ops.conv2d_k3_sr(srcs_of(x), wp, bp, cout, epilogue=epilogue, aux0=lay(hprev), aux1=lay(z), q4=q4))
+                    out.append((f"sr GRU_Q q4={q4}", back(hn, cout), iq))
+                else:
+                    gz, rh = launch(key, lambda: ops.conv2d_k3_sr(srcs_of(x), wp, bp, cout, epilogue=epilogue, aux0=lay(hprev), q4=q4))
+                    out += [(f"sr GRU z q4={q4}", back(gz, hd), iz), (f"sr GRU r*h q4={q4}", sr_value(rh), widen_sr(irh))]
+            return out
+        return kind, fam.members, run
+    w1, b1 = CC.weights(cout, sum(cins), 3, seed=4200 + cout + h, bias=True)
+    p1, pb1 = packing.pack_conv2d_bf16x3(d(w1), d(b1))
+    if epi == "k1":
+        c_extra, cout2 = CC.K1_EXTRA, 16
+        extras = CC.form_family((c_extra,), hw).members
+        w2, b2 = CC.weights(cout2, cout + c_extra, 1, seed=4300 + h, bias=True)
+        w2p, b2p = packing.pack_conv1x1_after(d(w2), d(b2), cout, c_extra)
+        fn = ops.conv2d_k3_k1_sr if sr else ops.conv2d_k3_k1_x3
+        members = [(x, extras[k % len(extras)]) for k, x in enumerate(fam.members)]
+
+        def run(m):
+            x, extra = m
+            got = launch(f"conv2d_k3k1_nt{nt}", lambda: fn(srcs_of(x), p1, pb1, cout, t(extra, DEV), w2p, b2p, cout2, relu=True, relu1=False))
+            i1 = CB.conv_interval(x, None, w1, b1, mode="split")
+            i2 = chain(CB.Interval(torch.cat([i1.mid, extra.double()]), torch.cat([i1.half, torch.zeros_like(extra, dtype=torch.float64)])),
+                       w2, b2, padding=0)
+            return [("3x3+1x1", got, CB.act_interval(*i2, "relu"))]
+        return kind, members, run
+    assert epi == "k1up"
+    w2, b2 = CC.weights(36, cout, 1, seed=4400 + h, bias=True)
+    inv, dv = torch.rand(1, h, w, generator=g), torch.linspace(1 / 935.0, 1 / 425.0, 384)
+    p2, pb2 = packing.pack_mask_taps_per_lane(d(w2), d(b2), cout, scale=0.25)
+    fn = ops.conv2d_k3_k1_up2x_sr if sr else ops.conv2d_k3_k1_up2x
+
+    def run(x):
+        i1 = CB.act_interval(*CB.conv_interval(x, None, w1, b1, mode="split"), "relu")
+        idepth, iinv = _up2x_interval(chain(i1, 0.25 * w2, 0.25 * b2, padding=0), inv, dv[0], dv[-1])
+        depth, dinv = launch(f"conv2d_k3k1up_nt{nt}", lambda: fn(srcs_of(x), p1, pb1, cout, p2, pb2, t(inv, DEV), t(dv, DEV)))
+        return [("mask head + upsampling depth", depth, idepth), ("mask head + upsampling inverse depth", dinv, iinv)]
+    return kind, fam.members, run
+
+
+def _run_form_case(row, members, run, ctx, other=None, finer_of=None):
+    """Every member under the form's options (``ctx``) bounded, and bitwise the run under ``other`` (default: no option, the rule's own
+    form).  ``finer_of(member, label)``: the finer arithmetic's interval -- some output must leave it (bf16 cases)."""
+    import contextlib
+    left = False
+    for k, m in enumerate(members):
+        with ctx:
+            forced = run(m)
+        with (other or contextlib.nullcontext()):
+            ruled = run(m)
+        for (label, got, iv), (_, ref, _) in zip(forced, ruled):
+            bounded(row, f"{row}: {label} member {k}", got, iv)
+            same_bits(f"{row}: {label} member {k}", got, ref)
+            if finer_of is not None:
+                left |= CB.escapes(got, *finer_of(m, label))
+    assert finer_of is None or left, "the bf16 case stayed inside the split interval everywhere: the split kernel ran"
+
+
+@pytest.mark.parametrize("epi,sr,f", CC.X3_CASES, ids=[f"{e}-{'sr' if s_ else 'planar'}-{f}" for e, s_, f in CC.X3_CASES])
+def test_split_3x3_tile_forms_bounded(epi, sr, f):
+    """launch_bf16x3 with every epilogue under 4 rows per wave, narrow (16 x 16 tiles, force_mr at 21 x 28) and wide (4 x 64 tiles, force_mr
+    at 21 x 528: the rule's own w >= 512; ragged last tile of 16 columns), planar and split-resident; 2 rows per wave dealt round; the
+    eight-wave SR workgroup where the rule picks it unaided ((48, 48) -> 96 at 21 x 28), against the four-wave one (sr_waves = 4)."""
+    from effi_mvs_plus_amd import ops
+    form, hw, opts = CC.x3_form(epi, sr, f)
+    nt = (CC.x3_channels(epi)[1] + 15) // 16
+    with precision_("split"):
+        ctx = reach(dict(launcher="x3", h=hw[0], w=hw[1], nt=nt, sr=sr), opts, form)
+        other = None
+        if f == "w8":
+            with ops.options(sr_waves=4):
+                assert tuple(ops.launch_form("x3", hw[0], hw[1], nt=nt, sr=True)) == CC.MR1
+            other = ops.options(sr_waves=4)
+        # (SR GRU epilogues: the q4 layout of the auxiliaries, the product's default, everywhere; the planar one too on the 9-row maps)
+        row, members, run = _x3_runner(epi, sr, hw, q4s=(False, True) if f == "wide9" else (True,))
+        _run_form_case(row, members, run, ctx, other)
+
+
+def test_split_3x3_wide_tiles_in_bf16_leave_the_split_interval():
+    """The wide tile once more with plain bf16 operands: bounded by the bf16 interval, bitwise the narrow form, and somewhere outside
+    the split interval (the split kernel did not run in its place)."""
+    epi, sr, f = CC.X3_BF16
+    form, hw, opts = CC.x3_form(epi, sr, f)
+    cins, cout = CC.x3_channels(epi)
+    wt, b = CC.weights(cout, sum(cins), 3, seed=4000 + hw[0], bias=True)         # (the weights of _x3_runner's "plain" case)
+    with precision_("bf16"):
+        ctx = reach(dict(launcher="x3", h=hw[0], w=hw[1], nt=1), opts, form)
+        row, members, run = _x3_runner(epi, sr, hw, mode="bf16")
+        _run_form_case(row + " (bf16)", members, run, ctx,
+                       finer_of=lambda x, label: CB.act_interval(*CB.conv_interval(x, None, wt, b, mode="split"), "relu"))
+
+
+@pytest.mark.parametrize("sr,f", CC.PAIR_CASES, ids=[f"{'sr' if s_ else 'planar'}-{f}" for s_, f in CC.PAIR_CASES])
+def test_split_3x3_pair_tile_forms_bounded(sr, f):
+    """launch_bf16x3_pair: 1 (the rule at 21 x 28), 2 and 4 rows per wave and the wide tile (9 x 528), planar and split-resident; two
+    DIFFERENT convolutions of one member, each bitwise the single launch of the rule's form."""
+    from effi_mvs_plus_amd import ops, packing
+    form, (h, w), opts = CC._X3_FORM[f]
+    cins, cout = (16,), 16
+    fam = CC.form_family(cins, (h, w))
+    fam.assert_full()
+    (wa, ba), (wb, bb) = CC.weights(cout, 16, 3, seed=4500 + h, bias=True), CC.weights(cout, 16, 3, seed=4600 + h, bias=False)
+    d = lambda v: None if v is None else v.to(DEV)       # noqa: E731
+    (pa, pba), (pb, pbb) = packing.pack_conv2d_bf16x3(d(wa), d(ba)), packing.pack_conv2d_bf16x3(d(wb), d(bb))
+    row = f"conv2d_k3 pair{' sr' if sr else ''}, tile forms"
+    with precision_("split"):
+        ctx = reach(dict(launcher="x3_pair", h=h, w=w, nt=1, sr=sr), opts, form)
+        for k, x in enumerate(fam.members):
+            ia = CB.act_interval(*CB.conv_interval(x, None, wa, ba, mode="split"), "relu")
+            ib = CB.act_interval(*CB.conv_interval(x, None, wb, bb, mode="split"), "relu")
+            if sr:
+                srcs = [ops.sr_from_planar(s_) for s_ in dev_srcs(fam, x)]
+                oa, ob = ops.sr_alloc(2, cout, h, w, DEV)
+                with ctx:
+                    launch("conv2d_k3x3_pair_nt1", lambda: ops.conv2d_k3_pair_sr(srcs, pa, pba, oa, srcs, pb, pbb, ob, cout, act=ops.ACT_RELU))
+                ga, gb, ia, ib = sr_value(oa), sr_value(ob), widen_sr(ia), widen_sr(ib)
+                ra = sr_value(launch("conv2d_k3x3_nt1_epi0", lambda: ops.conv2d_k3_sr(srcs, pa, pba, cout, act=ops.ACT_RELU)))
+                rb = sr_value(launch("conv2d_k3x3_nt1_epi0", lambda: ops.conv2d_k3_sr(srcs, pb, pbb, cout, act=ops.ACT_RELU)))
+            else:
+                srcs = dev_srcs(fam, x)
+                with ctx:
+                    ga, gb = launch("conv2d_k3x3_pair_nt1", lambda: ops.conv2d_k3_bf16x3_pair(srcs, pa, pba, srcs, pb, pbb, cout, act=ops.ACT_RELU))
+                ra = launch("conv2d_k3x3_nt1_epi0", lambda: ops.conv2d_k3_bf16x3(srcs, pa, pba, cout, act=ops.ACT_RELU))
+                rb = launch("conv2d_k3x3_nt1_epi0", lambda: ops.conv2d_k3_bf16x3(srcs, pb, pbb, cout, act=ops.ACT_RELU))
+            for name, got, iv, ref, wt in (("a", ga, ia, ra, wa), ("b", gb, ib, rb, wb)):
+                bounded(row, f"{row} {f}: {name} member {k}", got, iv, x, wt.shape)
+                same_bits(f"{row} {f}: {name} member {k}", got, ref)
+
+
+@pytest.mark.parametrize("launcher,f", CC.BATCH_CASES, ids=[f for _, f in CC.BATCH_CASES])
+def test_split_3x3_batch_tile_forms_bounded(launcher, f):
+    """launch_bf16x3_batch: a whole family as ONE launch (NHWC for the odd cases); the rule counts the tiles of all images -- 48 images
+    of 9 x 528 get the wide tile unaided -- and image i is bitwise the single launch on member i."""
+    from effi_mvs_plus_amd import ops, packing
+    form, (h, w), opts = CC._X3_FORM[f]
+    opts = {} if f == "wide9" else opts
+    fam = CC.form_family((16,), (h, w))
+    fam.assert_full()
+    wt, b = CC.weights(16, 16, 3, seed=4700 + h, bias=True)
+    wp, bp = packing.pack_conv2d_bf16x3(wt.to(DEV), b.to(DEV))
+    nhwc = f in ("mr2", "wide9")
+    epilogue = ops.EPI_NHWC if nhwc else ops.EPI_PLAIN
+    xb = t(torch.stack(fam.members), DEV)
+    row = "split 3x3 batch, tile forms"
+    with precision_("split"):
+        with reach(dict(launcher=launcher, h=h, w=w, nt=1, count=len(fam.members)), opts, form):
+            got = launch(f"conv2d_k3x3_nt1_epi{epilogue}_batch", lambda: ops.conv2d_k3_bf16x3([xb], wp, bp, 16, epilogue=epilogue, act=ops.ACT_RELU))
+        for k, x in enumerate(fam.members):
+            one = launch(f"conv2d_k3x3_nt1_epi{epilogue}", lambda: ops.conv2d_k3_bf16x3([xb[k]], wp, bp, 16, epilogue=epilogue, act=ops.ACT_RELU))
+            gk = got[k].permute(2, 0, 1) if nhwc else got[k]
+            bounded(row, f"{row} {f}: member {k}", gk, CB.act_interval(*CB.conv_interval(x, None, wt, b, mode="split"), "relu"), x, wt.shape)
+            same_bits(f"{row} {f}: member {k}", got[k], one)
+
+
+@pytest.mark.parametrize("f", ["mr1", "mr2", "mr4"])
+def test_conv3d_z_batched_tile_forms_bounded(f):
+    """The z-batched split 3-D convolution (launch_bf16x3 with ZB, VOL case 4) and its sample batch (launch_bf16x3_zb_batch) under 1
+    (the rule), 2 and 4 rows per wave; samples in batches of ZB_BATCH, each bitwise the single launch of the rule's form."""
+    from effi_mvs_plus_amd import ops
+    i = 4
+    form, _, opts = CC._X3_FORM[f]
+    kind, cins, cout, stride, (D, h, w), relu, skip = CC.VOL_CASES[i]
+    fam = CC.vol_family(i)
+    m, wf, shift = _vol_module(i)
+    key = CC.VOL_KEYS[i][0]
+    n, members = CC.ZB_BATCH, fam.members
+    row = "conv3d z-batched split, tile forms"
+    with precision_("split"), torch.no_grad():
+        one = reach(dict(launcher="x3", h=h, w=w, nt=2, planes=D, zb=True), opts, form)
+        many = reach(dict(launcher="x3_zb_batch", h=h, w=w, nt=2, planes=D, count=n), opts, form)
+        for s0 in [min(s0, len(members) - n) for s0 in range(0, len(members), n)]:
+            xb = t(torch.stack(members[s0:s0 + n]), DEV)
+            with many:
+                gb = launch(key, lambda: m.run([xb]))
+            for j in range(n):
+                x = members[s0 + j]
+                with one:
+                    got = launch(key, lambda: m.run([xb[j]]))
+                ref = got if not opts else launch(key, lambda: m.run([xb[j]]))
+                bounded(row, f"{row} {f}: member {s0 + j}", got, _vol_interval(i, x, wf, shift, "split", None), x, wf.shape, (1, 1, 1), 1, 3)
+                same_bits(f"{row} {f}: member {s0 + j}", got, ref)
+                same_bits(f"{row} {f}: batched member {s0 + j}", gb[j], ref)
+
+
+@pytest.mark.parametrize("idx", range(len(CC.GENERIC_FORM_CASES)))
+def test_generic_fp32_tile_forms_bounded(idx):
+    """launch2d / launch2d_batch have no option: the narrowest maps that cross the rule's thresholds (conv_cases.GENERIC_FORM_CASES),
+    single and as batches of images.  A batch is compared bitwise with the single launches (another form: fewer tiles)."""
+    from effi_mvs_plus_amd import ops, packing
+    ks, cins, cout, act, (h, w), n, form = CC.GENERIC_FORM_CASES[idx]
+    fam = CC.family(cins, (h, w), ks // 2, CC.fam_key(CC.GENERIC_TILES), seed=ks + sum(cins))
+    fam.assert_full()
+    wt, b = CC.weights(cout, sum(cins), ks, seed=4800 + idx, bias=idx % 2)
+    wp, bp = packing.pack_conv2d_mfma(wt.to(DEV), None if b is None else b.to(DEV))
+    nt = (cout + 15) // 16
+    key = f"conv2d_k{ks}_nt{nt}_epi{ops.EPI_PLAIN}"
+    row = f"generic fp32 conv2d k{ks}, tile forms"
+    query = dict(launcher="conv2d", h=h, w=w, nt=nt, k1=ks == 1)
+    members = fam.members
+
+    def check(k, got):
+        iv = CB.conv_interval(members[k], None, wt, b, 1, ks // 2, None, "fp32")
+        a = CB.act_interval(*iv, ACTS[act], "exact")
+        a.k_eff = iv.k_eff
+        bounded(row, f"{row} {h}x{w} x{n}: member {k}", got, a, members[k], wt.shape, 1, ks // 2)
+
+    with reach(dict(query, count=n), {}, form):
+        if n == 1:
+            for k, x in enumerate(members):
+                check(k, launch(key, lambda: ops.conv2d(dev_srcs(fam, x), wp, bp, cout, ks, act=act)))
+            return
+        assert tuple(ops.launch_form(**dict(query, count=1))) != tuple(form), "the single image takes the same form: nothing to compare"
+        for s0 in [min(s0, len(members) - n) for s0 in range(0, len(members), n)]:
+            xb = t(torch.stack(members[s0:s0 + n]), DEV)
+            gb = launch(key + "_batch", lambda: ops.conv2d([xb], wp, bp, cout, ks, act=act))
+            for j in range(n):
+                check(s0 + j, gb[j])
+                same_bits(f"{row}: member {s0 + j}", gb[j], launch(key, lambda: ops.conv2d([xb[j]], wp, bp, cout, ks, act=act)))
+
+
+def _roll_interval(i, x, wf, shift, mode):
+    return _vol_interval(i, x, wf, shift, mode, None)
+
+
+@pytest.mark.parametrize("entry,i,rp,mr,zt", CC.ROLL_CASES, ids=[f"{e}-case{i}-rp{rp}-mr{mr}-zt{zt}" for e, i, rp, mr, zt in CC.ROLL_CASES])
+def test_conv3d_rolling_window_tile_forms_bounded(entry, i, rp, mr, zt):
+    """launch_roll at D = 12: 2 and 4 rows per wave with one run of 12 planes, three full runs of 4 (the window refilled at every run
+    boundary) and runs of 5 with a ragged last one of 2; the single, pair and sample-batched entries; the row-pair kernels (cout <=
+    8) and the one-row operand (roll_rp = 0, packed under the same option; cout 16).  Bitwise the rule's own form (runs of one plane)."""
+    from effi_mvs_plus_amd import ops, packing
+    kind, cins, cout, stride, (D, h, w), relu, skip = CC.VOL_CASES[i]
+    fam = CC.form_vol_family(i)
+    fam.assert_full()
+    m, wf, shift = _vol_module(i)
+    opts = {"roll_mr": mr, "roll_zt": zt}
+    rp_opts = {} if rp is None else {"roll_rp": rp}
+    count = {"single": 1, "pair": 2, "batch": CC.ROLL_BATCH}[entry]
+    key = CC.VOL_KEYS[i][0]
+    row = f"conv3d roll {entry}, tile forms"
+    variant = 1 if cout <= 8 and rp != 0 else 0
+    with precision_("split"), torch.no_grad(), ops.options(**rp_opts):
+        ctx = reach(dict(launcher="roll", h=h, w=w, nt=(cout + 15) // 16, planes=D, cout=cout, count=count, oct2=sum(cins) == 16), opts,
+                    (mr, 16, 4, zt, variant))
+        wp, bp = packing.pack_conv3d_roll_bf16x3(m.conv, m.bn)          # (packed under roll_rp: the operand layout follows the option)
+        run1 = lambda srcs: ops.conv3d_k3s1_roll(srcs, wp, bp, cout, relu=relu)          # noqa: E731
+        members = fam.members
+        if entry == "batch":
+            for s0 in [min(s0, len(members) - count) for s0 in range(0, len(members), count)]:
+                xb = t(torch.stack(members[s0:s0 + count]), DEV)
+                with ctx:
+                    gb = launch(key, lambda: run1([xb]))
+                for j in range(count):
+                    bounded(row, f"{row}: member {s0 + j}", gb[j], _roll_interval(i, members[s0 + j], wf, shift, "split"))
+                    same_bits(f"{row}: member {s0 + j}", gb[j], launch(key, lambda: run1([xb[j]])))
+            return
+        for k, x in enumerate(members):
+            srcs = dev_srcs(fam, x)
+            iv = _roll_interval(i, x, wf, shift, "split")
+            ref = launch(key, lambda: run1(srcs))
+            if entry == "single":
+                with ctx:
+                    outs = [launch(key, lambda: run1(srcs))]
+            else:                                    # the pair: the same convolution on a member and on its neighbour in the family
+                y = members[(k + 1) % len(members)]
+                with ctx:
+                    ga, gb = launch(f"conv3d_roll_pair_oct{sum(cins) // 8}", lambda: ops.conv3d_k3s1_roll_pair(
+                        srcs, wp, bp, dev_srcs(fam, y), wp, bp, cout, relu=relu))
+                bounded(row, f"{row}: b member {k}", gb, _roll_interval(i, y, wf, shift, "split"))
+                outs = [ga]
+            for got in outs:
+                bounded(row, f"{row}: member {k}", got, iv, x, wf.shape, (1, 1, 1), 1, 3)
+                same_bits(f"{row}: member {k}", got, ref)
+
+
+def test_conv3d_rolling_window_runs_in_bf16_leave_the_split_interval():
+    """4 rows per wave, runs of 5 planes, plain bf16 operands: inside the bf16 interval, bitwise the rule's form, outside the split one."""
+    from effi_mvs_plus_amd import ops, packing
+    entry, i, rp, mr, zt = CC.ROLL_BF16
+    kind, cins, cout, stride, (D, h, w), relu, skip = CC.VOL_CASES[i]
+    fam = CC.form_vol_family(i)
+    m, wf, shift = _vol_module(i)
+    left = False
+    with precision_("bf16"), torch.no_grad():
+        ctx = reach(dict(launcher="roll", h=h, w=w, planes=D, cout=cout), {"roll_mr": mr, "roll_zt": zt}, (mr, 16, 4, zt, 1))
+        wp, bp = packing.pack_conv3d_roll_bf16x3(m.conv, m.bn)
+        for k, x in enumerate(fam.members):
+            srcs = dev_srcs(fam, x)
+            with ctx:
+                got = launch(CC.VOL_KEYS[i][0], lambda: ops.conv3d_k3s1_roll(srcs, wp, bp, cout, relu=relu))
+            bounded("conv3d roll single, tile forms (bf16)", f"roll bf16 member {k}", got, _roll_interval(i, x, wf, shift, "bf16"))
+            same_bits(f"roll bf16 member {k}", got, launch(CC.VOL_KEYS[i][0], lambda: ops.conv3d_k3s1_roll(srcs, wp, bp, cout, relu=relu)))
+            left |= CB.escapes(got, *_roll_interval(i, x, wf, shift, "split"))
+    assert left, "the bf16 case stayed inside the split interval everywhere: the split kernel ran"
+
+
+@pytest.mark.parametrize("i,n,mr", CC.DECONV_CASES)
+def test_deconv3d_split_two_rows_per_wave_bounded(i, n, mr):
+    """deconv3d_s2_bf16x3 with 2 rows per wave (deconv_mr; the rule picks 1 on these maps): cout 8 with a skip on unaligned rows and cout
+    16, single and as sample batches of 3 (the batched kernel), bitwise the one-row form."""
+    from effi_mvs_plus_amd import ops
+    kind, cins, cout, stride, (D, h, w), relu, skip = CC.VOL_CASES[i]
+    fam = CC.vol_family(i)
+    m, wf, shift = _vol_module(i)
+    g = torch.Generator().manual_seed(i)
+    sk = torch.randn(cout, 2 * D, 2 * h, 2 * w, generator=g) if skip else None
+    row = "deconv3d_x3, two rows per wave"
+    members = fam.members
+    with precision_("split"), torch.no_grad():
+        ctx = reach(dict(launcher="deconv_x3", h=h, w=w, planes=D, cout=cout, count=n), {"deconv_mr": mr}, (mr, 16, 4, 1, 0))
+        for s0 in [min(s0, len(members) - n) for s0 in range(0, len(members), n)]:
+            xb = t(torch.stack(members[s0:s0 + n]), DEV)
+            kw = {} if sk is None else {"skip": t(sk, DEV) if n == 1 else t(torch.stack([sk] * n), DEV)}
+            with ctx:
+                gb = launch("deconv3d_x3", lambda: m.run(xb[0] if n == 1 else xb, **kw))
+            gb = gb[None] if n == 1 else gb
+            for j in range(n):
+                kw1 = {} if sk is None else {"skip": t(sk, DEV)}
+                bounded(row, f"{row}: case {i} member {s0 + j}", gb[j], _vol_interval(i, members[s0 + j], wf, shift, "split", sk))
+                same_bits(f"{row}: case {i} member {s0 + j}", gb[j], launch("deconv3d_x3", lambda: m.run(xb[j], **kw1)))
+
+
+@pytest.mark.parametrize("row,launcher,i,mode,n,form", CC.VOL_BATCH_CASES, ids=[f"{r.replace(' ', '_')}-case{i}-x{n}" for r, _, i, _, n, _ in CC.VOL_BATCH_CASES])
+def test_conv3d_batch_crosses_the_rule_threshold_bounded(row, launcher, i, mode, n, form):
+    """The 3-D rules without an option: the family of a VOL case, its members repeated in turn, as ONE sample batch large enough to
+    cross the rule's workgroup threshold (conv_cases.VOL_BATCH_CASES states each count beside its threshold).  Every member bounded,
+    bitwise the single launch (the rule's small-map form, asserted to differ) and bitwise its own repetitions."""
+    from effi_mvs_plus_amd import ops
+    kind, cins, cout, stride, dims, relu, skip = CC.VOL_CASES[i]
+    key = CC.VOL_KEYS[i][0 if mode == "split" else 1]
+    arith = mode if any(s_ in key for s_ in ("roll", "x3")) else "fp32"
+    fam = CC.vol_family(i)
+    m, wf, shift = _vol_module(i)
+    members = fam.members
+    xb = t(torch.stack([members[j % len(members)] for j in range(n)]), DEV)
+    trow = f"{key} ({mode}), sample batch of {n}"
+    with precision_(mode), torch.no_grad():
+        assert tuple(ops.launch_form(**CC.vol_query(launcher, i, 1))) != tuple(form)
+        with reach(CC.vol_query(launcher, i, n), {}, form):
+            gb = launch(key, lambda: m.run([xb]) if kind == "conv" else m.run(xb))
+        for j in range(n):
+            k = j % len(members)
+            if j == k:
+                x = members[k]
+                bounded(trow, f"{trow}: member {k}", gb[j], _vol_interval(i, x, wf, shift, arith, None), x if kind == "conv" else None, wf.shape,
+                        CB._tuple(stride, 3), 1, 3)
+                same_bits(f"{trow}: member {k}", gb[j], launch(key, lambda: m.run([xb[j]]) if kind == "conv" else m.run(xb[j])))
+            else:
+                same_bits(f"{trow}: sample {j}, a repetition of member {k}", gb[j], gb[k])
+
+
+@pytest.mark.parametrize("mode", ["fp32", "split"])
+@pytest.mark.parametrize("hw,n,form", CC.K5S2_FORM_CASES)
+def test_5x5_stride2_two_rows_per_wave_bounded(hw, n, form, mode):
+    """dispatch_k5s2 / launch_s2_x3 and their batched twins with 2 rows per wave: the narrowest maps that cross 512 (split: 400)
+    tiles -- one image of 17 x 8192, two of 17 x 4096 (each alone takes one row per wave: the form the batch is compared with)."""
+    from effi_mvs_plus_amd import ops, packing
+    (cin,), cout = CC.K5S2_FORM_CHANNELS
+    fam = CC.k5s2_form_family(hw)
+    fam.assert_full()
+    wt, b = CC.weights(cout, cin, 5, seed=4900 + hw[1], bias=True)
+    wp, bp = packing.pack_conv2d(wt.to(DEV), b.to(DEV))
+    launcher = "s2_x3" if mode == "split" else "k5s2"
+    key = f"conv2d_k5s2{'x3' if mode == 'split' else ''}_nt{(cout + 15) // 16}"
+    q = dict(launcher=launcher, h=(hw[0] - 1) // 2 + 1, w=(hw[1] - 1) // 2 + 1, nt=(cout + 15) // 16)
+    row = f"conv2d_k5s2 ({mode}), two rows per wave"
+    members = fam.members
+    iv = lambda x: CB.act_interval(*CB.conv_interval(x, None, wt, b, 2, 2, None, mode), "relu")          # noqa: E731
+    with precision_(mode), reach(dict(q, count=n), {}, form):
+        if n == 1:
+            for k, x in enumerate(members):
+                bounded(row, f"{row}: member {k}", launch(key, lambda: ops.conv2d_k5s2(t(x, DEV), wp, bp, cout, act=ops.ACT_RELU)), iv(x), x, wt.shape, 2, 2)
+            return
+        assert tuple(ops.launch_form(**dict(q, count=1))) == CC.MR1
+        for s0 in [min(s0, len(members) - n) for s0 in range(0, len(members), n)]:
+            xb = t(torch.stack(members[s0:s0 + n]), DEV)
+            gb = launch(key + "_batch", lambda: ops.conv2d_k5s2(xb, wp, bp, cout, act=ops.ACT_RELU))
+            for j in range(n):
+                bounded(row, f"{row}: member {s0 + j}", gb[j], iv(members[s0 + j]), members[s0 + j], wt.shape, 2, 2)
+                same_bits(f"{row}: member {s0 + j}", gb[j], launch(key, lambda: ops.conv2d_k5s2(xb[j], wp, bp, cout, act=ops.ACT_RELU)))
