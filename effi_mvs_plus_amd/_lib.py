@@ -27,6 +27,14 @@ SIGNATURES = {
     "effi_fusion_dtu_filter_scan_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "effi_fusion_dynamic_filter_scan_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp],
+    # the fixed-threshold visibility filter (misc/fusion.py:50-115)
+    "effi_fusion_static_filter_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp],
+    "effi_fusion_static_filter_scan_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _f, _d, _d, _d, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp],
+    "effi_fusion_project_img_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "effi_fusion_static_vis_filter_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp],
+    "effi_fusion_prob_filter_f32": [_vp, _l, _i, _l, _f, _i, _vp, _vp],
     "effi_fusion_compact_blocks": [_i, _i, _i],
     "effi_fusion_compact_scan_tile": [],
     "effi_fusion_compact_count_u8": [_vp, _i, _i, _i, _vp, _vp, _vp],

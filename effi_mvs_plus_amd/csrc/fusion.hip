@@ -249,6 +249,217 @@ __global__ __launch_bounds__(256) void fusion_dynamic_filter_scan_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
+// The FIXED-threshold visibility filter of the same module (Vis-MVSNet's): project_img, get_reproj, vis_filter, ave_fusion
+// (misc/fusion.py:50-65,79-115).  The reference first maps every SOURCE pixel q into the reference view, S(q) = (x, y of the image
+// point, z of the reference-camera point), then samples that [3,h,w] map at the reference pixel's projection into the source view
+// (project_img).  Here one thread per reference pixel evaluates S only at the four taps its sample touches, from the four source
+// depths, so the [v,3,h,w] map never exists.  The reference's oddities are kept: the projection is normalised by the size
+// (u / w * 2 - 1, not w - 1) and clamped to +-1.1 while grid_sample runs with align_corners=True, the centres are (x+0.5, y+0.5),
+// in_range does not enter vis_filter's result.
+
+// project_img's warp coordinate of one destination pixel (:53-63) and grid_sample's tap set-up (bilinear, zeros, align_corners=True)
+struct StaticTaps {
+    int x0, y0;
+    float nw, ne, sw, se;       // weights of (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1)
+    float in_range;             // 0/1 on the clamped coordinates (:62)
+};
+__device__ __forceinline__ StaticTaps fus_static_taps(const float* Md, const float* Ms, float u, float vv, float depth, int height,
+                                                      int width, int hs, int ws) {
+    const V4 cp = img2cam<true>(Md + 9, u, vv, depth);
+    const V4 world = xform<true>(Md + 34, cp);
+    const V4 c = xform<true>(Ms + 18, world);
+    const V3 im = cam2img<true>(Ms, c);
+    float gx = im.x / (float)width * 2.0f - 1.0f, gy = im.y / (float)height * 2.0f - 1.0f;     // :59-61
+    gx = gx < -1.1f ? -1.1f : (gx > 1.1f ? 1.1f : gx);
+    gy = gy < -1.1f ? -1.1f : (gy > 1.1f ? 1.1f : gy);
+    StaticTaps t;
+    t.in_range = (-1.0f <= gx && gx <= 1.0f && -1.0f <= gy && gy <= 1.0f) ? 1.0f : 0.0f;
+    const float ix = ((gx + 1.0f) / 2.0f) * (float)(ws - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(hs - 1);
+    const float fx = floorf(ix), fy = floorf(iy);
+    t.x0 = (fx == fx) ? (int)fx : -2;                                // a NaN coordinate touches no tap
+    t.y0 = (fy == fy) ? (int)fy : -2;
+    const float tx = ix - fx, ty = iy - fy;
+    t.nw = (1.0f - tx) * (1.0f - ty);
+    t.ne = tx * (1.0f - ty);
+    t.sw = (1.0f - tx) * ty;
+    t.se = tx * ty;
+    return t;
+}
+
+// S(q) of one source pixel (get_reproj, :87-91), zero outside the map as grid_sample's padding makes it.  Continuous outputs: the
+// reciprocal forms.
+__device__ __forceinline__ V3 fus_static_tap(const float* Mr, const float* Ms, const float* __restrict__ src, int h, int w, int yy, int xx) {
+    if (yy < 0 || yy >= h || xx < 0 || xx >= w) return {0.0f, 0.0f, 0.0f};
+    const V4 sc = img2cam<false>(Ms + 9, (float)xx + 0.5f, (float)yy + 0.5f, src[(long)yy * w + xx]);
+    const V4 sw = xform<false>(Ms + 34, sc);
+    const V4 rc = xform<false>(Mr + 18, sw);
+    const V3 ri = cam2img<false>(Mr, rc);
+    return {ri.x, ri.y, rc.z};
+}
+
+// vis_filter's two tests of one (view, pixel) (:102,105): thresholds are the fp32 roundings of 1/img_dist_thresh, 1/depth_thresh
+__device__ __forceinline__ float fus_static_test(float u, float vv, float dref, float x, float y, float d, float dist_thr, float depth_thr) {
+    const float dx = x - u, dy = y - vv;
+    const float dist = sqrtf(dx * dx + dy * dy), ddiff = fabsf(dref - d);
+    const bool m = (dist < dist_thr) & (ddiff < depth_thr);
+    return m ? 1.0f : 0.0f;
+}
+
+// The filter of ONE reference pixel p (pointers already the reference view's own, ``src_of(s)`` = depth map of its s-th source).
+template <class SrcOf>
+__device__ __forceinline__ void fusion_static_filter_pixel(
+    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
+    unsigned char* __restrict__ out_mask, float* __restrict__ out_points, float* __restrict__ out_xyd, float* __restrict__ out_in_range) {
+    const long hw = (long)h * w;
+    const int y = p / w, x = p - y * w;
+    const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
+    const float* Mr = mats;
+    const float dref = ref_depth[p];
+    float dsum = 0.0f, msum = 0.0f;
+    for (int s = 0; s < V; ++s) {
+        const float* Ms = mats + (long)(s + 1) * MAT_STRIDE;
+        const float* src = src_of(s);
+        const StaticTaps t = fus_static_taps(Mr, Ms, u, vv, dref, h, w, h, w);
+        const V3 a = fus_static_tap(Mr, Ms, src, h, w, t.y0, t.x0), b = fus_static_tap(Mr, Ms, src, h, w, t.y0, t.x0 + 1);
+        const V3 c = fus_static_tap(Mr, Ms, src, h, w, t.y0 + 1, t.x0), e = fus_static_tap(Mr, Ms, src, h, w, t.y0 + 1, t.x0 + 1);
+        const float rx = a.x * t.nw + b.x * t.ne + c.x * t.sw + e.x * t.se;
+        const float ry = a.y * t.nw + b.y * t.ne + c.y * t.sw + e.y * t.se;
+        const float rd = a.z * t.nw + b.z * t.ne + c.z * t.sw + e.z * t.se;
+        if (out_xyd) {
+            out_xyd[((long)s * 3 + 0) * hw + p] = rx;
+            out_xyd[((long)s * 3 + 1) * hw + p] = ry;
+            out_xyd[((long)s * 3 + 2) * hw + p] = rd;
+        }
+        if (out_in_range) out_in_range[(long)s * hw + p] = t.in_range;
+        const float m = fus_static_test(u, vv, dref, rx, ry, rd, dist_thr, depth_thr);
+        dsum = dsum + rd * m;                                       // ave_fusion (:114): the product, in view order
+        msum = msum + m;
+    }
+    const float davg = (dsum + dref) / (msum + 1.0f);
+    const bool geo = msum >= count_thr;                             // :109, count_thr = (float)(vthresh - 1.1)
+    bool pm = true;
+    if (conf) {                                                     // F.interpolate(nearest) of the confidence, test_tank.py:471-473
+        const int sy = min((int)floorf((float)y * ((float)ch / (float)h)), ch - 1);
+        const int sx = min((int)floorf((float)x * ((float)cw / (float)w)), cw - 1);
+        pm = conf[(long)sy * cw + sx] > prob_thr;
+    }
+    out_depth[p] = davg;
+    if (out_geo) out_geo[p] = geo ? 1 : 0;
+    if (out_prob) out_prob[p] = pm ? 1 : 0;
+    if (out_mask) out_mask[p] = (geo & pm) ? 1 : 0;
+    if (out_points) {                                               // test_tank.py:513-515
+        const V4 pc = img2cam<true>(Mr + 9, u, vv, davg);
+        const V4 pw = xform<true>(Mr + 34, pc);
+        out_points[p] = pw.x;
+        out_points[hw + p] = pw.y;
+        out_points[2 * hw + p] = pw.z;
+    }
+}
+
+__global__ __launch_bounds__(256) void fusion_static_filter_kernel(
+    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
+    unsigned char* __restrict__ out_mask, float* __restrict__ out_points, float* __restrict__ out_xyd, float* __restrict__ out_in_range) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    fusion_static_filter_pixel(p, ref_depth, [=](int s) { return src_depths + (long)s * hw; }, V, h, w, mats, conf, ch, cw, prob_thr,
+                               dist_thr, depth_thr, count_thr, out_depth, out_geo, out_prob, out_mask, out_points, out_xyd, out_in_range);
+}
+
+// Scan launch: grid, table and layouts as fusion_dynamic_filter_scan_kernel.
+__global__ __launch_bounds__(256) void fusion_static_filter_scan_kernel(
+    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
+    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
+    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
+    unsigned char* __restrict__ out_mask, float* __restrict__ out_points) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    const int r = blockIdx.y;
+    const int* row = table + (long)r * (v_max + 1);
+    const int V = fus_row_sources(row, v_max);
+    fusion_static_filter_pixel(p, depths + (long)row[0] * hw, [=](int s) { return depths + (long)row[1 + s] * hw; }, V, h, w,
+                               mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + (long)r * ch * cw : nullptr, ch, cw, prob_thr,
+                               dist_thr, depth_thr, count_thr, out_depth + r * hw, out_geo ? out_geo + r * hw : nullptr,
+                               out_prob ? out_prob + r * hw : nullptr, out_mask ? out_mask + r * hw : nullptr,
+                               out_points ? out_points + 3 * r * hw : nullptr, nullptr, nullptr);
+}
+
+// mats [n][2][52]: slot 2b = destination camera b, slot 2b + 1 = source camera b
+__global__ void fusion_prepare_pairs_kernel(const float* __restrict__ dst_cams, const float* __restrict__ src_cams, int n,
+                                            float* __restrict__ mats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * n) return;
+    fus_prepare_view(((i & 1) ? src_cams : dst_cams) + (long)(i >> 1) * 32, mats + (long)i * MAT_STRIDE);
+}
+
+// project_img (:50-65) for any channel count: blockIdx.y = batch element, mats [n][2][52] = destination camera, source camera.
+// src_img [n][C][hs][ws], dst_depth [n][height][width] -> out [n][C][height][width], in_range [n][height][width]; the weights are
+// computed once, the channels loop over them.
+__global__ __launch_bounds__(256) void fusion_project_img_kernel(const float* __restrict__ src_img, const float* __restrict__ dst_depth,
+                                                                 const float* __restrict__ mats, int C, int hs, int ws, int height,
+                                                                 int width, float* __restrict__ out, float* __restrict__ in_range) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)height * width, shw = (long)hs * ws;
+    if (p >= hw) return;
+    const int b = blockIdx.y;
+    const int y = p / width, x = p - y * width;
+    const float* Md = mats + (long)b * 2 * MAT_STRIDE;
+    const StaticTaps t = fus_static_taps(Md, Md + MAT_STRIDE, (float)x + 0.5f, (float)y + 0.5f, dst_depth[b * hw + p], height, width, hs, ws);
+    if (in_range) in_range[b * hw + p] = t.in_range;
+    const bool x0in = t.x0 >= 0 && t.x0 < ws, x1in = t.x0 + 1 >= 0 && t.x0 + 1 < ws;
+    const bool y0in = t.y0 >= 0 && t.y0 < hs, y1in = t.y0 + 1 >= 0 && t.y0 + 1 < hs;
+    const long o00 = (long)t.y0 * ws + t.x0;
+    for (int c = 0; c < C; ++c) {
+        const float* img = src_img + ((long)b * C + c) * shw;
+        const float a = (y0in && x0in) ? img[o00] : 0.0f, bb = (y0in && x1in) ? img[o00 + 1] : 0.0f;
+        const float cc = (y1in && x0in) ? img[o00 + ws] : 0.0f, e = (y1in && x1in) ? img[o00 + ws + 1] : 0.0f;
+        out[((long)b * C + c) * hw + p] = a * t.nw + bb * t.ne + cc * t.sw + e * t.se;
+    }
+}
+
+// vis_filter (:99-110) and ave_fusion (:113-115) on a GIVEN reproj_xyd [n][V][3][h][w], blockIdx.y = batch element: per pixel the
+// loop over the views.  masks_in != NULL: ave_fusion with the caller's masks [n][V][h][w] (any values: the product is formed);
+// otherwise the masks are vis_filter's and go to masks_out (0/1 floats) / mask_out (bytes) when asked for.
+__global__ __launch_bounds__(256) void fusion_static_vis_kernel(const float* __restrict__ ref_depth, const float* __restrict__ xyd,
+                                                                const float* __restrict__ masks_in, int V, int h, int w, float dist_thr,
+                                                                float depth_thr, float count_thr, float* __restrict__ masks_out,
+                                                                unsigned char* __restrict__ mask_out, float* __restrict__ ave_out) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    const int b = blockIdx.y;
+    const int y = p / w, x = p - y * w;
+    const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
+    const float dref = ref_depth[b * hw + p];
+    float dsum = 0.0f, msum = 0.0f;
+    for (int s = 0; s < V; ++s) {
+        const float* q = xyd + ((long)b * V + s) * 3 * hw + p;
+        const float rd = q[2 * hw];
+        const float m = masks_in ? masks_in[((long)b * V + s) * hw + p] : fus_static_test(u, vv, dref, q[0], q[hw], rd, dist_thr, depth_thr);
+        if (masks_out) masks_out[((long)b * V + s) * hw + p] = m;
+        dsum = dsum + rd * m;
+        msum = msum + m;
+    }
+    if (mask_out) mask_out[b * hw + p] = (msum >= count_thr) ? 1 : 0;
+    if (ave_out) ave_out[b * hw + p] = (dsum + dref) / (msum + 1.0f);
+}
+
+// prob_filter (:68-76), one channel per launch: mask = (first ? 1 : mask) & (prob > thr); prob of batch element b at b * bstride
+__global__ __launch_bounds__(256) void fusion_prob_filter_kernel(const float* __restrict__ prob, long bstride, long hw, float thr, int first,
+                                                                 unsigned char* __restrict__ mask) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= hw) return;
+    const int b = blockIdx.y;
+    const unsigned char m = prob[b * bstride + p] > thr ? 1 : 0;
+    mask[b * hw + p] = first ? m : (mask[b * hw + p] & m);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
 // DTU branch of row n3: reproject_with_depth + check_geometric_consistency + the array part of filter_depth of the reference's
 // test_dtu_dypcd.py:164-333 (the numpy / cv2 filter its DTU driver runs per scan on the host, in a multiprocessing pool), one thread
 // per reference pixel walking the source views.  Differences from the Tanks-and-Temples kernel above that matter for parity: pixel
@@ -854,6 +1065,103 @@ extern "C" int effi_fusion_dynamic_filter_f32(const float* ref_depth, const floa
     hipLaunchKernelGGL(fusion_dynamic_filter_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depths,
                        n_src, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dh_view_num, dist_base, rel_diff_base,
                        relative, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points, out_reproj_xyd);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+// ---- the fixed-threshold visibility filter (misc/fusion.py:50-115) ----
+static int fus_static_thresholds(double img_dist_thresh, double depth_thresh, double vthresh, float* dist_thr, float* depth_thr,
+                                 float* count_thr) {
+    if (!(img_dist_thresh > 0.0) || !(depth_thresh > 0.0) || !(vthresh == vthresh)) return EFFI_ERR_BADARG;
+    *dist_thr = (float)(1.0 / img_dist_thresh);                      // formed in double, compared as its fp32 rounding
+    *depth_thr = (float)(1.0 / depth_thresh);
+    *count_thr = (float)(vthresh - 1.1);
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_static_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams,
+                                             int n_src, int h, int w, const float* ref_conf, int conf_h, int conf_w, float prob_threshold,
+                                             double img_dist_thresh, double depth_thresh, double vthresh, float* mats_scratch,
+                                             float* out_depth, unsigned char* out_geo_mask, unsigned char* out_prob_mask,
+                                             unsigned char* out_mask, float* out_points, float* out_reproj_xyd, float* out_in_range,
+                                             effi_stream_t stream) {
+    if (!ref_depth || !src_depths || !ref_cam || !src_cams || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
+    if (n_src < 1 || h < 2 || w < 2 || (long)h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    if (n_src > FUS_MAX_VIEWS) return EFFI_ERR_UNSUPPORTED;
+    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
+    float dist_thr, depth_thr, count_thr;
+    if (fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &dist_thr, &depth_thr, &count_thr) != EFFI_OK) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_prepare_kernel, dim3(1), dim3(64), 0, st, ref_cam, src_cams, n_src, mats_scratch);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_static_filter_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depths, n_src, h, w,
+                       mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dist_thr, depth_thr, count_thr, out_depth, out_geo_mask,
+                       out_prob_mask, out_mask, out_points, out_reproj_xyd, out_in_range);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_static_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                                  const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf,
+                                                  int conf_h, int conf_w, float prob_threshold, double img_dist_thresh, double depth_thresh,
+                                                  double vthresh, float* mats_scratch, float* out_depth, unsigned char* out_geo_mask,
+                                                  unsigned char* out_prob_mask, unsigned char* out_mask, float* out_points,
+                                                  effi_stream_t stream) {
+    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
+    if (h < 2 || w < 2) return EFFI_ERR_BADARG;
+    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
+    float dist_thr, depth_thr, count_thr;
+    if (fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &dist_thr, &depth_thr, &count_thr) != EFFI_OK) return EFFI_ERR_BADARG;
+    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, 1) != EFFI_OK) return EFFI_ERR_BADARG;
+    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table, n_ref,
+                       v_max, mats_scratch);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_static_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table,
+                       v_max, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dist_thr, depth_thr, count_thr, out_depth,
+                       out_geo_mask, out_prob_mask, out_mask, out_points);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_project_img_f32(const float* src_img, const float* dst_depth, const float* src_cams, const float* dst_cams,
+                                           int n, int channels, int src_h, int src_w, int height, int width, float* mats_scratch,
+                                           float* out_img, float* out_in_range, effi_stream_t stream) {
+    if (!src_img || !dst_depth || !src_cams || !dst_cams || !mats_scratch || !out_img) return EFFI_ERR_BADARG;
+    if (n < 1 || n > 65535 || channels < 1 || src_h < 1 || src_w < 1 || height < 1 || width < 1) return EFFI_ERR_BADARG;
+    if ((long)n * channels * height * width >= (1L << 31) || (long)n * channels * src_h * src_w >= (1L << 31)) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_prepare_pairs_kernel, dim3(effi_cdiv(2L * n, 64)), dim3(64), 0, st, dst_cams, src_cams, n, mats_scratch);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fusion_project_img_kernel, dim3(effi_cdiv((long)height * width, 256), n), dim3(256), 0, st, src_img, dst_depth,
+                       mats_scratch, channels, src_h, src_w, height, width, out_img, out_in_range);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_static_vis_filter_f32(const float* ref_depth, const float* reproj_xyd, const float* masks_in, int n, int n_src,
+                                                 int h, int w, double img_dist_thresh, double depth_thresh, double vthresh,
+                                                 float* masks_out, unsigned char* mask_out, float* ave_out, effi_stream_t stream) {
+    if (!ref_depth || !reproj_xyd || n < 1 || n > 65535 || n_src < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    if (!masks_out && !mask_out && !ave_out) return EFFI_ERR_BADARG;
+    if ((long)n * n_src * 3 * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
+    float dist_thr = 0.0f, depth_thr = 0.0f, count_thr = 0.0f;
+    if (!masks_in && fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &dist_thr, &depth_thr, &count_thr) != EFFI_OK)
+        return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_static_vis_kernel, dim3(effi_cdiv((long)h * w, 256), n), dim3(256), 0, st, ref_depth, reproj_xyd, masks_in,
+                       n_src, h, w, dist_thr, depth_thr, count_thr, masks_out, mask_out, ave_out);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_fusion_prob_filter_f32(const float* prob, long batch_stride, int n, long hw, float threshold, int first,
+                                           unsigned char* mask, effi_stream_t stream) {
+    if (!prob || !mask || n < 1 || n > 65535 || hw < 1 || hw >= (1L << 31) || batch_stride < hw) return EFFI_ERR_BADARG;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(fusion_prob_filter_kernel, dim3(effi_cdiv(hw, 256), n), dim3(256), 0, st, prob, batch_stride, hw, threshold, first,
+                       mask);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }

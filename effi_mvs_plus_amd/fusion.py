@@ -6,6 +6,14 @@
 as ONE fused kernel per reference view (no ``[n,v,3,h,w]`` intermediates), what bench.py times.  ``dynamic_filter_scan`` is the
 driver's whole loop over a scan's reference views -- depth maps of a scan in, point cloud out -- in scan-batched launches with the
 survivors compacted on the device.  CUDA (ROCm) fp32 tensors only; no CPU fallback.
+
+The module's other filter, the FIXED-threshold visibility fusion of Vis-MVSNet (``misc/fusion.py:50-115``), is here under the
+reference's names and signatures too: ``project_img``, ``prob_filter``, ``get_reproj``, ``vis_filter``, ``ave_fusion``.
+``static_filter`` is their composition as ONE fused kernel per reference view and ``static_filter_scan`` the scan-level form
+(depth maps of a scan in, point cloud out), the twins of ``dynamic_filter`` / ``dynamic_filter_scan``.
+
+Not mirrored: ``vis_filter_dynamic_open3d``, ``filter_depth``, ``generate_points_from_depth`` and ``homo_warping``
+(``misc/fusion.py:185-311``).  ``filter_depth`` ends without a ``return``, so that family cannot run in the reference either.
 """
 from __future__ import annotations
 
@@ -107,6 +115,65 @@ def dynamic_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_thre
     return out
 
 
+@ops.on_tensor_device
+def project_img(src_img, dst_depth, src_cam, dst_cam, height=None, width=None):  # nchw, n1hw -> nchw, n1hw
+    """misc/fusion.py:50-65 -> (warped_img [n,c,height,width], in_range [n,1,height,width] as 0/1 in the image's dtype): the source
+    image sampled (bilinear, zeros, align_corners=True) where the destination pixels of depth ``dst_depth`` fall in the source view.
+    The projection is normalised by ``width`` / ``height`` (not minus one) and clamped to +-1.1, as the reference does."""
+    return ops.fusion_project_img(src_img.contiguous(), dst_depth.contiguous(), src_cam.contiguous(), dst_cam.contiguous(), height, width)
+
+
+@ops.on_tensor_device
+def prob_filter(ref_prob, prob_thresh, greater=True):  # n31hw -> n1hw
+    """misc/fusion.py:68-76: the AND over the channels of ``ref_prob[:, [i]] > prob_thresh[i]`` -> bool [n,1,1,h,w] for ref_prob
+    [n,c,1,h,w].  ``greater`` is accepted and ignored, as in the reference."""
+    mask = ops.fusion_prob_filter(ref_prob.contiguous(), prob_thresh)
+    return None if mask is None else mask.bool()
+
+
+@ops.on_tensor_device
+def get_reproj(ref_depth, srcs_depth, ref_cam, srcs_cam):  # n1hw, nv1hw -> n1hw
+    """misc/fusion.py:79-96 -> (reproj_xyd [n,v,3,h,w], in_range [n,v,1,h,w]): per reference pixel and source view, the source
+    view's pixels mapped into the reference view (x, y, depth), sampled at the reference pixel's projection.  The by-products of the
+    fused kernel (``ops.fusion_static_filter``), one launch per sample."""
+    n, v, _, h, w = srcs_depth.shape
+    xyd, rng = [], []
+    for b in range(n):
+        r = ops.fusion_static_filter(ref_depth[b, 0].contiguous(), srcs_depth[b, :, 0].contiguous(), ref_cam[b].contiguous(),
+                                     srcs_cam[b].contiguous(), want_points=False, want_reproj=True)
+        xyd.append(r["reproj_xyd"]), rng.append(r["in_range"])
+    return torch.stack(xyd), torch.stack(rng).unsqueeze(2)
+
+
+@ops.on_tensor_device
+def vis_filter(ref_depth, reproj_xyd, in_range, img_dist_thresh, depth_thresh, vthresh):
+    """misc/fusion.py:99-110 -> (masks [n,v,1,h,w] 0/1 in ref_depth's dtype, mask [n,1,h,w] bool = sum_v masks >= vthresh - 1.1).
+    ``in_range`` is accepted and, as in the reference (:106 overwrites it with ones), does not enter the result."""
+    masks, mask = ops.fusion_static_vis_filter(ref_depth.contiguous(), reproj_xyd.contiguous(), img_dist_thresh, depth_thresh, vthresh)
+    return masks, mask.bool()
+
+
+@ops.on_tensor_device
+def ave_fusion(ref_depth, reproj_xyd, masks):
+    """misc/fusion.py:113-115 -> [n,1,h,w]: (sum_v d * masks + ref_depth) / (sum_v masks + 1)."""
+    return ops.fusion_static_ave(ref_depth.contiguous(), reproj_xyd.contiguous(), masks.to(ref_depth.dtype).contiguous())
+
+
+@ops.on_tensor_device
+def static_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh):
+    """``get_reproj`` + ``vis_filter`` + ``ave_fusion`` with the driver's photometric mask and points (test_tank.py:471-475,512-515)
+    for a batch of reference views as ONE kernel each; shapes as ``dynamic_filter``, ref_conf [n,H,W] or None
+    -> dict(depth [n,1,h,w] = ave_fusion, geo_mask = vis_filter's mask, prob_mask, mask = their AND [n,1,h,w] bool, points [n,3,h,w])."""
+    n = ref_depth.shape[0]
+    res = [ops.fusion_static_filter(ref_depth[b, 0].contiguous(), src_depths[b, :, 0].contiguous(), ref_cam[b].contiguous(),
+                                    src_cams[b].contiguous(), None if ref_conf is None else ref_conf[b].contiguous(), prob_threshold,
+                                    img_dist_thresh, depth_thresh, vthresh) for b in range(n)]
+    out = {"depth": torch.stack([r["depth"] for r in res]).unsqueeze(1), "points": torch.stack([r["points"] for r in res])}
+    for k in ("geo_mask", "prob_mask", "mask"):
+        out[k] = torch.stack([r[k] for r in res]).unsqueeze(1).bool()
+    return out
+
+
 def pair_table(pair_data):
     """Host only: the ``read_pair_file`` list [(ref_view, [src_views...]), ...] -> int32 CPU tensor [n_ref, 1 + v_max] (reference id,
     source ids, -1 padding), the table the scan launches index a scan's depth maps and cameras with."""
@@ -162,6 +229,39 @@ def dynamic_filter_scan(depths, confidences, cams, images, pair_data, prob_thres
     def filter_chunk(t_, r0, r1):
         conf = None if confidences is None else confidences[t_[:, 0].long().to(dev)].contiguous()
         return ops.fusion_dynamic_filter_scan(depths, cams, t_, conf, prob_threshold, dh_view_num, dist_filter, depth_filter, relative)
+
+    out = fuse_chunks(table, filter_chunk, images, "chw", chunk, ("depth", "prob_mask", "geo_mask", "mask"))
+    for k in ("prob_mask", "geo_mask", "mask"):
+        out[k] = out[k].bool()
+    out["ref_ids"] = [ref for ref, _ in rows]
+    return out
+
+
+def static_scan_rows(pair_data):
+    """Host only: the rows of a ``read_pair_file`` list the fixed-threshold filter keeps -- a reference view without a source has
+    nothing to be checked against and contributes nothing."""
+    return [(ref, list(srcs)) for ref, srcs in pair_data if len(srcs) >= 1]
+
+
+@ops.on_tensor_device
+def static_filter_scan(depths, confidences, cams, images, pair_data, prob_threshold=0.3, img_dist_thresh=1.0, depth_thresh=0.01,
+                       vthresh=4, chunk=None):
+    """``static_filter`` over a scan's reference views, from the maps on the device to the fused point cloud; arguments, chunking and
+    result as ``dynamic_filter_scan``.  Reference views without a source are dropped; ``ref_ids`` lists the ones that remain."""
+    rows = static_scan_rows(pair_data)
+    dev = depths.device
+    if not rows:
+        h, w = depths.shape[-2:]
+        z = lambda *sh, dt=torch.float32: torch.empty(*sh, device=dev, dtype=dt)
+        return {"xyz": z(0, 3), "rgb": z(0, 3, dt=torch.uint8), "offsets": torch.zeros(1, dtype=torch.int32, device=dev), "ref_ids": [],
+                "depth": z(0, h, w), "prob_mask": z(0, h, w, dt=torch.bool), "geo_mask": z(0, h, w, dt=torch.bool),
+                "mask": z(0, h, w, dt=torch.bool)}
+    table = pair_table(rows)
+    depths, cams, images = depths.contiguous(), cams.contiguous(), images.contiguous()
+
+    def filter_chunk(t_, r0, r1):
+        conf = None if confidences is None else confidences[t_[:, 0].long().to(dev)].contiguous()
+        return ops.fusion_static_filter_scan(depths, cams, t_, conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh)
 
     out = fuse_chunks(table, filter_chunk, images, "chw", chunk, ("depth", "prob_mask", "geo_mask", "mask"))
     for k in ("prob_mask", "geo_mask", "mask"):

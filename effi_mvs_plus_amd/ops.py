@@ -1153,6 +1153,137 @@ def fusion_dynamic_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshol
     return out
 
 
+def fusion_static_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf=None, prob_threshold=0.0, img_dist_thresh=1.0,
+                         depth_thresh=0.01, vthresh=4, want_points=True, want_reproj=False):
+    """Scope row n3, the fixed-threshold visibility filter: get_reproj + vis_filter + ave_fusion (misc/fusion.py:79-115) and the
+    driver's masks and points (test_tank.py:471-475,512-515) for one reference view in ONE kernel.  Arguments and result as
+    ``fusion_dynamic_filter``; with ``want_reproj`` also ``in_range`` [V,h,w] (0/1 floats), get_reproj's second result."""
+    for name, t_ in (("ref_depth", ref_depth), ("src_depths", src_depths), ("ref_cam", ref_cam), ("src_cams", src_cams)):
+        _t(t_, name)
+    if src_depths.dim() != 3:
+        raise ValueError("fusion_static_filter: src_depths [V,h,w] expected")
+    V, h, w = src_depths.shape
+    dev = ref_depth.device
+    if tuple(ref_depth.shape) != (h, w) or tuple(ref_cam.shape) != (2, 4, 4) or tuple(src_cams.shape) != (V, 2, 4, 4):
+        raise ValueError("fusion_static_filter: ref_depth [h,w], src_depths [V,h,w], ref_cam [2,4,4], src_cams [V,2,4,4]")
+    ch = cw = 0
+    if ref_conf is not None:
+        _t(ref_conf, "ref_conf")
+        ch, cw = ref_conf.shape
+    out = {"depth": torch.empty(h, w, device=dev, dtype=torch.float32),
+           "geo_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
+           "prob_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
+           "mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
+           "points": torch.empty(3, h, w, device=dev, dtype=torch.float32) if want_points else None,
+           "reproj_xyd": torch.empty(V, 3, h, w, device=dev, dtype=torch.float32) if want_reproj else None,
+           "in_range": torch.empty(V, h, w, device=dev, dtype=torch.float32) if want_reproj else None}
+    scratch = torch.empty(52 * (V + 1), device=dev, dtype=torch.float32)
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (1 + V + 1 + (3 if want_points else 0) + (4 * V if want_reproj else 0)) + 3.0 * h * w}
+    check(_call("fusion_static_filter", work, _lib.lib().effi_fusion_static_filter_f32, _p(ref_depth), _p(src_depths), _p(ref_cam),
+                _p(src_cams), V, h, w, _p(ref_conf), ch, cw, float(prob_threshold), float(img_dist_thresh), float(depth_thresh),
+                float(vthresh), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]), _p(out["prob_mask"]), _p(out["mask"]),
+                _p(out["points"]), _p(out["reproj_xyd"]), _p(out["in_range"]), _stream()), "effi_fusion_static_filter_f32")
+    return out
+
+
+def fusion_static_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshold=0.0, img_dist_thresh=1.0, depth_thresh=0.01, vthresh=4,
+                              want_points=True):
+    """``fusion_static_filter`` for every reference view of a scan in ONE launch; arguments and result as
+    ``fusion_dynamic_filter_scan``.  Every row needs at least one source; row r is bitwise the single-view launch."""
+    pairs, pairs_dev = _scan_inputs("fusion_static_filter_scan", depths, cams, pairs)
+    n_views, h, w = depths.shape
+    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
+    dev = depths.device
+    ch = cw = 0
+    if ref_conf is not None:
+        _t(ref_conf, "ref_conf")
+        if ref_conf.dim() != 3 or ref_conf.shape[0] != n_ref:
+            raise ValueError(f"fusion_static_filter_scan: ref_conf [n_ref,ch,cw] expected, got {tuple(ref_conf.shape)}")
+        ch, cw = ref_conf.shape[1:]
+    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
+           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "prob_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
+           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
+    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
+    n_src = int((pairs[:, 1:] >= 0).sum())
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (2 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
+    check(_call("fusion_static_filter_scan", work, _lib.lib().effi_fusion_static_filter_scan_f32, _p(depths), _p(cams), n_views, _p(pairs),
+                _p(pairs_dev), n_ref, v_max, h, w, _p(ref_conf), ch, cw, float(prob_threshold), float(img_dist_thresh),
+                float(depth_thresh), float(vthresh), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]), _p(out["prob_mask"]),
+                _p(out["mask"]), _p(out["points"]), _stream()), "effi_fusion_static_filter_scan_f32")
+    return out
+
+
+def fusion_project_img(src_img, dst_depth, src_cam, dst_cam, height=None, width=None):
+    """misc/fusion.py:50-65: src_img [N,C,hs,ws], dst_depth [N,1,height,width], cameras [N,2,4,4] -> (warped [N,C,height,width],
+    in_range [N,1,height,width] 0/1 floats).  ``height`` / ``width`` default to the source's size, as in the reference."""
+    for name, t_ in (("src_img", src_img), ("dst_depth", dst_depth), ("src_cam", src_cam), ("dst_cam", dst_cam)):
+        _t(t_, name)
+    if src_img.dim() != 4:
+        raise ValueError("fusion_project_img: src_img [N,C,hs,ws] expected")
+    n, c, hs, ws = src_img.shape
+    height, width = int(hs if height is None else height), int(ws if width is None else width)
+    if tuple(dst_depth.shape) != (n, 1, height, width) or tuple(src_cam.shape) != (n, 2, 4, 4) or tuple(dst_cam.shape) != (n, 2, 4, 4):
+        raise ValueError(f"fusion_project_img: dst_depth [N,1,height,width] = {(n, 1, height, width)} and cameras [N,2,4,4] expected, got "
+                         f"{tuple(dst_depth.shape)} / {tuple(src_cam.shape)} / {tuple(dst_cam.shape)}")
+    dev = src_img.device
+    out = torch.empty(n, c, height, width, device=dev, dtype=torch.float32)
+    in_range = torch.empty(n, 1, height, width, device=dev, dtype=torch.float32)
+    scratch = torch.empty(104 * n, device=dev, dtype=torch.float32)
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * n * height * width * (2 + 5 * c)}
+    check(_call("fusion_project_img", work, _lib.lib().effi_fusion_project_img_f32, _p(src_img), _p(dst_depth), _p(src_cam), _p(dst_cam), n,
+                c, hs, ws, height, width, _p(scratch), _p(out), _p(in_range), _stream()), "effi_fusion_project_img_f32")
+    return out, in_range
+
+
+def fusion_static_vis_filter(ref_depth, reproj_xyd, img_dist_thresh, depth_thresh, vthresh):
+    """misc/fusion.py:99-110: ref_depth [n,1,h,w], reproj_xyd [n,v,3,h,w] -> (masks [n,v,1,h,w] 0/1 floats, mask [n,1,h,w] uint8)."""
+    _t(ref_depth, "ref_depth"), _t(reproj_xyd, "reproj_xyd")
+    if reproj_xyd.dim() != 5 or reproj_xyd.shape[2] != 3 or tuple(ref_depth.shape) != (reproj_xyd.shape[0], 1) + tuple(reproj_xyd.shape[3:]):
+        raise ValueError("fusion_static_vis_filter: ref_depth [n,1,h,w], reproj_xyd [n,v,3,h,w]")
+    n, v, _, h, w = reproj_xyd.shape
+    masks = torch.empty(n, v, 1, h, w, device=ref_depth.device, dtype=torch.float32)
+    mask = torch.empty(n, 1, h, w, device=ref_depth.device, dtype=torch.uint8)
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * n * h * w * (1 + 4 * v) + 1.0 * n * h * w}
+    check(_call("fusion_static_vis_filter", work, _lib.lib().effi_fusion_static_vis_filter_f32, _p(ref_depth), _p(reproj_xyd), _p(None), n,
+                v, h, w, float(img_dist_thresh), float(depth_thresh), float(vthresh), _p(masks), _p(mask), _p(None), _stream()),
+          "effi_fusion_static_vis_filter_f32")
+    return masks, mask
+
+
+def fusion_static_ave(ref_depth, reproj_xyd, masks):
+    """misc/fusion.py:113-115: (sum_v d * masks + ref_depth) / (sum_v masks + 1) -> [n,1,h,w]; masks [n,v,1,h,w] fp32."""
+    _t(ref_depth, "ref_depth"), _t(reproj_xyd, "reproj_xyd"), _t(masks, "masks")
+    if reproj_xyd.dim() != 5 or reproj_xyd.shape[2] != 3 or tuple(ref_depth.shape) != (reproj_xyd.shape[0], 1) + tuple(reproj_xyd.shape[3:]) \
+            or tuple(masks.shape) != tuple(reproj_xyd.shape[:2]) + (1,) + tuple(reproj_xyd.shape[3:]):
+        raise ValueError("fusion_static_ave: ref_depth [n,1,h,w], reproj_xyd [n,v,3,h,w], masks [n,v,1,h,w]")
+    n, v, _, h, w = reproj_xyd.shape
+    ave = torch.empty(n, 1, h, w, device=ref_depth.device, dtype=torch.float32)
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * n * h * w * (2 + 2 * v)}
+    check(_call("fusion_static_ave", work, _lib.lib().effi_fusion_static_vis_filter_f32, _p(ref_depth), _p(reproj_xyd), _p(masks), n, v, h,
+                w, 1.0, 1.0, 0.0, _p(None), _p(None), _p(ave), _stream()), "effi_fusion_static_vis_filter_f32")
+    return ave
+
+
+def fusion_prob_filter(ref_prob, prob_thresh):
+    """misc/fusion.py:68-76: ref_prob [n,c,1,h,w], one threshold per leading channel -> [n,1,1,h,w] uint8, the AND of
+    ``ref_prob[:, [i]] > prob_thresh[i]``; no threshold -> None, as the reference."""
+    _t(ref_prob, "ref_prob")
+    thr = [float(p) for p in prob_thresh]
+    if ref_prob.dim() < 2 or len(thr) > ref_prob.shape[1]:
+        raise ValueError(f"fusion_prob_filter: {len(thr)} thresholds for ref_prob {tuple(ref_prob.shape)}")
+    if not thr:
+        return None
+    n, c = ref_prob.shape[:2]
+    hw = ref_prob[0, 0].numel()
+    mask = torch.empty((n, 1) + tuple(ref_prob.shape[2:]), device=ref_prob.device, dtype=torch.uint8)
+    for i, p in enumerate(thr):
+        check(_lib.lib().effi_fusion_prob_filter_f32(C.c_void_p(ref_prob.data_ptr() + 4 * i * hw), c * hw, n, hw, p, int(i == 0), _p(mask),
+                                                     _stream()), "effi_fusion_prob_filter_f32")
+    return mask
+
+
 def fusion_compact(mask, points, images, layout="hwc", pairs=None):
     """The survivors of a scan as vertex arrays in the reference's order (test_dtu_dypcd.py:327-333, test_tank.py:517-533: boolean
     indexing view by view, then np.concatenate) without leaving the device and without atomics.  mask [n_ref,h,w] uint8; points

@@ -886,6 +886,44 @@ int effi_fusion_dynamic_filter_scan_f32(const float* depths, const float* cams, 
                                         int relative, float* mats_scratch, float* out_depth, unsigned char* out_geo_mask,
                                         unsigned char* out_prob_mask, unsigned char* out_mask, float* out_points, effi_stream_t stream);
 
+/* ---- n3, the FIXED-threshold visibility filter of the same module (Vis-MVSNet's): get_reproj + vis_filter + ave_fusion
+ * (misc/fusion.py:79-115, through project_img :50-65) for one reference view in ONE kernel, with the photometric mask, the final
+ * mask and the world points the T&T driver adds (test_tank.py:471-475,512-515).  Arguments as effi_fusion_dynamic_filter_f32.  Per
+ * reference pixel and source: the projection into the source view (pixel centres x+0.5, normalised u / w * 2 - 1, clamped to +-1.1),
+ * grid_sample's four taps (bilinear, zeros, align_corners=True), each tap's source pixel mapped into the reference view from its own
+ * depth -- the reference's [n_src][3][h][w] map is never stored.  A view counts where |(x, y) - centre| < (float)(1 / img_dist_thresh)
+ * and |d_ref - d| < (float)(1 / depth_thresh); out_geo_mask = count >= (float)(vthresh - 1.1); out_depth = (sum d*m + d_ref) /
+ * (count + 1).  out_reproj_xyd [n_src][3][h][w] and out_in_range [n_src][h][w] (0/1 floats; it does not enter the masks, :106) are
+ * get_reproj's two results, or NULL.  img_dist_thresh, depth_thresh > 0; n_src <= 16 (else EFFI_ERR_UNSUPPORTED). */
+int effi_fusion_static_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams, int n_src,
+                                  int h, int w, const float* ref_conf, int conf_h, int conf_w, float prob_threshold,
+                                  double img_dist_thresh, double depth_thresh, double vthresh, float* mats_scratch, float* out_depth,
+                                  unsigned char* out_geo_mask, unsigned char* out_prob_mask, unsigned char* out_mask, float* out_points,
+                                  float* out_reproj_xyd, float* out_in_range, effi_stream_t stream);
+/* The same for every reference view of a scan in one launch; table, checks and layouts as effi_fusion_dynamic_filter_scan_f32, every
+ * row with at least one source.  Row r of every output is bitwise the single-view entry's. */
+int effi_fusion_static_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                       const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf, int conf_h,
+                                       int conf_w, float prob_threshold, double img_dist_thresh, double depth_thresh, double vthresh,
+                                       float* mats_scratch, float* out_depth, unsigned char* out_geo_mask, unsigned char* out_prob_mask,
+                                       unsigned char* out_mask, float* out_points, effi_stream_t stream);
+/* project_img (misc/fusion.py:50-65): src_img [n][channels][src_h][src_w] sampled where the destination pixels [n][height][width] with
+ * depth dst_depth land in the source view; cameras [n][2][4][4] each; normalisation by height / width, sampling over the source's
+ * own size.  out_img [n][channels][height][width]; out_in_range [n][height][width] 0/1 floats or NULL.  mats_scratch: 104 * n floats. */
+int effi_fusion_project_img_f32(const float* src_img, const float* dst_depth, const float* src_cams, const float* dst_cams, int n,
+                                int channels, int src_h, int src_w, int height, int width, float* mats_scratch, float* out_img,
+                                float* out_in_range, effi_stream_t stream);
+/* vis_filter (misc/fusion.py:99-110) and ave_fusion (:113-115) on a given reproj_xyd [n][n_src][3][h][w], ref_depth [n][h][w].
+ * masks_in NULL: the masks are vis_filter's -> masks_out [n][n_src][h][w] (0/1 floats), mask_out [n][h][w] bytes, ave_out [n][h][w],
+ * each or NULL.  masks_in [n][n_src][h][w]: ave_fusion with the caller's masks (the thresholds are not read). */
+int effi_fusion_static_vis_filter_f32(const float* ref_depth, const float* reproj_xyd, const float* masks_in, int n, int n_src, int h,
+                                      int w, double img_dist_thresh, double depth_thresh, double vthresh, float* masks_out,
+                                      unsigned char* mask_out, float* ave_out, effi_stream_t stream);
+/* prob_filter (misc/fusion.py:68-76), one channel per call: mask [n][hw] bytes = (first ? 1 : mask) & (prob > threshold), the channel's
+ * plane of batch element b at prob + b * batch_stride. */
+int effi_fusion_prob_filter_f32(const float* prob, long batch_stride, int n, long hw, float threshold, int first, unsigned char* mask,
+                                effi_stream_t stream);
+
 /* Ordered compaction of the survivors into vertex arrays, what test_dtu_dypcd.py:327-333 and test_tank.py:517-533 do on the host with
  * boolean indexing and np.concatenate: vertices in reference-view order, row-major inside a view.  No atomics (bitwise reproducible).
  * effi_fusion_compact_count_u8: mask [n_ref][h][w] bytes -> block_base [effi_fusion_compact_blocks(n_ref, h, w)] (survivors before each
