@@ -6,6 +6,11 @@
 // photometric mask and the world-space point -- nothing of the reference's [n,v,3,h,w] intermediates is materialised
 // unless the caller asks for reproj_xyd.  Arithmetic is fp32 in the reference's operation order; the 3x3 / 4x4 inverses
 // are formed once per view on the device in fp64 and rounded (torch.inverse in fp32 differs from that by ~1e-7 relative).
+//
+// The file holds three fused filters -- this dynamic one, the fixed-threshold one of the same module and the DTU driver's -- and each
+// is ONE kernel (fusion_filter_kernel over FusDynamic / FusStatic / FusDtu) for both launch forms: a scan launch addresses its views
+// through a pair table, a single view is one row without a table (FusRows); the filter kernel is compiled once per form, the two
+// view-prepare kernels choose per launch.  The six entry points are thin wrappers over one fus_*_impl per filter (end of the file).
 #include "common.hpp"
 
 namespace {
@@ -51,14 +56,6 @@ __device__ void fus_prepare_view(const float* __restrict__ cam, float* __restric
     for (int i = 0; i < 16; ++i) { m[18 + i] = (float)E[i]; m[34 + i] = (float)Ei[i]; }
 }
 
-// cams: view 0 = reference ([2][4][4]: extrinsic, intrinsic in the top-left 3x3), views 1..V = sources
-__global__ void fusion_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
-                                      float* __restrict__ mats) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > V) return;
-    fus_prepare_view((v == 0) ? ref_cam : src_cams + (long)(v - 1) * 32, mats + (long)v * MAT_STRIDE);
-}
-
 // Pair table of a scan launch: row r = [reference id, source ids ..., -1 padding], 1 + v_max ints.  The entry points validate the
 // HOST copy of the table (ids inside the scan, source counts, padding only at the end) before any kernel reads the device copy.
 __device__ __forceinline__ int fus_row_sources(const int* __restrict__ row, int v_max) {
@@ -67,15 +64,31 @@ __device__ __forceinline__ int fus_row_sources(const int* __restrict__ row, int 
     return n;
 }
 
-// scan variant: mats [n_ref][v_max+1][52], one thread per (reference view, slot); slots past a row's source count stay unwritten
-__global__ void fusion_prepare_scan_kernel(const float* __restrict__ cams, const int* __restrict__ table, int n_ref, int v_max,
-                                           float* __restrict__ mats) {
+// Where row r of a launch finds its views (depth maps, or cameras; ``stride`` = floats per view).  With a table (scan launch) the
+// row's ids index one array of views, ref_base == src_base; without one (single view, one row) the reference is ref_base itself and
+// the v_max sources are stacked at src_base.  Per-row data -- matrices [v_max+1][52], confidence, outputs -- follows row r - 1's in
+// both forms.
+struct FusRows {
+    const float* ref_base;
+    const float* src_base;
+    const int* table;
+    int v_max;
+    __device__ __forceinline__ const int* row(int r) const { return table ? table + (long)r * (v_max + 1) : nullptr; }   // null: single view
+    __device__ __forceinline__ const float* ref(const int* row, long stride) const { return row ? ref_base + (long)row[0] * stride : ref_base; }
+    __device__ __forceinline__ const float* src(const int* row, int s, long stride) const {
+        return src_base + (long)(row ? row[1 + s] : s) * stride;
+    }
+};
+
+// mats [n_rows][v_max+1][52], one thread per (row, slot): cameras [2][4][4] (extrinsic, intrinsic in the top-left 3x3); slots past a
+// row's source count stay unwritten
+__global__ void fusion_prepare_kernel(FusRows cams, int n_rows, float* __restrict__ mats) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_ref * (v_max + 1)) return;
-    const int r = i / (v_max + 1), v = i - r * (v_max + 1);
-    const int id = table[(long)r * (v_max + 1) + v];
-    if (id < 0) return;
-    fus_prepare_view(cams + (long)id * 32, mats + (long)i * MAT_STRIDE);
+    if (i >= n_rows * (cams.v_max + 1)) return;
+    const int r = i / (cams.v_max + 1), v = i - r * (cams.v_max + 1);
+    const int* row = cams.row(r);
+    if (row && row[v] < 0) return;
+    fus_prepare_view(v == 0 ? cams.ref(row, 32) : cams.src(row, v - 1, 32), mats + (long)i * MAT_STRIDE);
 }
 
 struct V3 { float x, y, z; };
@@ -137,15 +150,89 @@ __device__ __forceinline__ float sample_bilinear_zero(const float* __restrict__ 
     return at(y0, x0) * nw + at(y0, x0 + 1) * ne + at(y0 + 1, x0) * sw + at(y0 + 1, x0 + 1) * se;
 }
 
-// The filter of ONE reference pixel p, shared by the single-view kernel and the scan kernel: every pointer is already the reference
-// view's own (``src_of(s)`` = depth map of its s-th source), so both launches run one arithmetic.
+// What a filter launch reads and writes per row besides the depth maps.  The kernel moves the pointers to its row (to_row), so a
+// pixel function sees the reference view's own, as it does the depth maps (``src_of(s)`` = depth map of its s-th source).
+struct FusIO {
+    const float* __restrict__ conf;             // [ch][cw] (DTU: [h][w]) or null
+    int ch, cw;
+    float prob_thr;
+    float* __restrict__ out_depth;              // [h][w]
+    unsigned char *__restrict__ out_geo, *__restrict__ out_prob, *__restrict__ out_mask;    // [h][w] or null; DTU: prob = photometric, mask = final
+    float* __restrict__ out_points;             // [3][h][w] or null
+    float *__restrict__ out_xyd, *__restrict__ out_in_range;       // [V][3][h][w], [V][h][w] or null: single view only, the scan entries pass null
+
+    __device__ __forceinline__ void to_row(int r, long hw) {
+        if (conf) conf += (long)r * ch * cw;
+        out_depth += r * hw;
+        if (out_geo) out_geo += r * hw;
+        if (out_prob) out_prob += r * hw;
+        if (out_mask) out_mask += r * hw;
+        if (out_points) out_points += 3 * r * hw;
+    }
+
+    // The end of the dynamic and the fixed-threshold pixel: photometric mask, the stores, the averaged depth as a world point.
+    __device__ __forceinline__ void finish(int p, int h, int w, const float* Mr, float davg, bool geo) const {
+        const long hw = (long)h * w;
+        const int y = p / w, x = p - y * w;
+        const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
+        bool pm = true;
+        if (conf) {                                                     // F.interpolate(nearest) of the confidence, test_tank.py:471-473
+            const int sy = min((int)floorf((float)y * ((float)ch / (float)h)), ch - 1);
+            const int sx = min((int)floorf((float)x * ((float)cw / (float)w)), cw - 1);
+            pm = conf[(long)sy * cw + sx] > prob_thr;
+        }
+        out_depth[p] = davg;
+        if (out_geo) out_geo[p] = geo ? 1 : 0;
+        if (out_prob) out_prob[p] = pm ? 1 : 0;
+        if (out_mask) out_mask[p] = (geo & pm) ? 1 : 0;
+        if (out_points) {                                               // :507-509 / :513-515
+            const V4 pc = img2cam<true>(Mr + 9, u, vv, davg);
+            const V4 pw = xform<true>(Mr + 34, pc);
+            out_points[p] = pw.x;
+            out_points[hw + p] = pw.y;
+            out_points[2 * hw + p] = pw.z;
+        }
+    }
+};
+
+// One kernel for every filter and both launch forms: blockIdx.y = row r (one row for a single view), so no workgroup straddles two
+// reference views, and ``Filter::pixel`` is the filter of ONE reference pixel p.  A scan launch reads maps [n_views][h][w] in place
+// through the table's ids; conf [n_rows][ch][cw]; outputs [n_rows][h][w] / points [n_rows][3][h][w].  ``Filter::kMinWaves`` is the
+// occupancy the register allocator has to keep where it would not by itself: the single view of the fixed-threshold filter takes
+// 101 scalar registers without it (7 waves per SIMD, not 8); the DTU filter keeps its 4 waves without it as the code stands, but one
+// more live offset in this kernel has put it at 149 vector registers (3 waves), so it names them; the dynamic one asks nothing.  ``TABLE`` is the
+// launch form the kernel is compiled for (fus_run picks the instance): with the choice made per launch instead, the source
+// loop of a single view loses its running pointer and holds the scalars of both forms, which cost the dynamic and the DTU filter
+// more than their run-to-run spread (profiles/fusion_unify_ab.txt).
+template <class Filter, bool TABLE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Filter::kMinWaves))) void fusion_filter_kernel(
+    FusRows maps, int h, int w, const float* __restrict__ mats, Filter f) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const long hw = (long)h * w;
+    if (p >= hw) return;
+    const int r = TABLE ? blockIdx.y : 0;                          // a single view is one row
+    const int* row = TABLE ? maps.row(r) : nullptr;
+    f.to_row(r, hw);
+    if (TABLE) f.out_xyd = f.out_in_range = nullptr;                // single-view outputs: the scan entries pass null
+    mats += (long)r * (maps.v_max + 1) * MAT_STRIDE;
+    f.pixel(p, maps.ref(row, hw), [=](int s) { return maps.src(row, s, hw); }, TABLE ? fus_row_sources(row, maps.v_max) : maps.v_max, h, w,
+            mats);
+}
+
+// The dynamic filter: thresholds i / dist_base and i / rel_base for i = dh .. V
+struct FusDynamic : FusIO {
+    static constexpr int kMinWaves = 1;
+    int dh;
+    float dist_base, rel_base;
+    int relative;
+    template <class SrcOf>
+    __device__ void pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                          const float* __restrict__ mats) const;
+};
+
 template <class SrcOf>
-__device__ __forceinline__ void fusion_dynamic_filter_pixel(
-    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
-    const float* __restrict__ mats, const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base,
-    float rel_base, int relative, float* __restrict__ out_depth, unsigned char* __restrict__ out_geo,
-    unsigned char* __restrict__ out_prob, unsigned char* __restrict__ out_mask, float* __restrict__ out_points,
-    float* __restrict__ out_xyd) {
+__device__ __forceinline__ void FusDynamic::pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                                                  const float* __restrict__ mats) const {
     const long hw = (long)h * w;
     const int y = p / w, x = p - y * w;
     const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
@@ -196,56 +283,7 @@ __device__ __forceinline__ void fusion_dynamic_filter_pixel(
 #pragma unroll
     for (int k = 0; k <= FUS_MAX_VIEWS; ++k)
         if (k < nthr && k < V + 1 - dh) geo = geo | (counts[k] >= dh + k);   // :503-504
-    bool pm = true;
-    if (conf) {                                                     // F.interpolate(nearest) of the confidence, :471-473
-        const int sy = min((int)floorf((float)y * ((float)ch / (float)h)), ch - 1);
-        const int sx = min((int)floorf((float)x * ((float)cw / (float)w)), cw - 1);
-        pm = conf[(long)sy * cw + sx] > prob_thr;
-    }
-    out_depth[p] = davg;
-    if (out_geo) out_geo[p] = geo ? 1 : 0;
-    if (out_prob) out_prob[p] = pm ? 1 : 0;
-    if (out_mask) out_mask[p] = (geo & pm) ? 1 : 0;
-    if (out_points) {                                               // :507-509
-        const V4 pc = img2cam<true>(Mr + 9, u, vv, davg);
-        const V4 pw = xform<true>(Mr + 34, pc);
-        out_points[p] = pw.x;
-        out_points[hw + p] = pw.y;
-        out_points[2 * hw + p] = pw.z;
-    }
-}
-
-__global__ __launch_bounds__(256) void fusion_dynamic_filter_kernel(
-    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w,
-    const float* __restrict__ mats, const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base,
-    float rel_base, int relative, float* __restrict__ out_depth, unsigned char* __restrict__ out_geo,
-    unsigned char* __restrict__ out_prob, unsigned char* __restrict__ out_mask, float* __restrict__ out_points,
-    float* __restrict__ out_xyd) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    fusion_dynamic_filter_pixel(p, ref_depth, [=](int s) { return src_depths + (long)s * hw; }, V, h, w, mats, conf, ch, cw, prob_thr,
-                                dh, dist_base, rel_base, relative, out_depth, out_geo, out_prob, out_mask, out_points, out_xyd);
-}
-
-// Scan launch: blockIdx.y = row r of the pair table, so no workgroup straddles two reference views.  depths [n_views][h][w] is read
-// in place through the table's ids; conf [n_ref][ch][cw]; outputs [n_ref][h][w] / points [n_ref][3][h][w].
-__global__ __launch_bounds__(256) void fusion_dynamic_filter_scan_kernel(
-    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, int ch, int cw, float prob_thr, int dh, float dist_base, float rel_base, int relative,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
-    unsigned char* __restrict__ out_mask, float* __restrict__ out_points) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    const int r = blockIdx.y;
-    const int* row = table + (long)r * (v_max + 1);
-    const int V = fus_row_sources(row, v_max);
-    fusion_dynamic_filter_pixel(p, depths + (long)row[0] * hw, [=](int s) { return depths + (long)row[1 + s] * hw; }, V, h, w,
-                                mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + (long)r * ch * cw : nullptr, ch, cw, prob_thr,
-                                dh, dist_base, rel_base, relative, out_depth + r * hw, out_geo ? out_geo + r * hw : nullptr,
-                                out_prob ? out_prob + r * hw : nullptr, out_mask ? out_mask + r * hw : nullptr,
-                                out_points ? out_points + 3 * r * hw : nullptr, nullptr);
+    finish(p, h, w, Mr, davg, geo);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -305,13 +343,18 @@ __device__ __forceinline__ float fus_static_test(float u, float vv, float dref, 
     return m ? 1.0f : 0.0f;
 }
 
-// The filter of ONE reference pixel p (pointers already the reference view's own, ``src_of(s)`` = depth map of its s-th source).
+// The fixed-threshold filter: thresholds as fus_static_thresholds (below) rounds them
+struct FusStatic : FusIO {
+    static constexpr int kMinWaves = 8;
+    float dist_thr, depth_thr, count_thr;
+    template <class SrcOf>
+    __device__ void pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                          const float* __restrict__ mats) const;
+};
+
 template <class SrcOf>
-__device__ __forceinline__ void fusion_static_filter_pixel(
-    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
-    unsigned char* __restrict__ out_mask, float* __restrict__ out_points, float* __restrict__ out_xyd, float* __restrict__ out_in_range) {
+__device__ __forceinline__ void FusStatic::pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                                                 const float* __restrict__ mats) const {
     const long hw = (long)h * w;
     const int y = p / w, x = p - y * w;
     const float u = (float)x + 0.5f, vv = (float)y + 0.5f;
@@ -339,54 +382,7 @@ __device__ __forceinline__ void fusion_static_filter_pixel(
     }
     const float davg = (dsum + dref) / (msum + 1.0f);
     const bool geo = msum >= count_thr;                             // :109, count_thr = (float)(vthresh - 1.1)
-    bool pm = true;
-    if (conf) {                                                     // F.interpolate(nearest) of the confidence, test_tank.py:471-473
-        const int sy = min((int)floorf((float)y * ((float)ch / (float)h)), ch - 1);
-        const int sx = min((int)floorf((float)x * ((float)cw / (float)w)), cw - 1);
-        pm = conf[(long)sy * cw + sx] > prob_thr;
-    }
-    out_depth[p] = davg;
-    if (out_geo) out_geo[p] = geo ? 1 : 0;
-    if (out_prob) out_prob[p] = pm ? 1 : 0;
-    if (out_mask) out_mask[p] = (geo & pm) ? 1 : 0;
-    if (out_points) {                                               // test_tank.py:513-515
-        const V4 pc = img2cam<true>(Mr + 9, u, vv, davg);
-        const V4 pw = xform<true>(Mr + 34, pc);
-        out_points[p] = pw.x;
-        out_points[hw + p] = pw.y;
-        out_points[2 * hw + p] = pw.z;
-    }
-}
-
-__global__ __launch_bounds__(256) void fusion_static_filter_kernel(
-    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
-    unsigned char* __restrict__ out_mask, float* __restrict__ out_points, float* __restrict__ out_xyd, float* __restrict__ out_in_range) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    fusion_static_filter_pixel(p, ref_depth, [=](int s) { return src_depths + (long)s * hw; }, V, h, w, mats, conf, ch, cw, prob_thr,
-                               dist_thr, depth_thr, count_thr, out_depth, out_geo, out_prob, out_mask, out_points, out_xyd, out_in_range);
-}
-
-// Scan launch: grid, table and layouts as fusion_dynamic_filter_scan_kernel.
-__global__ __launch_bounds__(256) void fusion_static_filter_scan_kernel(
-    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, int ch, int cw, float prob_thr, float dist_thr, float depth_thr, float count_thr,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_geo, unsigned char* __restrict__ out_prob,
-    unsigned char* __restrict__ out_mask, float* __restrict__ out_points) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    const int r = blockIdx.y;
-    const int* row = table + (long)r * (v_max + 1);
-    const int V = fus_row_sources(row, v_max);
-    fusion_static_filter_pixel(p, depths + (long)row[0] * hw, [=](int s) { return depths + (long)row[1 + s] * hw; }, V, h, w,
-                               mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + (long)r * ch * cw : nullptr, ch, cw, prob_thr,
-                               dist_thr, depth_thr, count_thr, out_depth + r * hw, out_geo ? out_geo + r * hw : nullptr,
-                               out_prob ? out_prob + r * hw : nullptr, out_mask ? out_mask + r * hw : nullptr,
-                               out_points ? out_points + 3 * r * hw : nullptr, nullptr, nullptr);
+    finish(p, h, w, Mr, davg, geo);
 }
 
 // mats [n][2][52]: slot 2b = destination camera b, slot 2b + 1 = source camera b
@@ -471,7 +467,7 @@ __global__ __launch_bounds__(256) void fusion_prob_filter_kernel(const float* __
 // their dtypes, OpenCV's published remap algorithm restated).  Matrix inverses / products are formed once per view in double and
 // rounded to float32 (the reference: single-precision LAPACK / float32 matmul; ~1e-7 relative apart).
 // per view: ref: K[9] Kinv[9] E[16] Einv[16]; source s: K[9] Kinv[9] T_ref->src[16] = E_s . E_ref^-1, T_src->ref[16] = E_ref . E_s^-1
-__device__ void fus_dtu_prepare_view(const float* __restrict__ ref_cam, const float* __restrict__ src_cam, float* __restrict__ m) {
+__device__ __noinline__ void fus_dtu_prepare_view(const float* __restrict__ ref_cam, const float* __restrict__ src_cam, float* __restrict__ m) {
     auto load = [](const float* cam, double* K, double* E) {
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) K[r * 3 + c] = (double)cam[16 + r * 4 + c];
@@ -502,22 +498,14 @@ __device__ void fus_dtu_prepare_view(const float* __restrict__ ref_cam, const fl
         }
 }
 
-__global__ void fusion_dtu_prepare_kernel(const float* __restrict__ ref_cam, const float* __restrict__ src_cams, int V,
-                                          float* __restrict__ mats) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > V) return;
-    fus_dtu_prepare_view(ref_cam, v == 0 ? nullptr : src_cams + (long)(v - 1) * 32, mats + (long)v * MAT_STRIDE);
-}
-
-// scan variant (layout and table as fusion_prepare_scan_kernel): the per-pair products of every (reference, source) pair in one launch
-__global__ void fusion_dtu_prepare_scan_kernel(const float* __restrict__ cams, const int* __restrict__ table, int n_ref, int v_max,
-                                               float* __restrict__ mats) {
+// layout and addressing as fusion_prepare_kernel: the per-pair products of every (reference, source) pair in one launch
+__global__ void fusion_dtu_prepare_kernel(FusRows cams, int n_rows, float* __restrict__ mats) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_ref * (v_max + 1)) return;
-    const int r = i / (v_max + 1), v = i - r * (v_max + 1);
-    const int* row = table + (long)r * (v_max + 1);
-    if (row[v] < 0) return;
-    fus_dtu_prepare_view(cams + (long)row[0] * 32, v == 0 ? nullptr : cams + (long)row[v] * 32, mats + (long)i * MAT_STRIDE);
+    if (i >= n_rows * (cams.v_max + 1)) return;
+    const int r = i / (cams.v_max + 1), v = i - r * (cams.v_max + 1);
+    const int* row = cams.row(r);
+    if (row && row[v] < 0) return;
+    fus_dtu_prepare_view(cams.ref(row, 32), v == 0 ? nullptr : cams.src(row, v - 1, 32), mats + (long)i * MAT_STRIDE);
 }
 
 struct D3 { double x, y, z; };
@@ -577,14 +565,30 @@ __device__ __forceinline__ DtuReproj dtu_reproject_pixel(const float* __restrict
     return r;
 }
 
-// The DTU filter of ONE reference pixel p, shared by the single-view kernel and the scan kernel (pointers already the reference
-// view's own, ``src_of(sv)`` = depth map of its sv-th source).
+// Threshold pair i of check_geometric_consistency (:227), shared by the two DTU kernels: dist < i * dist_base in float64,
+// depth_diff < math.log(max(i, 1.05), 10) * diff_base as a float32 comparison
+struct DtuThr {
+    double dist;
+    float diff;
+};
+__device__ __forceinline__ DtuThr dtu_thresholds(int i, float dist_base, float diff_base) {
+    return {(double)i * (double)dist_base, (float)(log(fmax((double)i, 1.05)) / log(10.0) * (double)diff_base)};
+}
+
+// The DTU filter: pairs i = s_lo .. e_hi - 1; conf [h][w], already at the depth size, prob_thr = the photometric threshold
+struct FusDtu : FusIO {
+    static constexpr int kMinWaves = 4;
+    float conf_keep;
+    int s_lo, e_hi;
+    float dist_base, diff_base;
+    template <class SrcOf>
+    __device__ void pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                          const float* __restrict__ mats) const;
+};
+
 template <class SrcOf>
-__device__ __forceinline__ void fusion_dtu_filter_pixel(
-    int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
-    unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
+__device__ __forceinline__ void FusDtu::pixel(int p, const float* __restrict__ ref_depth, SrcOf src_of, int V, int h, int w,
+                                              const float* __restrict__ mats) const {
     const long hw = (long)h * w;
     const int y = p / w, x = p - y * w;
     const double xd = (double)x, yd = (double)y;
@@ -596,10 +600,10 @@ __device__ __forceinline__ void fusion_dtu_filter_pixel(
     int counts[DTU_MAX_THR];
 #pragma unroll
     for (int k = 0; k < DTU_MAX_THR; ++k) {
-        const int i = s_lo + k;
+        const DtuThr t = dtu_thresholds(s_lo + k, dist_base, diff_base);
         counts[k] = 0;
-        thr_dist[k] = (double)i * (double)dist_base;                                                          // i * dist_base (:227)
-        thr_diff[k] = (float)(log(fmax((double)i, 1.05)) / log(10.0) * (double)diff_base);    // math.log(max(i, 1.05), 10) * diff_base; float32 comparison
+        thr_dist[k] = t.dist;
+        thr_diff[k] = t.diff;
     }
     float num = 0.0f;                          // sum(all_srcview_depth_ests): float32, in view order (:299)
     int nlast = 0;
@@ -631,11 +635,11 @@ __device__ __forceinline__ void fusion_dtu_filter_pixel(
 #pragma unroll
     for (int k = 0; k < DTU_MAX_THR; ++k)
         if (k < nthr) geo = geo | (counts[k] >= s_lo + k);                                                     // (:304-305)
-    const bool photo = c > conf_thr;                                                                           // (:261)
+    const bool photo = c > prob_thr;                                                                           // (:261)
     out_depth[p] = (float)davg;
-    if (out_photo) out_photo[p] = photo ? 1 : 0;
+    if (out_prob) out_prob[p] = photo ? 1 : 0;
     if (out_geo) out_geo[p] = geo ? 1 : 0;
-    if (out_final) out_final[p] = (photo & geo) ? 1 : 0;
+    if (out_mask) out_mask[p] = (photo & geo) ? 1 : 0;
     if (out_points) {                                                                                          // (:327-330)
         const D3 pc = dmul3(Mr + 9, xd * davg, yd * davg, davg);
         const D3 pw = dmul4_xyz(Mr + 34, pc);
@@ -643,37 +647,6 @@ __device__ __forceinline__ void fusion_dtu_filter_pixel(
         out_points[hw + p] = (float)pw.y;
         out_points[2 * hw + p] = (float)pw.z;
     }
-}
-
-__global__ __launch_bounds__(256) void fusion_dtu_filter_kernel(
-    const float* __restrict__ ref_depth, const float* __restrict__ src_depths, int V, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
-    unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    fusion_dtu_filter_pixel(p, ref_depth, [=](int sv) { return src_depths + (long)sv * hw; }, V, h, w, mats, conf, conf_thr, conf_keep,
-                            s_lo, e_hi, dist_base, diff_base, out_depth, out_photo, out_geo, out_final, out_points);
-}
-
-// Scan launch (grid and layouts as fusion_dynamic_filter_scan_kernel); conf [n_ref][h][w], already at the depth size.
-__global__ __launch_bounds__(256) void fusion_dtu_filter_scan_kernel(
-    const float* __restrict__ depths, const int* __restrict__ table, int v_max, int h, int w, const float* __restrict__ mats,
-    const float* __restrict__ conf, float conf_thr, float conf_keep, int s_lo, int e_hi, float dist_base, float diff_base,
-    float* __restrict__ out_depth, unsigned char* __restrict__ out_photo, unsigned char* __restrict__ out_geo,
-    unsigned char* __restrict__ out_final, float* __restrict__ out_points) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const long hw = (long)h * w;
-    if (p >= hw) return;
-    const int r = blockIdx.y;
-    const int* row = table + (long)r * (v_max + 1);
-    const int V = fus_row_sources(row, v_max);
-    fusion_dtu_filter_pixel(p, depths + (long)row[0] * hw, [=](int sv) { return depths + (long)row[1 + sv] * hw; }, V, h, w,
-                            mats + (long)r * (v_max + 1) * MAT_STRIDE, conf ? conf + r * hw : nullptr, conf_thr, conf_keep, s_lo, e_hi,
-                            dist_base, diff_base, out_depth + r * hw, out_photo ? out_photo + r * hw : nullptr,
-                            out_geo ? out_geo + r * hw : nullptr, out_final ? out_final + r * hw : nullptr,
-                            out_points ? out_points + 3 * r * hw : nullptr);
 }
 
 // reproject_with_depth (test_dtu_dypcd.py:164-205) and, with ``masks``, check_geometric_consistency (:208-233) for one
@@ -697,9 +670,8 @@ __global__ __launch_bounds__(256) void fusion_dtu_reproject_kernel(const float* 
         const float ddiff = fabsf(r.depth_rep - dref);
         bool last = false;
         for (int k = 0; k < e_hi - s_lo; ++k) {
-            const int i = s_lo + k;
-            const float thr_diff = (float)(log(fmax((double)i, 1.05)) / log(10.0) * (double)diff_base);
-            last = (dist < (double)i * (double)dist_base) & (ddiff < thr_diff);
+            const DtuThr t = dtu_thresholds(s_lo + k, dist_base, diff_base);
+            last = (dist < t.dist) & (ddiff < t.diff);
             masks[(long)k * hw + p] = last ? 1 : 0;
         }
         if (!last) r.depth_rep = r.x_rep = r.y_rep = 0.0f;
@@ -898,50 +870,6 @@ static int fus_check_table(const int* table, int n_ref, int v_max, int n_views, 
     return EFFI_OK;
 }
 
-extern "C" int effi_fusion_dtu_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
-                                               const int* pair_table, int n_ref, int v_max, int h, int w, const float* confidence,
-                                               float conf_threshold, float conf_keep, int s, int e, float dist_base, float diff_base,
-                                               float* mats_scratch, float* out_depth, unsigned char* out_photo_mask,
-                                               unsigned char* out_geo_mask, unsigned char* out_final_mask, float* out_points,
-                                               effi_stream_t stream) {
-    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || s < 1 || e <= s || dist_base <= 0.0f || diff_base <= 0.0f) return EFFI_ERR_BADARG;
-    if (e - s > DTU_MAX_THR) return EFFI_ERR_UNSUPPORTED;
-    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, 1) != EFFI_OK) return EFFI_ERR_BADARG;
-    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_dtu_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table,
-                       n_ref, v_max, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_dtu_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table, v_max,
-                       h, w, mats_scratch, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, out_depth, out_photo_mask,
-                       out_geo_mask, out_final_mask, out_points);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
-extern "C" int effi_fusion_dynamic_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
-                                                   const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf,
-                                                   int conf_h, int conf_w, float prob_threshold, int dh_view_num, float dist_base,
-                                                   float rel_diff_base, int relative, float* mats_scratch, float* out_depth,
-                                                   unsigned char* out_geo_mask, unsigned char* out_prob_mask, unsigned char* out_mask,
-                                                   float* out_points, effi_stream_t stream) {
-    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || dh_view_num < 1 || dist_base <= 0.0f || rel_diff_base <= 0.0f) return EFFI_ERR_BADARG;
-    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
-    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, dh_view_num) != EFFI_OK) return EFFI_ERR_BADARG;
-    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table, n_ref,
-                       v_max, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_dynamic_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table,
-                       v_max, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dh_view_num, dist_base, rel_diff_base, relative,
-                       out_depth, out_geo_mask, out_prob_mask, out_mask, out_points);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
 extern "C" int effi_fusion_compact_blocks(int n_ref, int h, int w) {
     if (n_ref < 1 || n_ref > 65535 || h < 1 || w < 1 || (long)n_ref * h * w >= (1L << 31)) return 0;
     return n_ref * effi_cdiv((long)h * w, CMP_THREADS);
@@ -1021,50 +949,11 @@ extern "C" int effi_fusion_dtu_reproject_f32(const float* ref_depth, const float
     if (!ref_depth || !src_depth || !ref_cam || !src_cam || !mats_scratch || !out5 || h < 2 || w < 2) return EFFI_ERR_BADARG;
     if (masks && (s < 1 || e <= s || dist_base <= 0.0f || diff_base <= 0.0f)) return EFFI_ERR_BADARG;
     hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_dtu_prepare_kernel, dim3(1), dim3(64), 0, st, ref_cam, src_cam, 1, mats_scratch);
+    const FusRows cams{ref_cam, src_cam, nullptr, 1};
+    hipLaunchKernelGGL(fusion_dtu_prepare_kernel, dim3(1), dim3(64), 0, st, cams, 1, mats_scratch);
     EFFI_LAUNCH_CHECK();
     hipLaunchKernelGGL(fusion_dtu_reproject_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depth, h, w,
                        mats_scratch, s, e, dist_base, diff_base, out5, masks);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
-extern "C" int effi_fusion_dtu_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams,
-                                          int n_src, int h, int w, const float* confidence, float conf_threshold, float conf_keep,
-                                          int s, int e, float dist_base, float diff_base, float* mats_scratch, float* out_depth,
-                                          unsigned char* out_photo_mask, unsigned char* out_geo_mask, unsigned char* out_final_mask,
-                                          float* out_points, effi_stream_t stream) {
-    if (!ref_depth || !src_depths || !ref_cam || !src_cams || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (n_src < 1 || h < 2 || w < 2 || s < 1 || e <= s || dist_base <= 0.0f || diff_base <= 0.0f) return EFFI_ERR_BADARG;
-    if (n_src > FUS_MAX_VIEWS || e - s > DTU_MAX_THR) return EFFI_ERR_UNSUPPORTED;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_dtu_prepare_kernel, dim3(1), dim3(64), 0, st, ref_cam, src_cams, n_src, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_dtu_filter_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depths, n_src, h, w,
-                       mats_scratch, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, out_depth, out_photo_mask,
-                       out_geo_mask, out_final_mask, out_points);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
-extern "C" int effi_fusion_dynamic_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam,
-                                              const float* src_cams, int n_src, int h, int w, const float* ref_conf, int conf_h,
-                                              int conf_w, float prob_threshold, int dh_view_num, float dist_base,
-                                              float rel_diff_base, int relative, float* mats_scratch, float* out_depth,
-                                              unsigned char* out_geo_mask, unsigned char* out_prob_mask,
-                                              unsigned char* out_mask, float* out_points, float* out_reproj_xyd,
-                                              effi_stream_t stream) {
-    if (!ref_depth || !src_depths || !ref_cam || !src_cams || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (n_src < 1 || h < 2 || w < 2 || dh_view_num < 1 || dh_view_num > n_src || dist_base <= 0.0f || rel_diff_base <= 0.0f)
-        return EFFI_ERR_BADARG;
-    if (n_src > FUS_MAX_VIEWS) return EFFI_ERR_UNSUPPORTED;
-    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_prepare_kernel, dim3(1), dim3(64), 0, st, ref_cam, src_cams, n_src, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_dynamic_filter_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depths,
-                       n_src, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dh_view_num, dist_base, rel_diff_base,
-                       relative, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points, out_reproj_xyd);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }
@@ -1079,26 +968,112 @@ static int fus_static_thresholds(double img_dist_thresh, double depth_thresh, do
     return EFFI_OK;
 }
 
+// ---- the three fused filters, each as a single-view and a scan entry over one body ----
+// One filter launch as its entry describes it: depth maps and cameras under one addressing, mats [n_rows][v_max+1][52].
+struct FusLaunch {
+    bool scan;                  // false: one row, no table, maps / cams = (reference, stacked sources)
+    FusRows maps, cams;
+    const int* table_host;
+    int n_views, n_rows, h, w;
+    float* mats;
+};
+static FusLaunch fus_single(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams, int n_src, int h,
+                            int w, float* mats) {
+    return {false, {ref_depth, src_depths, nullptr, n_src}, {ref_cam, src_cams, nullptr, n_src}, nullptr, 0, 1, h, w, mats};
+}
+static FusLaunch fus_scan(const float* depths, const float* cams, int n_views, const int* table_host, const int* table, int n_ref,
+                          int v_max, int h, int w, float* mats) {
+    return {true, {depths, depths, table, v_max}, {cams, cams, table, v_max}, table_host, n_views, n_ref, h, w, mats};
+}
+
+// What every filter entry refuses beyond its own parameters.  A single view may have too many sources for the kernels
+// (UNSUPPORTED, as is ``over_limit``, a filter's own capacity); a table with such a row is a bad argument.  Every entry refuses
+// 2^31 pixels or more per launch (BADARG): the kernels index pixels with an int.  The single-view dynamic and DTU entries did not
+// before they shared this check, and could not have run such a size.
+static int fus_check(const FusLaunch& L, const FusIO& io, int min_src, bool over_limit) {
+    const int V = L.maps.v_max;
+    if (!L.maps.ref_base || !L.maps.src_base || !L.cams.ref_base || !L.cams.src_base || !L.mats || !io.out_depth) return EFFI_ERR_BADARG;
+    if ((L.scan && !L.maps.table) || L.h < 2 || L.w < 2) return EFFI_ERR_BADARG;
+    if (!L.scan && (V < 1 || V < min_src || (long)L.h * L.w >= (1L << 31))) return EFFI_ERR_BADARG;
+    if (over_limit || (!L.scan && V > FUS_MAX_VIEWS)) return EFFI_ERR_UNSUPPORTED;
+    if (io.conf && (io.ch < 1 || io.cw < 1)) return EFFI_ERR_BADARG;
+    if (L.scan && (fus_check_table(L.table_host, L.n_rows, V, L.n_views, min_src) != EFFI_OK || (long)L.n_rows * L.h * L.w >= (1L << 31)))
+        return EFFI_ERR_BADARG;
+    return EFFI_OK;
+}
+
+// the view matrices of every row, then the filter: one workgroup row per table row
+template <class Filter>
+static int fus_run(const FusLaunch& L, void (*prepare)(FusRows, int, float*), const Filter& f, effi_stream_t stream) {
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(prepare, dim3(effi_cdiv((long)L.n_rows * (L.maps.v_max + 1), 64)), dim3(64), 0, st, L.cams, L.n_rows, L.mats);
+    EFFI_LAUNCH_CHECK();
+    hipLaunchKernelGGL((L.scan ? fusion_filter_kernel<Filter, true> : fusion_filter_kernel<Filter, false>),
+                       dim3(effi_cdiv((long)L.h * L.w, 256), L.n_rows), dim3(256), 0, st, L.maps, L.h, L.w, L.mats, f);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+static int fus_dynamic_impl(const FusLaunch& L, const FusIO& io, int dh, float dist_base, float rel_base, int relative,
+                            effi_stream_t stream) {
+    if (dh < 1 || dist_base <= 0.0f || rel_base <= 0.0f) return EFFI_ERR_BADARG;
+    const int rc = fus_check(L, io, dh, false);                     // every row needs dh sources
+    if (rc != EFFI_OK) return rc;
+    return fus_run(L, fusion_prepare_kernel, FusDynamic{io, dh, dist_base, rel_base, relative}, stream);
+}
+
+static int fus_static_impl(const FusLaunch& L, const FusIO& io, double img_dist_thresh, double depth_thresh, double vthresh,
+                           effi_stream_t stream) {
+    const int rc = fus_check(L, io, 1, false);
+    if (rc != EFFI_OK) return rc;
+    FusStatic f{io};
+    if (fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &f.dist_thr, &f.depth_thr, &f.count_thr) != EFFI_OK) return EFFI_ERR_BADARG;
+    return fus_run(L, fusion_prepare_kernel, f, stream);
+}
+
+static int fus_dtu_impl(const FusLaunch& L, const FusIO& io, float conf_keep, int s, int e, float dist_base, float diff_base,
+                        effi_stream_t stream) {
+    if (s < 1 || e <= s || dist_base <= 0.0f || diff_base <= 0.0f) return EFFI_ERR_BADARG;
+    const int rc = fus_check(L, io, 1, e - s > DTU_MAX_THR);
+    if (rc != EFFI_OK) return rc;
+    return fus_run(L, fusion_dtu_prepare_kernel, FusDtu{io, conf_keep, s, e, dist_base, diff_base}, stream);
+}
+
+extern "C" int effi_fusion_dynamic_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam,
+                                              const float* src_cams, int n_src, int h, int w, const float* ref_conf, int conf_h,
+                                              int conf_w, float prob_threshold, int dh_view_num, float dist_base,
+                                              float rel_diff_base, int relative, float* mats_scratch, float* out_depth,
+                                              unsigned char* out_geo_mask, unsigned char* out_prob_mask,
+                                              unsigned char* out_mask, float* out_points, float* out_reproj_xyd,
+                                              effi_stream_t stream) {
+    return fus_dynamic_impl(fus_single(ref_depth, src_depths, ref_cam, src_cams, n_src, h, w, mats_scratch),
+                            {ref_conf, conf_h, conf_w, prob_threshold, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points,
+                             out_reproj_xyd, nullptr},
+                            dh_view_num, dist_base, rel_diff_base, relative, stream);
+}
+
+extern "C" int effi_fusion_dynamic_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                                   const int* pair_table, int n_ref, int v_max, int h, int w, const float* ref_conf,
+                                                   int conf_h, int conf_w, float prob_threshold, int dh_view_num, float dist_base,
+                                                   float rel_diff_base, int relative, float* mats_scratch, float* out_depth,
+                                                   unsigned char* out_geo_mask, unsigned char* out_prob_mask, unsigned char* out_mask,
+                                                   float* out_points, effi_stream_t stream) {
+    return fus_dynamic_impl(fus_scan(depths, cams, n_views, pair_table_host, pair_table, n_ref, v_max, h, w, mats_scratch),
+                            {ref_conf, conf_h, conf_w, prob_threshold, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points,
+                             nullptr, nullptr},
+                            dh_view_num, dist_base, rel_diff_base, relative, stream);
+}
+
 extern "C" int effi_fusion_static_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams,
                                              int n_src, int h, int w, const float* ref_conf, int conf_h, int conf_w, float prob_threshold,
                                              double img_dist_thresh, double depth_thresh, double vthresh, float* mats_scratch,
                                              float* out_depth, unsigned char* out_geo_mask, unsigned char* out_prob_mask,
                                              unsigned char* out_mask, float* out_points, float* out_reproj_xyd, float* out_in_range,
                                              effi_stream_t stream) {
-    if (!ref_depth || !src_depths || !ref_cam || !src_cams || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (n_src < 1 || h < 2 || w < 2 || (long)h * w >= (1L << 31)) return EFFI_ERR_BADARG;
-    if (n_src > FUS_MAX_VIEWS) return EFFI_ERR_UNSUPPORTED;
-    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
-    float dist_thr, depth_thr, count_thr;
-    if (fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &dist_thr, &depth_thr, &count_thr) != EFFI_OK) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_prepare_kernel, dim3(1), dim3(64), 0, st, ref_cam, src_cams, n_src, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_static_filter_kernel, dim3(effi_cdiv((long)h * w, 256)), dim3(256), 0, st, ref_depth, src_depths, n_src, h, w,
-                       mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dist_thr, depth_thr, count_thr, out_depth, out_geo_mask,
-                       out_prob_mask, out_mask, out_points, out_reproj_xyd, out_in_range);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return fus_static_impl(fus_single(ref_depth, src_depths, ref_cam, src_cams, n_src, h, w, mats_scratch),
+                           {ref_conf, conf_h, conf_w, prob_threshold, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points,
+                            out_reproj_xyd, out_in_range},
+                           img_dist_thresh, depth_thresh, vthresh, stream);
 }
 
 extern "C" int effi_fusion_static_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
@@ -1107,22 +1082,34 @@ extern "C" int effi_fusion_static_filter_scan_f32(const float* depths, const flo
                                                   double vthresh, float* mats_scratch, float* out_depth, unsigned char* out_geo_mask,
                                                   unsigned char* out_prob_mask, unsigned char* out_mask, float* out_points,
                                                   effi_stream_t stream) {
-    if (!depths || !cams || !pair_table || !mats_scratch || !out_depth) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2) return EFFI_ERR_BADARG;
-    if (ref_conf && (conf_h < 1 || conf_w < 1)) return EFFI_ERR_BADARG;
-    float dist_thr, depth_thr, count_thr;
-    if (fus_static_thresholds(img_dist_thresh, depth_thresh, vthresh, &dist_thr, &depth_thr, &count_thr) != EFFI_OK) return EFFI_ERR_BADARG;
-    if (fus_check_table(pair_table_host, n_ref, v_max, n_views, 1) != EFFI_OK) return EFFI_ERR_BADARG;
-    if ((long)n_ref * h * w >= (1L << 31)) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(fusion_prepare_scan_kernel, dim3(effi_cdiv((long)n_ref * (v_max + 1), 64)), dim3(64), 0, st, cams, pair_table, n_ref,
-                       v_max, mats_scratch);
-    EFFI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fusion_static_filter_scan_kernel, dim3(effi_cdiv((long)h * w, 256), n_ref), dim3(256), 0, st, depths, pair_table,
-                       v_max, h, w, mats_scratch, ref_conf, conf_h, conf_w, prob_threshold, dist_thr, depth_thr, count_thr, out_depth,
-                       out_geo_mask, out_prob_mask, out_mask, out_points);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return fus_static_impl(fus_scan(depths, cams, n_views, pair_table_host, pair_table, n_ref, v_max, h, w, mats_scratch),
+                           {ref_conf, conf_h, conf_w, prob_threshold, out_depth, out_geo_mask, out_prob_mask, out_mask, out_points, nullptr,
+                            nullptr},
+                           img_dist_thresh, depth_thresh, vthresh, stream);
+}
+
+// confidence [n_rows][h][w], already at the depth size
+extern "C" int effi_fusion_dtu_filter_f32(const float* ref_depth, const float* src_depths, const float* ref_cam, const float* src_cams,
+                                          int n_src, int h, int w, const float* confidence, float conf_threshold, float conf_keep,
+                                          int s, int e, float dist_base, float diff_base, float* mats_scratch, float* out_depth,
+                                          unsigned char* out_photo_mask, unsigned char* out_geo_mask, unsigned char* out_final_mask,
+                                          float* out_points, effi_stream_t stream) {
+    return fus_dtu_impl(fus_single(ref_depth, src_depths, ref_cam, src_cams, n_src, h, w, mats_scratch),
+                        {confidence, h, w, conf_threshold, out_depth, out_geo_mask, out_photo_mask, out_final_mask, out_points, nullptr,
+                         nullptr},
+                        conf_keep, s, e, dist_base, diff_base, stream);
+}
+
+extern "C" int effi_fusion_dtu_filter_scan_f32(const float* depths, const float* cams, int n_views, const int* pair_table_host,
+                                               const int* pair_table, int n_ref, int v_max, int h, int w, const float* confidence,
+                                               float conf_threshold, float conf_keep, int s, int e, float dist_base, float diff_base,
+                                               float* mats_scratch, float* out_depth, unsigned char* out_photo_mask,
+                                               unsigned char* out_geo_mask, unsigned char* out_final_mask, float* out_points,
+                                               effi_stream_t stream) {
+    return fus_dtu_impl(fus_scan(depths, cams, n_views, pair_table_host, pair_table, n_ref, v_max, h, w, mats_scratch),
+                        {confidence, h, w, conf_threshold, out_depth, out_geo_mask, out_photo_mask, out_final_mask, out_points, nullptr,
+                         nullptr},
+                        conf_keep, s, e, dist_base, diff_base, stream);
 }
 
 extern "C" int effi_fusion_project_img_f32(const float* src_img, const float* dst_depth, const float* src_cams, const float* dst_cams,

@@ -100,19 +100,24 @@ def vis_filter_dynamic(ref_depth, reproj_xyd, ref_idx_world, src2ref_idx_cam, di
     return masks, masks[:, :, -1:, :, :]
 
 
+def _filter_samples(op, ref_depth, src_depths, ref_cam, src_cams, ref_conf, *params):
+    """What ``dynamic_filter`` and ``static_filter`` share: one launch of the single-view ``op`` per sample, results stacked."""
+    n = ref_depth.shape[0]
+    res = [op(ref_depth[b, 0].contiguous(), src_depths[b, :, 0].contiguous(), ref_cam[b].contiguous(), src_cams[b].contiguous(),
+              None if ref_conf is None else ref_conf[b].contiguous(), *params) for b in range(n)]
+    out = {"depth": torch.stack([r["depth"] for r in res]).unsqueeze(1), "points": torch.stack([r["points"] for r in res])}
+    for k in ("geo_mask", "prob_mask", "mask"):
+        out[k] = torch.stack([r[k] for r in res]).unsqueeze(1).bool()
+    return out
+
+
 @ops.on_tensor_device
 def dynamic_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_threshold, dh_view_num, dist_filter, depth_filter,
                    relative=False):
     """The tensor part of ``dynamic_filter_depth`` (test_tank.py:466-512) for a batch of reference views as ONE kernel each:
     -> dict(depth [n,1,h,w] averaged depth, geo_mask / prob_mask / mask [n,1,h,w] bool, points [n,3,h,w])."""
-    n = ref_depth.shape[0]
-    res = [ops.fusion_dynamic_filter(ref_depth[b, 0].contiguous(), src_depths[b, :, 0].contiguous(), ref_cam[b].contiguous(),
-                                     src_cams[b].contiguous(), None if ref_conf is None else ref_conf[b].contiguous(),
-                                     prob_threshold, dh_view_num, dist_filter, depth_filter, relative) for b in range(n)]
-    out = {"depth": torch.stack([r["depth"] for r in res]).unsqueeze(1), "points": torch.stack([r["points"] for r in res])}
-    for k in ("geo_mask", "prob_mask", "mask"):
-        out[k] = torch.stack([r[k] for r in res]).unsqueeze(1).bool()
-    return out
+    return _filter_samples(ops.fusion_dynamic_filter, ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_threshold, dh_view_num,
+                           dist_filter, depth_filter, relative)
 
 
 @ops.on_tensor_device
@@ -164,14 +169,8 @@ def static_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_thres
     """``get_reproj`` + ``vis_filter`` + ``ave_fusion`` with the driver's photometric mask and points (test_tank.py:471-475,512-515)
     for a batch of reference views as ONE kernel each; shapes as ``dynamic_filter``, ref_conf [n,H,W] or None
     -> dict(depth [n,1,h,w] = ave_fusion, geo_mask = vis_filter's mask, prob_mask, mask = their AND [n,1,h,w] bool, points [n,3,h,w])."""
-    n = ref_depth.shape[0]
-    res = [ops.fusion_static_filter(ref_depth[b, 0].contiguous(), src_depths[b, :, 0].contiguous(), ref_cam[b].contiguous(),
-                                    src_cams[b].contiguous(), None if ref_conf is None else ref_conf[b].contiguous(), prob_threshold,
-                                    img_dist_thresh, depth_thresh, vthresh) for b in range(n)]
-    out = {"depth": torch.stack([r["depth"] for r in res]).unsqueeze(1), "points": torch.stack([r["points"] for r in res])}
-    for k in ("geo_mask", "prob_mask", "mask"):
-        out[k] = torch.stack([r[k] for r in res]).unsqueeze(1).bool()
-    return out
+    return _filter_samples(ops.fusion_static_filter, ref_depth, src_depths, ref_cam, src_cams, ref_conf, prob_threshold, img_dist_thresh,
+                           depth_thresh, vthresh)
 
 
 def pair_table(pair_data):
@@ -205,17 +204,9 @@ def fuse_chunks(table, filter_chunk, images, layout, chunk, mask_keys):
     return out
 
 
-@ops.on_tensor_device
-def dynamic_filter_scan(depths, confidences, cams, images, pair_data, prob_threshold=0.3, dh_view_num=2, dist_filter=4.0,
-                        depth_filter=1300.0, relative=False, chunk=None):
-    """``dynamic_filter_depth`` (test_tank.py:455-570) from the maps a scan's forward pass left on the device to the fused point
-    cloud, ``filter_dixt``'s fields as keywords.  depths [n_views,h,w]; confidences [n_views,ch,cw] or None; cams [n_views,2,4,4];
-    images [n_views,3,h,w] fp32 in [0,1]; ``pair_data`` the ``read_pair_file`` list.  A reference view with fewer than
-    ``dh_view_num + 1`` sources contributes nothing (:478) -> dict(xyz [M,3] float32, rgb [M,3] uint8 -- vertices in the reference's
-    order: retained reference views in list order, row-major survivors --, offsets [n_kept+1] int32, ref_ids: the retained reference
-    ids, depth [n_kept,h,w], prob_mask / geo_mask / mask [n_kept,h,w] bool).  Works through the reference views ``chunk`` at a time
-    (None: sized so that a chunk's dense points stay below 400 MB); the result is the same for every ``chunk``."""
-    rows = [(ref, srcs) for ref, srcs in pair_data if len(srcs) >= dh_view_num + 1]
+def _filter_scan(op, rows, depths, confidences, cams, images, chunk, *params):
+    """What ``dynamic_filter_scan`` and ``static_filter_scan`` share: the scan-batched ``op`` over the kept ``rows`` of the pair list,
+    chunk by chunk, survivors compacted."""
     dev = depths.device
     if not rows:
         h, w = depths.shape[-2:]
@@ -228,13 +219,28 @@ def dynamic_filter_scan(depths, confidences, cams, images, pair_data, prob_thres
 
     def filter_chunk(t_, r0, r1):
         conf = None if confidences is None else confidences[t_[:, 0].long().to(dev)].contiguous()
-        return ops.fusion_dynamic_filter_scan(depths, cams, t_, conf, prob_threshold, dh_view_num, dist_filter, depth_filter, relative)
+        return op(depths, cams, t_, conf, *params)
 
     out = fuse_chunks(table, filter_chunk, images, "chw", chunk, ("depth", "prob_mask", "geo_mask", "mask"))
     for k in ("prob_mask", "geo_mask", "mask"):
         out[k] = out[k].bool()
     out["ref_ids"] = [ref for ref, _ in rows]
     return out
+
+
+@ops.on_tensor_device
+def dynamic_filter_scan(depths, confidences, cams, images, pair_data, prob_threshold=0.3, dh_view_num=2, dist_filter=4.0,
+                        depth_filter=1300.0, relative=False, chunk=None):
+    """``dynamic_filter_depth`` (test_tank.py:455-570) from the maps a scan's forward pass left on the device to the fused point
+    cloud, ``filter_dixt``'s fields as keywords.  depths [n_views,h,w]; confidences [n_views,ch,cw] or None; cams [n_views,2,4,4];
+    images [n_views,3,h,w] fp32 in [0,1]; ``pair_data`` the ``read_pair_file`` list.  A reference view with fewer than
+    ``dh_view_num + 1`` sources contributes nothing (:478) -> dict(xyz [M,3] float32, rgb [M,3] uint8 -- vertices in the reference's
+    order: retained reference views in list order, row-major survivors --, offsets [n_kept+1] int32, ref_ids: the retained reference
+    ids, depth [n_kept,h,w], prob_mask / geo_mask / mask [n_kept,h,w] bool).  Works through the reference views ``chunk`` at a time
+    (None: sized so that a chunk's dense points stay below 400 MB); the result is the same for every ``chunk``."""
+    rows = [(ref, srcs) for ref, srcs in pair_data if len(srcs) >= dh_view_num + 1]
+    return _filter_scan(ops.fusion_dynamic_filter_scan, rows, depths, confidences, cams, images, chunk, prob_threshold, dh_view_num,
+                        dist_filter, depth_filter, relative)
 
 
 def static_scan_rows(pair_data):
@@ -248,23 +254,5 @@ def static_filter_scan(depths, confidences, cams, images, pair_data, prob_thresh
                        vthresh=4, chunk=None):
     """``static_filter`` over a scan's reference views, from the maps on the device to the fused point cloud; arguments, chunking and
     result as ``dynamic_filter_scan``.  Reference views without a source are dropped; ``ref_ids`` lists the ones that remain."""
-    rows = static_scan_rows(pair_data)
-    dev = depths.device
-    if not rows:
-        h, w = depths.shape[-2:]
-        z = lambda *sh, dt=torch.float32: torch.empty(*sh, device=dev, dtype=dt)
-        return {"xyz": z(0, 3), "rgb": z(0, 3, dt=torch.uint8), "offsets": torch.zeros(1, dtype=torch.int32, device=dev), "ref_ids": [],
-                "depth": z(0, h, w), "prob_mask": z(0, h, w, dt=torch.bool), "geo_mask": z(0, h, w, dt=torch.bool),
-                "mask": z(0, h, w, dt=torch.bool)}
-    table = pair_table(rows)
-    depths, cams, images = depths.contiguous(), cams.contiguous(), images.contiguous()
-
-    def filter_chunk(t_, r0, r1):
-        conf = None if confidences is None else confidences[t_[:, 0].long().to(dev)].contiguous()
-        return ops.fusion_static_filter_scan(depths, cams, t_, conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh)
-
-    out = fuse_chunks(table, filter_chunk, images, "chw", chunk, ("depth", "prob_mask", "geo_mask", "mask"))
-    for k in ("prob_mask", "geo_mask", "mask"):
-        out[k] = out[k].bool()
-    out["ref_ids"] = [ref for ref, _ in rows]
-    return out
+    return _filter_scan(ops.fusion_static_filter_scan, static_scan_rows(pair_data), depths, confidences, cams, images, chunk,
+                        prob_threshold, img_dist_thresh, depth_thresh, vthresh)

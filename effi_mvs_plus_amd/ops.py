@@ -12,6 +12,7 @@ import ctypes as C
 import functools
 import os
 import threading
+from typing import NamedTuple
 
 import weakref
 
@@ -948,30 +949,10 @@ def fusion_dynamic_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf=Non
     """Scope row n3: one reference view through the dynamic geometric-consistency filter (misc/fusion.py:117-181,
     test_tank.py:466-512).  ref_depth [h,w]; src_depths [V,h,w]; ref_cam [2,4,4]; src_cams [V,2,4,4]; ref_conf [H,W] or None
     -> dict(depth [h,w], geo_mask / prob_mask / mask [h,w] uint8, points [3,h,w] or None, reproj_xyd [V,3,h,w] or None)."""
-    for name, t_ in (("ref_depth", ref_depth), ("src_depths", src_depths), ("ref_cam", ref_cam), ("src_cams", src_cams)):
-        _t(t_, name)
-    V, h, w = src_depths.shape
-    dev = ref_depth.device
-    if tuple(ref_depth.shape) != (h, w) or tuple(ref_cam.shape) != (2, 4, 4) or tuple(src_cams.shape) != (V, 2, 4, 4):
-        raise ValueError("fusion_dynamic_filter: ref_depth [h,w], src_depths [V,h,w], ref_cam [2,4,4], src_cams [V,2,4,4]")
-    ch = cw = 0
-    if ref_conf is not None:
-        _t(ref_conf, "ref_conf")
-        ch, cw = ref_conf.shape
-    out = {"depth": torch.empty(h, w, device=dev, dtype=torch.float32),
-           "geo_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "prob_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(3, h, w, device=dev, dtype=torch.float32) if want_points else None,
-           "reproj_xyd": torch.empty(V, 3, h, w, device=dev, dtype=torch.float32) if want_reproj else None}
-    scratch = torch.empty(52 * (V + 1), device=dev, dtype=torch.float32)
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (1 + V + 1 + (3 if want_points else 0)) + 3.0 * h * w}
-    check(_call("fusion_dynamic_filter", work, _lib.lib().effi_fusion_dynamic_filter_f32, _p(ref_depth), _p(src_depths),
-                _p(ref_cam), _p(src_cams), V, h, w, _p(ref_conf), ch, cw, float(prob_threshold), int(dh_view_num),
-                float(dist_base), float(rel_diff_base), int(bool(relative)), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]),
-                _p(out["prob_mask"]), _p(out["mask"]), _p(out["points"]), _p(out["reproj_xyd"]), _stream()),
-          "effi_fusion_dynamic_filter_f32")
-    return out
+    rows = _view_inputs("fusion_dynamic_filter", ref_depth, src_depths, ref_cam, src_cams)
+    return _fusion_dynamic("fusion_dynamic_filter", _lib.lib().effi_fusion_dynamic_filter_f32,
+                           rows, ref_conf, prob_threshold, dh_view_num, dist_base, rel_diff_base, relative, want_points,
+                           {"reproj_xyd": (rows.v_max, 3) if want_reproj else None})
 
 
 def fusion_vis_filter(ref_depth, reproj_xyd, dist_base=4.0, rel_diff_base=1300.0, thres_view=2, relative=False):
@@ -1040,28 +1021,9 @@ def fusion_dtu_filter(ref_depth, src_depths, ref_cam, src_cams, confidence=None,
     geometric-consistency filter.  ref_depth [h,w]; src_depths [V,h,w]; ref_cam [2,4,4]; src_cams [V,2,4,4]; confidence [ch,cw] (any
     size: resized to the depth size as cv2.resize does) or None -> dict(depth [h,w], photo_mask / geo_mask / mask [h,w] uint8,
     points [3,h,w] or None)."""
-    for name, t_ in (("ref_depth", ref_depth), ("src_depths", src_depths), ("ref_cam", ref_cam), ("src_cams", src_cams)):
-        _t(t_, name)
-    V, h, w = src_depths.shape
-    dev = ref_depth.device
-    if tuple(ref_depth.shape) != (h, w) or tuple(ref_cam.shape) != (2, 4, 4) or tuple(src_cams.shape) != (V, 2, 4, 4):
-        raise ValueError("fusion_dtu_filter: ref_depth [h,w], src_depths [V,h,w], ref_cam [2,4,4], src_cams [V,2,4,4]")
-    conf = None
-    if confidence is not None:
-        _t(confidence, "confidence")
-        conf = confidence if tuple(confidence.shape) == (h, w) else resize_planar(confidence.reshape(1, *confidence.shape[-2:]).contiguous(), h, w)[0]
-    out = {"depth": torch.empty(h, w, device=dev, dtype=torch.float32),
-           "photo_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "geo_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(3, h, w, device=dev, dtype=torch.float32) if want_points else None}
-    scratch = torch.empty(52 * (V + 1), device=dev, dtype=torch.float32)
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (1 + V + 1 + 1 + (3 if want_points else 0)) + 3.0 * h * w}
-    check(_call("fusion_dtu_filter", work, _lib.lib().effi_fusion_dtu_filter_f32, _p(ref_depth), _p(src_depths), _p(ref_cam), _p(src_cams),
-                V, h, w, _p(conf), float(conf_threshold), float(conf_keep), int(s), int(e), float(dist_base), float(diff_base), _p(scratch),
-                _p(out["depth"]), _p(out["photo_mask"]), _p(out["geo_mask"]), _p(out["mask"]), _p(out["points"]), _stream()),
-          "effi_fusion_dtu_filter_f32")
-    return out
+    rows = _view_inputs("fusion_dtu_filter", ref_depth, src_depths, ref_cam, src_cams)
+    return _fusion_dtu("fusion_dtu_filter", _lib.lib().effi_fusion_dtu_filter_f32,
+                       rows, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, want_points)
 
 
 def fusion_pair_table(pair_data):
@@ -1081,6 +1043,31 @@ def fusion_pair_table(pair_data):
     return table
 
 
+class _FusionRows(NamedTuple):
+    """The views of one filter launch, single-view or scan: ``head`` = the entry's leading arguments up to ``h, w`` (``keep`` holds
+    the tensors it points into), ``lead`` = the outputs' leading shape, () or (n_ref,)."""
+    head: tuple
+    keep: tuple
+    lead: tuple
+    h: int
+    w: int
+    n_rows: int
+    v_max: int
+    n_src: int          # source maps read, over all rows
+
+
+def _view_inputs(what, ref_depth, src_depths, ref_cam, src_cams):
+    for name, t_ in (("ref_depth", ref_depth), ("src_depths", src_depths), ("ref_cam", ref_cam), ("src_cams", src_cams)):
+        _t(t_, name)
+    if src_depths.dim() != 3:
+        raise ValueError(f"{what}: src_depths [V,h,w] expected")
+    V, h, w = src_depths.shape
+    if tuple(ref_depth.shape) != (h, w) or tuple(ref_cam.shape) != (2, 4, 4) or tuple(src_cams.shape) != (V, 2, 4, 4):
+        raise ValueError(f"{what}: ref_depth [h,w], src_depths [V,h,w], ref_cam [2,4,4], src_cams [V,2,4,4]")
+    keep = (ref_depth, src_depths, ref_cam, src_cams)
+    return _FusionRows(tuple(map(_p, keep)) + (V,), keep, (), h, w, 1, V, V)
+
+
 def _scan_inputs(what, depths, cams, pairs):
     _t(depths, "depths"), _t(cams, "cams")
     if depths.dim() != 3 or tuple(cams.shape) != (depths.shape[0], 2, 4, 4):
@@ -1089,7 +1076,70 @@ def _scan_inputs(what, depths, cams, pairs):
             or pairs.shape[0] < 1:
         raise ValueError(f"{what}: pairs must be the int32 CPU table [n_ref, 1 + v_max] of ops.fusion_pair_table")
     pairs = pairs.contiguous()
-    return pairs, pairs.to(depths.device)
+    pairs_dev = pairs.to(depths.device)
+    n_views, h, w = depths.shape
+    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
+    return _FusionRows((_p(depths), _p(cams), n_views, _p(pairs), _p(pairs_dev), n_ref, v_max), (depths, cams, pairs, pairs_dev), (n_ref,),
+                       h, w, n_ref, v_max, int((pairs[:, 1:] >= 0).sum()))
+
+
+def _fusion_conf(what, name, conf, rows, resize=False):
+    """A launch's confidence, [ch,cw] or for a scan [n_ref,ch,cw] in table order, or None -> the entry's (conf, ch, cw); with
+    ``resize`` (DTU) brought to the depth size as cv2.resize does -> (conf,)."""
+    if conf is not None:
+        _t(conf, name)
+        if rows.lead and (conf.dim() != 3 or conf.shape[0] != rows.n_rows):
+            raise ValueError(f"{what}: {name} [n_ref,ch,cw] expected, got {tuple(conf.shape)}")
+    if resize:
+        if conf is not None and tuple(conf.shape[-2:]) != (rows.h, rows.w):
+            conf = resize_planar(conf.reshape(rows.n_rows, *conf.shape[-2:]).contiguous(), rows.h, rows.w).reshape(*rows.lead, rows.h, rows.w)
+        return (conf,)
+    if conf is None:
+        return None, 0, 0
+    ch, cw = conf.shape[len(rows.lead):]
+    return conf, ch, cw
+
+
+_TT_MASKS, _DTU_MASKS = ("geo_mask", "prob_mask", "mask"), ("photo_mask", "geo_mask", "mask")      # in the entries' argument order
+
+
+def _fusion_out(rows, masks, want_points, reproj=None):
+    """The result dict in the entry's output order; ``reproj``: {key: leading shape or None} of a single view's by-products."""
+    z = lambda *sh, dt=torch.float32: torch.empty(*sh, rows.h, rows.w, device=rows.keep[0].device, dtype=dt)
+    out = {"depth": z(*rows.lead)}
+    out.update((k, z(*rows.lead, dt=torch.uint8)) for k in masks)
+    out["points"] = z(*rows.lead, 3) if want_points else None
+    out.update((k, None if sh is None else z(*sh)) for k, sh in (reproj or {}).items())
+    return out
+
+
+def _fusion_launch(key, fn, rows, conf, params, out, maps, extra=0):
+    """Entry ``fn`` (``effi_<key>_f32``) under the profile key ``key``; ``maps`` = fp32 maps per row besides the sources and the points,
+    ``extra`` = further maps of the launch."""
+    scratch = torch.empty(52 * rows.n_rows * (rows.v_max + 1), device=rows.keep[0].device, dtype=torch.float32)
+    px, n = rows.h * rows.w, rows.n_rows
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * px * (rows.n_src + n * (maps + (0 if out["points"] is None else 3)) + extra) + 3.0 * n * px}
+    check(_call(key, work, fn, *rows.head, rows.h, rows.w, _p(conf[0]), *conf[1:], *params, _p(scratch),
+                *map(_p, out.values()), _stream()), f"effi_{key}_f32")
+    return out
+
+
+def _fusion_dynamic(key, fn, rows, ref_conf, prob_threshold, dh_view_num, dist_base, rel_diff_base, relative, want_points, reproj=None):
+    conf = _fusion_conf(key, "ref_conf", ref_conf, rows)
+    params = (float(prob_threshold), int(dh_view_num), float(dist_base), float(rel_diff_base), int(bool(relative)))
+    return _fusion_launch(key, fn, rows, conf, params, _fusion_out(rows, _TT_MASKS, want_points, reproj), 2)
+
+
+def _fusion_static(key, fn, rows, ref_conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh, want_points, reproj=None, extra=0):
+    conf = _fusion_conf(key, "ref_conf", ref_conf, rows)
+    params = (float(prob_threshold), float(img_dist_thresh), float(depth_thresh), float(vthresh))
+    return _fusion_launch(key, fn, rows, conf, params, _fusion_out(rows, _TT_MASKS, want_points, reproj), 2, extra)
+
+
+def _fusion_dtu(key, fn, rows, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, want_points):
+    conf = _fusion_conf(key, "confidence", confidence, rows, resize=True)
+    params = (float(conf_threshold), float(conf_keep), int(s), int(e), float(dist_base), float(diff_base))
+    return _fusion_launch(key, fn, rows, conf, params, _fusion_out(rows, _DTU_MASKS, want_points), 3)
 
 
 def fusion_dtu_filter_scan(depths, cams, pairs, confidence=None, conf_threshold=0.5, conf_keep=0.75, s=1, e=11, dist_base=0.5,
@@ -1098,29 +1148,9 @@ def fusion_dtu_filter_scan(depths, cams, pairs, confidence=None, conf_threshold=
     cams [n_views,2,4,4] are read in place through ``pairs`` (``fusion_pair_table``: each reference view its own source count, at most
     16); confidence [n_ref,ch,cw] in table order (any size) or None -> dict(depth [n_ref,h,w], photo_mask / geo_mask / mask
     [n_ref,h,w] uint8, points [n_ref,3,h,w] or None); row r is bitwise ``fusion_dtu_filter`` on reference view r and its stacked sources."""
-    pairs, pairs_dev = _scan_inputs("fusion_dtu_filter_scan", depths, cams, pairs)
-    n_views, h, w = depths.shape
-    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
-    dev = depths.device
-    conf = None
-    if confidence is not None:
-        _t(confidence, "confidence")
-        if confidence.dim() != 3 or confidence.shape[0] != n_ref:
-            raise ValueError(f"fusion_dtu_filter_scan: confidence [n_ref,ch,cw] expected, got {tuple(confidence.shape)}")
-        conf = confidence if tuple(confidence.shape[1:]) == (h, w) else resize_planar(confidence, h, w)
-    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
-           "photo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
-    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
-    n_src = int((pairs[:, 1:] >= 0).sum())
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (3 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
-    check(_call("fusion_dtu_filter_scan", work, _lib.lib().effi_fusion_dtu_filter_scan_f32, _p(depths), _p(cams), n_views, _p(pairs),
-                _p(pairs_dev), n_ref, v_max, h, w, _p(conf), float(conf_threshold), float(conf_keep), int(s), int(e), float(dist_base),
-                float(diff_base), _p(scratch), _p(out["depth"]), _p(out["photo_mask"]), _p(out["geo_mask"]), _p(out["mask"]),
-                _p(out["points"]), _stream()), "effi_fusion_dtu_filter_scan_f32")
-    return out
+    rows = _scan_inputs("fusion_dtu_filter_scan", depths, cams, pairs)
+    return _fusion_dtu("fusion_dtu_filter_scan", _lib.lib().effi_fusion_dtu_filter_scan_f32,
+                       rows, confidence, conf_threshold, conf_keep, s, e, dist_base, diff_base, want_points)
 
 
 def fusion_dynamic_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshold=0.0, dh_view_num=2, dist_base=4.0,
@@ -1128,29 +1158,9 @@ def fusion_dynamic_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshol
     """``fusion_dynamic_filter`` for every reference view of a scan in ONE launch (test_tank.py:466-512); arguments as
     ``fusion_dtu_filter_scan``, ref_conf [n_ref,ch,cw] in table order or None -> dict(depth [n_ref,h,w], geo_mask / prob_mask / mask
     [n_ref,h,w] uint8, points [n_ref,3,h,w] or None).  Every row needs at least ``dh_view_num`` sources."""
-    pairs, pairs_dev = _scan_inputs("fusion_dynamic_filter_scan", depths, cams, pairs)
-    n_views, h, w = depths.shape
-    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
-    dev = depths.device
-    ch = cw = 0
-    if ref_conf is not None:
-        _t(ref_conf, "ref_conf")
-        if ref_conf.dim() != 3 or ref_conf.shape[0] != n_ref:
-            raise ValueError(f"fusion_dynamic_filter_scan: ref_conf [n_ref,ch,cw] expected, got {tuple(ref_conf.shape)}")
-        ch, cw = ref_conf.shape[1:]
-    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
-           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "prob_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
-    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
-    n_src = int((pairs[:, 1:] >= 0).sum())
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (2 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
-    check(_call("fusion_dynamic_filter_scan", work, _lib.lib().effi_fusion_dynamic_filter_scan_f32, _p(depths), _p(cams), n_views,
-                _p(pairs), _p(pairs_dev), n_ref, v_max, h, w, _p(ref_conf), ch, cw, float(prob_threshold), int(dh_view_num),
-                float(dist_base), float(rel_diff_base), int(bool(relative)), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]),
-                _p(out["prob_mask"]), _p(out["mask"]), _p(out["points"]), _stream()), "effi_fusion_dynamic_filter_scan_f32")
-    return out
+    rows = _scan_inputs("fusion_dynamic_filter_scan", depths, cams, pairs)
+    return _fusion_dynamic("fusion_dynamic_filter_scan", _lib.lib().effi_fusion_dynamic_filter_scan_f32,
+                           rows, ref_conf, prob_threshold, dh_view_num, dist_base, rel_diff_base, relative, want_points)
 
 
 def fusion_static_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf=None, prob_threshold=0.0, img_dist_thresh=1.0,
@@ -1158,61 +1168,21 @@ def fusion_static_filter(ref_depth, src_depths, ref_cam, src_cams, ref_conf=None
     """Scope row n3, the fixed-threshold visibility filter: get_reproj + vis_filter + ave_fusion (misc/fusion.py:79-115) and the
     driver's masks and points (test_tank.py:471-475,512-515) for one reference view in ONE kernel.  Arguments and result as
     ``fusion_dynamic_filter``; with ``want_reproj`` also ``in_range`` [V,h,w] (0/1 floats), get_reproj's second result."""
-    for name, t_ in (("ref_depth", ref_depth), ("src_depths", src_depths), ("ref_cam", ref_cam), ("src_cams", src_cams)):
-        _t(t_, name)
-    if src_depths.dim() != 3:
-        raise ValueError("fusion_static_filter: src_depths [V,h,w] expected")
-    V, h, w = src_depths.shape
-    dev = ref_depth.device
-    if tuple(ref_depth.shape) != (h, w) or tuple(ref_cam.shape) != (2, 4, 4) or tuple(src_cams.shape) != (V, 2, 4, 4):
-        raise ValueError("fusion_static_filter: ref_depth [h,w], src_depths [V,h,w], ref_cam [2,4,4], src_cams [V,2,4,4]")
-    ch = cw = 0
-    if ref_conf is not None:
-        _t(ref_conf, "ref_conf")
-        ch, cw = ref_conf.shape
-    out = {"depth": torch.empty(h, w, device=dev, dtype=torch.float32),
-           "geo_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "prob_mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(3, h, w, device=dev, dtype=torch.float32) if want_points else None,
-           "reproj_xyd": torch.empty(V, 3, h, w, device=dev, dtype=torch.float32) if want_reproj else None,
-           "in_range": torch.empty(V, h, w, device=dev, dtype=torch.float32) if want_reproj else None}
-    scratch = torch.empty(52 * (V + 1), device=dev, dtype=torch.float32)
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (1 + V + 1 + (3 if want_points else 0) + (4 * V if want_reproj else 0)) + 3.0 * h * w}
-    check(_call("fusion_static_filter", work, _lib.lib().effi_fusion_static_filter_f32, _p(ref_depth), _p(src_depths), _p(ref_cam),
-                _p(src_cams), V, h, w, _p(ref_conf), ch, cw, float(prob_threshold), float(img_dist_thresh), float(depth_thresh),
-                float(vthresh), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]), _p(out["prob_mask"]), _p(out["mask"]),
-                _p(out["points"]), _p(out["reproj_xyd"]), _p(out["in_range"]), _stream()), "effi_fusion_static_filter_f32")
-    return out
+    rows = _view_inputs("fusion_static_filter", ref_depth, src_depths, ref_cam, src_cams)
+    V = rows.v_max
+    return _fusion_static("fusion_static_filter", _lib.lib().effi_fusion_static_filter_f32,
+                          rows, ref_conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh, want_points,
+                          {"reproj_xyd": (V, 3) if want_reproj else None, "in_range": (V,) if want_reproj else None},
+                          4 * V if want_reproj else 0)
 
 
 def fusion_static_filter_scan(depths, cams, pairs, ref_conf=None, prob_threshold=0.0, img_dist_thresh=1.0, depth_thresh=0.01, vthresh=4,
                               want_points=True):
     """``fusion_static_filter`` for every reference view of a scan in ONE launch; arguments and result as
     ``fusion_dynamic_filter_scan``.  Every row needs at least one source; row r is bitwise the single-view launch."""
-    pairs, pairs_dev = _scan_inputs("fusion_static_filter_scan", depths, cams, pairs)
-    n_views, h, w = depths.shape
-    n_ref, v_max = pairs.shape[0], pairs.shape[1] - 1
-    dev = depths.device
-    ch = cw = 0
-    if ref_conf is not None:
-        _t(ref_conf, "ref_conf")
-        if ref_conf.dim() != 3 or ref_conf.shape[0] != n_ref:
-            raise ValueError(f"fusion_static_filter_scan: ref_conf [n_ref,ch,cw] expected, got {tuple(ref_conf.shape)}")
-        ch, cw = ref_conf.shape[1:]
-    out = {"depth": torch.empty(n_ref, h, w, device=dev, dtype=torch.float32),
-           "geo_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "prob_mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "mask": torch.empty(n_ref, h, w, device=dev, dtype=torch.uint8),
-           "points": torch.empty(n_ref, 3, h, w, device=dev, dtype=torch.float32) if want_points else None}
-    scratch = torch.empty(52 * n_ref * (v_max + 1), device=dev, dtype=torch.float32)
-    n_src = int((pairs[:, 1:] >= 0).sum())
-    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (n_src + n_ref * (2 + (3 if want_points else 0))) + 3.0 * n_ref * h * w}
-    check(_call("fusion_static_filter_scan", work, _lib.lib().effi_fusion_static_filter_scan_f32, _p(depths), _p(cams), n_views, _p(pairs),
-                _p(pairs_dev), n_ref, v_max, h, w, _p(ref_conf), ch, cw, float(prob_threshold), float(img_dist_thresh),
-                float(depth_thresh), float(vthresh), _p(scratch), _p(out["depth"]), _p(out["geo_mask"]), _p(out["prob_mask"]),
-                _p(out["mask"]), _p(out["points"]), _stream()), "effi_fusion_static_filter_scan_f32")
-    return out
+    rows = _scan_inputs("fusion_static_filter_scan", depths, cams, pairs)
+    return _fusion_static("fusion_static_filter_scan", _lib.lib().effi_fusion_static_filter_scan_f32,
+                          rows, ref_conf, prob_threshold, img_dist_thresh, depth_thresh, vthresh, want_points)
 
 
 def fusion_project_img(src_img, dst_depth, src_cam, dst_cam, height=None, width=None):

@@ -336,7 +336,7 @@ def pixel_grid(h, w):
 
 
 def tt_chain(A, ref_depth, src_depths, mats, relative, mutant=None):
-    """fusion_dynamic_filter_pixel up to the comparisons (fusion.hip:149-180), for all pixels at once.  mats: prepare_view of the
+    """FusDynamic::pixel (fusion.hip) up to the comparisons, for all pixels at once.  mats: prepare_view of the
     reference view, then of the sources.  -> dict of per-view lists (reprojected x, y, depth; cdiff; ddiff) and the pixel's own."""
     h, w = ref_depth.shape
     ys, xs = pixel_grid(h, w)
@@ -391,7 +391,7 @@ def prob_mask_exact(conf, h, w, prob_thr, rounded=False):
 
 def tt_restate(ref_depth, src_depths, ref_cam, src_cams, conf=None, prob_thr=0.0, dh=2, dist_base=4.0, rel_base=1300.0,
                relative=False, mutant=None, mats=None):
-    """fusion_dynamic_filter_pixel op for op in numpy float32.  -> dict(depth [n], geo / prob / mask [n] bool, points [3,n],
+    """FusDynamic::pixel op for op in numpy float32.  -> dict(depth [n], geo / prob / mask [n] bool, points [3,n],
     xyd [V,3,n], m [V,nthr,n] bool).  mutant: None or one of the T&T names of MUTANTS."""
     ref_depth, src_depths = np.asarray(ref_depth, f32), np.asarray(src_depths, f32)
     h, w = ref_depth.shape
@@ -468,7 +468,7 @@ class Decision:
 
 def tt_reference(ref_depth, src_depths, ref_cam, src_cams, conf=None, prob_thr=0.0, dh=2, dist_base=4.0, rel_base=1300.0,
                  relative=False):
-    """The float64 interval reference of fusion_dynamic_filter_pixel.  -> dict: xyd B [V][3], T / Un [V,nthr,n] (comparison true /
+    """The float64 interval reference of FusDynamic::pixel.  -> dict: xyd B [V][3], T / Un [V,nthr,n] (comparison true /
     undecided), left [V,n] (left-out views), geo / mask Decision, prob bool (pinned), depth B, points [3] B, nund [n] (undecided
     views of the averaging set), near: (value - threshold, bound) of every component comparison, for the bite statistics."""
     ref_depth, src_depths = np.asarray(ref_depth, f32), np.asarray(src_depths, f32)
@@ -671,7 +671,7 @@ def _dtu_mats(A, ref_cam, src_cams, inv=gauss_jordan):
 
 def dtu_restate(ref_depth, src_depths, ref_cam, src_cams, conf=None, conf_thr=0.5, conf_keep=0.75, s_lo=1, e_hi=11, dist_base=0.5,
                 diff_base=0.25, mutant=None):
-    """fusion_dtu_filter_pixel op for op (float64 chain, float32 islands).  -> dict(depth f32 [n], photo / geo / final bool, points
+    """FusDtu::pixel op for op (float64 chain, float32 islands).  -> dict(depth f32 [n], photo / geo / final bool, points
     f32 [3,n], out5 [V,5,n] f32 (reproject outputs per view, unzeroed), masks [V,nthr,n] bool)."""
     ref_depth, src_depths = np.asarray(ref_depth, f32), np.asarray(src_depths, f32)
     h, w = ref_depth.shape

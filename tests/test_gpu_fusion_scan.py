@@ -144,6 +144,43 @@ def test_scan_launches_refuse_17_sources_and_ids_outside_the_scan():
     assert tuple(ops.fusion_dtu_filter_scan(d, cams, ok)["depth"].shape) == (1, 7, 9)
 
 
+def test_one_row_table_is_the_single_view_launch_for_all_three_filters():
+    """One kernel under its two addressings at 5x7 (one partial workgroup, odd width): the table [0, 1, 2, 3] over four views names
+    what the single-view form gets as (reference, stacked sources), so every output is bitwise the same; both forms refuse h = 1."""
+    from effi_mvs_plus_amd import ops
+    from effi_mvs_plus_amd._lib import EffiLibraryError
+    h, w = 5, 7
+    table = ops.fusion_pair_table([(0, [1, 2, 3])])
+    assert table.tolist() == [[0, 1, 2, 3]]
+    conf = t(torch.rand(1, 3, 4, generator=torch.Generator().manual_seed(11)), DEV)
+    dtu_rig = synth.synth_depth_maps(h, w, 4, seed=3, noise_mm=0.03, outlier_frac=0.08, pixel_center=0.0)
+    tank_rig = synth.synth_depth_maps(h, w, 4, seed=4)
+    for rig, scan, single, kw in (
+            (dtu_rig, ops.fusion_dtu_filter_scan, ops.fusion_dtu_filter, dict(conf_threshold=0.3)),
+            (tank_rig, ops.fusion_dynamic_filter_scan, ops.fusion_dynamic_filter, dict(prob_threshold=0.3, dh_view_num=2, rel_diff_base=1.3)),
+            (tank_rig, ops.fusion_static_filter_scan, ops.fusion_static_filter, dict(prob_threshold=0.3))):
+        d, cams = t(rig[0], DEV), t(rig[1], DEV)
+        got = scan(d, cams, table, conf, **kw)
+        want = single(d[0].contiguous(), d[1:].contiguous(), cams[0].contiguous(), cams[1:].contiguous(), conf[0].contiguous(), **kw)
+        assert len(got) == 5
+        for k, v in got.items():
+            assert tuple(v.shape[:1]) == (1,) and torch.equal(v[0], want[k]), (single.__name__, k)
+        flat = d[:, :1].contiguous()                                       # h = 1
+        with pytest.raises(EffiLibraryError):
+            scan(flat, cams, table, **kw)
+        with pytest.raises(EffiLibraryError):
+            single(flat[0].contiguous(), flat[1:].contiguous(), cams[0].contiguous(), cams[1:].contiguous(), **kw)
+    # a single view of 2^31 pixels is past the kernel's int pixel index: EFFI_ERR_BADARG from every single-view entry, before any launch.
+    # The pointers are one small tensor's address: nothing may read or write through them.  That holds because each entry returns from
+    # fus_check (null pointers, sizes, then this limit) before fus_run launches anything; keep that order, or give these calls real maps.
+    L, p, s = ops._lib.lib(), d.data_ptr(), ops._stream()
+    assert L.effi_fusion_dynamic_filter_f32(p, p, p, p, 3, 65536, 32768, None, 0, 0, 0.3, 2, 4.0, 1.3, 0, p, p, None, None, None, None, None, s) == -1
+    assert L.effi_fusion_dtu_filter_f32(p, p, p, p, 3, 65536, 32768, None, 0.3, 0.75, 1, 11, 0.5, 0.25, p, p, None, None, None, None, s) == -1
+    assert L.effi_fusion_static_filter_f32(p, p, p, p, 3, 65536, 32768, None, 0, 0, 0.3, 1.0, 0.01, 4.0, p, p, None, None, None, None, None, None,
+                                           s) == -1
+    torch.cuda.synchronize()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. compaction == numpy boolean indexing
 # ---------------------------------------------------------------------------------------------------------------------------
