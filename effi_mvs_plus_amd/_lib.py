@@ -51,6 +51,9 @@ SIGNATURES = {
     "effi_mvs_loss_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "effi_mvs_loss_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "effi_depth_metrics_f32": [_vp, _vp, _vp, _i, _l, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    # optimizer step (csrc/optim.hip)
+    "effi_adamw_max_tensors": [],
+    "effi_adamw_multi_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _d, _d, _d, _vp],
     "effi_fusion_vis_filter_f32": [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp],
     "effi_fusion_points_f32": [_i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_dtu_reproject_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],

@@ -1475,6 +1475,60 @@ def mvs_loss_bwd(ests, gts, masks, weights, count, grad_total):
     return grads
 
 
+# ---- optimizer step (csrc/optim.hip; the caller is optim.FusedAdamW) ----
+def adamw_max_tensors():
+    """Most tensors one ``effi_adamw_multi_f32`` call takes (host-only query: needs no GPU)."""
+    return int(_lib.lib().effi_adamw_max_tensors())
+
+
+def _adamw_slices(n, k):
+    """[(start, stop)] of the launches that cover n tensors in order, at most k per launch."""
+    return [(s, min(n, s + k)) for s in range(0, n, k)]
+
+
+def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay):
+    """One AdamW step (train.py:263,441; torch.optim.AdamW, amsgrad=False, maximize=False) IN PLACE over lists of tensors: two launches
+    per ``adamw_max_tensors()`` tensors.  params / exp_avgs / exp_avg_sqs are updated, steps (0-dim fp32 device tensors, one per
+    parameter) are incremented first, grads are only read.  lr: a number, or a one-element fp32 device tensor the kernel reads when
+    it runs (a captured step then follows a scheduler that fills it)."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
+        raise ValueError("adamw_multi: one gradient, exp_avg, exp_avg_sq and step per parameter expected")
+    if n == 0:
+        return
+    dev, f32 = _t(params[0], "params[0]").device, torch.float32
+    idx = dev.index
+    names = ("params", "grads", "exp_avgs", "exp_avg_sqs", "steps")
+    pp, pg, pm, pv, ps, numel = [], [], [], [], [], []
+    for i in range(n):
+        five = (params[i], grads[i], exp_avgs[i], exp_avg_sqs[i], steps[i])
+        for k, x in enumerate(five):
+            # the checks of _t, once per call and device instead of 1,210 times per step of the model; _t words the refusal
+            if not isinstance(x, torch.Tensor) or x.dtype is not f32 or x.get_device() != idx or not x.is_contiguous():
+                _t(x, f"{names[k]}[{i}]")
+                raise ValueError(f"adamw_multi: {names[k]}[{i}] lives on {x.device}, params[0] on {dev}: one device per call")
+        p, g, m, v, c = five
+        ne = p.numel()
+        if g.numel() != ne or m.numel() != ne or v.numel() != ne or c.numel() != 1:
+            raise ValueError(f"adamw_multi: tensor {i}: gradient and moments of the parameter's {ne} elements and a one-element step expected")
+        # an empty tensor has no storage (data_ptr() == 0) and the entry refuses null pointers: it gets its step counter's address,
+        # which the kernel never reads through (no chunk belongs to a tensor without elements); its counter is incremented like the others
+        cp = c.data_ptr()
+        pp.append(p.data_ptr() or cp), pg.append(g.data_ptr() or cp), pm.append(m.data_ptr() or cp), pv.append(v.data_ptr() or cp)
+        ps.append(cp), numel.append(ne)
+    lr_dev = None
+    if isinstance(lr, torch.Tensor):
+        lr_dev = _t(lr, "lr")
+        if lr_dev.numel() != 1 or lr_dev.device != dev:
+            raise ValueError("adamw_multi: a tensor lr is one fp32 element on the parameters' device")
+    fn, st = _lib.lib().effi_adamw_multi_f32, _stream()
+    lrv = 0.0 if lr_dev is not None else float(lr)
+    for s, e in _adamw_slices(n, adamw_max_tensors()):
+        arr = C.c_void_p * (e - s)
+        check(fn(arr(*pp[s:e]), arr(*pg[s:e]), arr(*pm[s:e]), arr(*pv[s:e]), arr(*ps[s:e]), (C.c_long * (e - s))(*numel[s:e]), e - s, lrv,
+                 _p(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), st), "effi_adamw_multi_f32")
+
+
 def depth_metrics(est, gt, mask, thresholds=(), bands=(), acc=None):
     """Thres_metrics / AbsDepthError_metrics (utils.py:139-160) for all thresholds and bands in one pass (two launches): est / gt /
     mask [B,H,W]; thresholds: up to 8 numbers; bands: up to 8 (lo, hi) pairs, both ends inclusive.  -> (scalars [1 + T + R] fp32 =

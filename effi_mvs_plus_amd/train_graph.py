@@ -46,6 +46,7 @@ import torch
 from . import metrics as _metrics
 from .graph import ReplayGraph
 from .models.module import mvs_loss_fused, _mvs_loss_fused_vector, mvs_loss_static  # noqa: F401  (re-exported: the losses a graphed step uses)
+from .optim import FusedAdamW  # noqa: F401  (re-exported: AdamW on csrc/optim.hip, a drop-in for torch.optim.AdamW(capturable=True) here)
 
 DLOSS = (1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4)            # train.py:246: stage of each of the 13 depth maps
 

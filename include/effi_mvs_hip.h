@@ -1008,6 +1008,27 @@ int effi_depth_metrics_f32(const float* est, const float* gt, const void* mask, 
                            int n_thres, const float* band_lo, const float* band_hi, int n_bands, long long* counts, double* sums,
                            float* scalars, double* acc, void* scratch, effi_stream_t stream);
 
+/* ---- The optimizer step of train_sample (train.py:263 optimizer.step() on the AdamW of train.py:441), csrc/optim.hip: decoupled
+ * weight-decay AdamW (torch.optim.AdamW with amsgrad=False, maximize=False) over n tensors in two launches -- the step counters, then
+ * every element -- instead of torch's chain of _foreach_* launches.
+ * effi_adamw_max_tensors(): the most tensors one call takes (the table travels in the kernel argument).
+ * effi_adamw_multi_f32: p / g / exp_avg / exp_avg_sq / step / numel are HOST arrays of n entries (1 <= n <= effi_adamw_max_tensors()):
+ *   the device pointers of parameter, gradient, first and second moment (numel[i] fp32 elements each, numel[i] >= 0; any alignment:
+ *   128-bit accesses are used where all four are 16-byte aligned) and of the step counter, ONE fp32 element per tensor as torch's
+ *   capturable AdamW keeps it.  The arrays are copied into the kernel argument: nothing is read from them after the call returns, a
+ *   captured launch holds the pointers and a replay needs nothing from the host.  lr_dev (optional DEVICE pointer to one fp32) is
+ *   read by the kernel when it runs and then replaces lr: a scheduler writes it between replays.  Per tensor: step += 1 first, then
+ *   with t = the new step, in double, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, and the scalars 1 - lr weight_decay, 1 - beta1, beta2,
+ *   1 - beta2, lr / bc1, sqrt(bc2), eps rounded once to fp32; per element in fp32, one rounding per operation:
+ *   p *= 1 - lr wd;  m += (g - m)(1 - beta1);  v = v beta2 + ((1 - beta2) g) g;  p -= ((lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps).
+ *   g is only read; nothing is written outside the numel[i] elements of p, exp_avg, exp_avg_sq and the one of step.
+ *   EFFI_ERR_BADARG before any launch: n out of range, a null array or a null pointer among the first n of an array, numel[i] < 0,
+ *   more than 2^31 - 1 chunks of 2048 elements in all, a beta outside [0, 1), eps < 0 (NaN is refused too). */
+int effi_adamw_max_tensors(void);
+int effi_adamw_multi_f32(float* const* p, const float* const* g, float* const* exp_avg, float* const* exp_avg_sq, float* const* step,
+                         const long* numel, int n, double lr, const float* lr_dev, double beta1, double beta2, double eps,
+                         double weight_decay, effi_stream_t stream);
+
 /* ---- tuning / A-B switches.  A table of named integers, initialised ONCE per process from the environment (variable EFFI_<NAME in
  * upper case>) and changed afterwards only through effi_set_option; no entry point reads the environment.  Names: warp_lds_kb
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One training step (forward in train mode -> mvs_loss -> backward -> AdamW step, train.py:229-263) at a DTU training shape:
 the HIP training path of this package against torch autograd through the oracle's op sequence with stock PyTorch-ROCm operators
-(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B]
+(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B] [--optimizer torch|fused]
+--optimizer fused: the HIP legs step effi_mvs_plus_amd.optim.FusedAdamW (csrc/optim.hip) instead of torch.optim.AdamW (default: torch).
 Environment: BENCH_TRAIN_NO_GRAPH, BENCH_TRAIN_HIP_ONLY, BENCH_TRAIN_DEPTH_RANGE=static|sample (the graphed step's mode)."""
 import os
 import sys
@@ -40,7 +41,14 @@ def timed(fn, n):
 
 
 def main():
-    H, W, N, B = (int(v) for v in (sys.argv[1:5] + ["512", "640", "5", "1"][len(sys.argv) - 1:]))
+    argv, optimizer = list(sys.argv[1:]), "torch"
+    if "--optimizer" in argv:
+        i = argv.index("--optimizer")
+        optimizer = argv[i + 1]
+        del argv[i:i + 2]
+    if optimizer not in ("torch", "fused"):
+        raise SystemExit("--optimizer torch|fused")
+    H, W, N, B = (int(v) for v in (argv[:4] + ["512", "640", "5", "1"][len(argv):]))
     nd = "48,8,8"
     net, sd = build_model(nd, seed=2, device=DEV)
     samples = [synth.synth_sample(H, W, N, seed=10 + b) for b in range(B)]
@@ -50,7 +58,13 @@ def main():
     gt, mask = loss_inputs(H, W, B, 1)
 
     net.train()
-    opt = torch.optim.AdamW(net.parameters(), lr=1e-5)
+    if optimizer == "fused":
+        from effi_mvs_plus_amd.optim import FusedAdamW
+        make_opt = lambda capturable: FusedAdamW(net.parameters(), lr=1e-5)                          # noqa: E731
+    else:
+        make_opt = lambda capturable: torch.optim.AdamW(net.parameters(), lr=1e-5, **({"capturable": True} if capturable else {}))   # noqa: E731
+    opt = make_opt(False)
+    print(f"optimizer: {optimizer} ({type(opt).__module__}.{type(opt).__name__})")
 
     def hip_step():
         opt.zero_grad(set_to_none=True)
@@ -65,7 +79,7 @@ def main():
     if not os.environ.get("BENCH_TRAIN_NO_GRAPH"):
         # the same step (static loss, capturable AdamW) captured into one HIP graph and replayed: no per-launch host work
         from effi_mvs_plus_amd import train_graph
-        opt_g = torch.optim.AdamW(net.parameters(), lr=1e-5, capturable=True)
+        opt_g = make_opt(True)
         # BENCH_TRAIN_DEPTH_RANGE=sample: the step that reads every sample's depth range on the device (profiles/train_range_ab.txt)
         mode = os.environ.get("BENCH_TRAIN_DEPTH_RANGE", "static")
         step = train_graph.GraphedTrainStep(net, opt_g, imgs, pm, dv, gt, mask, depth_range=mode)

@@ -4,7 +4,8 @@ names as there): host-mode ``datasets.blend`` samples out of DataLoader workers 
 reads every sample's own depth range on the device -> ``train_graph.train_epoch`` per epoch, a checkpoint per epoch.
 
 usage: finetune_blend.py --trainpath DIR --trainlist FILE --logdir DIR [--loadckpt CKPT] [--ndepths 48,8,8] [--numdepth 384]
-                         [--trainviews 3] [--batch_size 4] [--lr 0.001] [--wd 0.001] [--epochs 16] [--num_workers 4]"""
+                         [--trainviews 3] [--batch_size 4] [--lr 0.001] [--wd 0.001] [--epochs 16] [--num_workers 4]
+                         [--optimizer torch|fused]   (fused: optim.FusedAdamW on csrc/optim.hip; its checkpoints load into torch's AdamW)"""
 import argparse
 import os
 import sys
@@ -37,6 +38,8 @@ def parse_args(argv=None):
     p.add_argument("--GRUiters", type=str, default="3,3,3", help="iters")
     p.add_argument("--CostNum", type=int, default=3, help="CostNum")
     p.add_argument("--num_workers", type=int, default=4, help=f"DataLoader workers (at most {MAX_WORKERS})")
+    p.add_argument("--optimizer", choices=("torch", "fused"), default="torch",
+                   help="torch: torch.optim.AdamW(capturable=True); fused: effi_mvs_plus_amd.optim.FusedAdamW (the HIP kernel)")
     args = p.parse_args(argv)
     if not 0 <= args.num_workers <= MAX_WORKERS:
         p.error(f"--num_workers must be in 0..{MAX_WORKERS}")
@@ -56,7 +59,10 @@ def main(argv=None):
         print("loading model {}".format(args.loadckpt))
         model.load_state_dict(torch.load(args.loadckpt, map_location="cpu")["model"])
     model = model.to(dev).train()
-    optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8, capturable=True)   # train.py:441-442
+    if args.optimizer == "fused":
+        optimizer = train_graph.FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8)
+    else:
+        optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8, capturable=True)   # train.py:441-442
     dataset = blend.MVSDataset(args.trainpath, args.trainlist, "finetune", args.trainviews, args.numdepth, device="host")
     loader = DataLoader(dataset, args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=True)
     if len(loader) == 0:
