@@ -208,20 +208,41 @@ __device__ __forceinline__ void lookup1d_index(int Dp, float q_depth, float dmin
     w1 = ix - x0f;
     w0 = (x0f + 1.0f) - ix;
 }
-__device__ __forceinline__ float lookup1d_fetch(const float* __restrict__ vol, long dstride, int Dp, int x0, float w0, float w1) {
-    float r = 0.0f;
-    if (x0 >= 0 && x0 <= Dp - 1) r = vol[x0 * dstride] * w0;
-    if (x0 + 1 >= 0 && x0 + 1 <= Dp - 1) r = r + vol[(x0 + 1) * dstride] * w1;
+// The two taps of a position, WITHOUT branches around the loads: written as "if (tap in range) r = vol[..] * w" each tap is an
+// exec-masked block of its own (the compiler may not load speculatively) whose load is waited for before the next block starts --
+// per pixel of the generated-input convolution twelve serial round trips to memory.  Here both indices are clamped into the vector,
+// both values are loaded whatever the position (lookup1d_tap0 / _tap1 give the clamped indices), and lookup1d_blend SELECTS: the
+// multiplications and the addition are those of the branched form in the same order, so the result is bitwise the same -- also when
+// the tap that is not selected holds NaN or Inf (a select, never a multiplication by a zero weight).
+__device__ __forceinline__ int lookup1d_tap0(int Dp, int x0) { return min(max(x0, 0), Dp - 1); }
+__device__ __forceinline__ int lookup1d_tap1(int Dp, int x0) { return min(max(x0 + 1, 0), Dp - 1); }
+__device__ __forceinline__ float lookup1d_blend(int Dp, int x0, float w0, float w1, float v0, float v1) {
+    const bool in0 = (x0 >= 0) & (x0 <= Dp - 1), in1 = (x0 + 1 >= 0) & (x0 + 1 <= Dp - 1);
+    float r = in0 ? v0 * w0 : 0.0f;
+    r = in1 ? r + v1 * w1 : r;
     return r;
+}
+__device__ __forceinline__ float lookup1d_fetch(const float* __restrict__ vol, long dstride, int Dp, int x0, float w0, float w1) {
+    const float v0 = vol[lookup1d_tap0(Dp, x0) * dstride], v1 = vol[lookup1d_tap1(Dp, x0) * dstride];
+    return lookup1d_blend(Dp, x0, w0, w1, v0, v1);
 }
 // GetCost.forward for ONE pixel (models/Effi_MVS_plus.py:257-303 behind scale_inv_depth :138-148): NQ hypotheses at inverse depth
 // +-(NQ/2) intervals around the current estimate (module.py:554-570), looked up in the stage's two cached volumes -> cost[0..NQ) from
 // cur_vol, cost[NQ..2NQ) from reg_vol.  cur / reg point at the pixel's vector (element stride cds / rds).  Shared by
 // getcost_conv1x1_block (volume_ops.hip) and the generated-input convolution (conv2d_x3.hpp): one arithmetic, bitwise.
+// Three phases, so that the 2 * NQ * 2 taps of the pixel are in flight together and ONE wait covers them: every position, then every
+// load (lookup1d_fetch's clamped indices), then the blends.  cur_vol / reg_vol are the volumes' (workgroup-uniform) bases and cpo / rpo
+// the pixel's element offset in them.  off32 (uniform; the host has shown that each volume spans less than 2^31 bytes and has
+// non-negative strides, effi_vol_fits32): a tap's address is the uniform base + a 32-bit byte offset -- one multiply-add per tap and
+// one register, instead of a 64-bit multiply-add chain into a register pair.
+__host__ __device__ inline bool effi_vol_fits32(long npix, long ps, int D, long ds) {
+    return ps >= 0 && ds >= 0 && npix >= 1 && D >= 1 && ((npix - 1) * ps + (long)(D - 1) * ds + 1) * 4 < (1L << 31);
+}
 template <int NQ>
 __device__ __forceinline__ void effi_getcost_pixel(float inv_or_depth, int input_is_depth, const float* __restrict__ disp_range, int n_range,
-                                                   float itv, const float* __restrict__ cur, long cds, int Dcur,
-                                                   const float* __restrict__ reg, long rds, int Dreg, float rlo, float rhi, float (&cost)[2 * NQ]) {
+                                                   float itv, const float* __restrict__ cur_vol, long cpo, long cds, int Dcur,
+                                                   const float* __restrict__ reg_vol, long rpo, long rds, int Dreg, float rlo, float rhi,
+                                                   bool off32, float (&cost)[2 * NQ]) {
     float depth = inv_or_depth;
     if (!input_is_depth) depth = effi_inv_to_depth(depth, disp_range[0], disp_range[n_range - 1]);
     const float dv = effi_lk_rcp(depth);
@@ -229,17 +250,51 @@ __device__ __forceinline__ void effi_getcost_pixel(float inv_or_depth, int input
     const float smin = fmaxf(dv - half, 1e-4f);
     const float smax = fminf(fmaxf(dv + half, 1e-4f), 1e4f);
     const float step = (smax - smin) / (float)(NQ - 1);
+    // queries per batch: all of them up to NQ = 3 (the path); NQ = 4 in two halves (whole, getcost_conv1x1_kernel<4> goes from 60 to
+    // 84 registers and from 8 to 5 waves per SIMD)
+    constexpr int QB = NQ <= 3 ? NQ : 2;
+    static_assert(NQ % QB == 0, "whole batches");
 #pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-        const float s = fmaxf(smin + (float)k * step, 1e-5f);
-        const float qd = effi_lk_rcp(s);
-        // both volumes of a stage are equally long on the path: one position per query serves both (bitwise the same values)
-        int x0;
-        float w0, w1;
-        lookup1d_index(Dcur, qd, rlo, rhi, x0, w0, w1);
-        cost[k] = lookup1d_fetch(cur, cds, Dcur, x0, w0, w1);
-        if (Dreg != Dcur) lookup1d_index(Dreg, qd, rlo, rhi, x0, w0, w1);
-        cost[NQ + k] = lookup1d_fetch(reg, rds, Dreg, x0, w0, w1);
+    for (int k0 = 0; k0 < NQ; k0 += QB) {
+        int xc[QB], xr[QB];
+        float wc0[QB], wc1[QB], wr0[QB], wr1[QB];
+#pragma unroll
+        for (int k = 0; k < QB; ++k) {
+            const float s = fmaxf(smin + (float)(k0 + k) * step, 1e-5f);
+            const float qd = effi_lk_rcp(s);
+            // both volumes of a stage are equally long on the path: one position per query serves both (bitwise the same values)
+            lookup1d_index(Dcur, qd, rlo, rhi, xc[k], wc0[k], wc1[k]);
+            xr[k] = xc[k]; wr0[k] = wc0[k]; wr1[k] = wc1[k];
+            if (Dreg != Dcur) lookup1d_index(Dreg, qd, rlo, rhi, xr[k], wr0[k], wr1[k]);
+        }
+        float vc0[QB], vc1[QB], vr0[QB], vr1[QB];
+        if (off32) {
+            const unsigned cb = (unsigned)cpo * 4u, rb = (unsigned)rpo * 4u, cs = (unsigned)cds * 4u, rs = (unsigned)rds * 4u;
+            const char* cbase = reinterpret_cast<const char*>(cur_vol);
+            const char* rbase = reinterpret_cast<const char*>(reg_vol);
+#pragma unroll
+            for (int k = 0; k < QB; ++k) {
+                vc0[k] = *reinterpret_cast<const float*>(cbase + (size_t)(cb + (unsigned)lookup1d_tap0(Dcur, xc[k]) * cs));
+                vc1[k] = *reinterpret_cast<const float*>(cbase + (size_t)(cb + (unsigned)lookup1d_tap1(Dcur, xc[k]) * cs));
+                vr0[k] = *reinterpret_cast<const float*>(rbase + (size_t)(rb + (unsigned)lookup1d_tap0(Dreg, xr[k]) * rs));
+                vr1[k] = *reinterpret_cast<const float*>(rbase + (size_t)(rb + (unsigned)lookup1d_tap1(Dreg, xr[k]) * rs));
+            }
+        } else {
+            const float* __restrict__ cur = cur_vol + cpo;
+            const float* __restrict__ reg = reg_vol + rpo;
+#pragma unroll
+            for (int k = 0; k < QB; ++k) {
+                vc0[k] = cur[lookup1d_tap0(Dcur, xc[k]) * cds];
+                vc1[k] = cur[lookup1d_tap1(Dcur, xc[k]) * cds];
+                vr0[k] = reg[lookup1d_tap0(Dreg, xr[k]) * rds];
+                vr1[k] = reg[lookup1d_tap1(Dreg, xr[k]) * rds];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < QB; ++k) {
+            cost[k0 + k] = lookup1d_blend(Dcur, xc[k], wc0[k], wc1[k], vc0[k], vc1[k]);
+            cost[NQ + k0 + k] = lookup1d_blend(Dreg, xr[k], wr0[k], wr1[k], vr0[k], vr1[k]);
+        }
     }
 }
 

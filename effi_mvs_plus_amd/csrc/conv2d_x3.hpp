@@ -122,6 +122,7 @@ struct EncGenArgs {
     const float* w_c1; const float* b_c1;          // convc1: [6][hd], [hd]
     const float* w_d1; const float* b_d1;          // convd1 (7x7): [49][hd], [hd]
     int hd;
+    int off32;                                     // both volumes span less than 2^31 bytes (effi_vol_fits32): 32-bit tap offsets
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -464,8 +465,9 @@ __device__ __forceinline__ void conv2d_k3_bf16x3_tile(const Conv2dArgs a, int ti
             const int gy = y0 - 1 + row, gx = x0 - 1 + col;
             gin[i] = (p < APIX) & (gy >= 0) & (gy < h) & (gx >= 0) & (gx < w);
             const long pix = gin[i] ? (long)gy * w + gx : 0;
-            effi_getcost_pixel<3>(g.inv_depth[pix], 0, g.disp_range, g.n_range, itv, g.cur_vol + pix * g.cps, g.cds, g.Dcur,
-                                  g.reg_vol + pix * g.rps, g.rds, g.Dreg, g.dmin[pix * g.range_ps], g.dmax[pix * g.range_ps], gcost[i]);
+            effi_getcost_pixel<3>(g.inv_depth[pix], 0, g.disp_range, g.n_range, itv, g.cur_vol, pix * g.cps, g.cds, g.Dcur,
+                                  g.reg_vol, pix * g.rps, g.rds, g.Dreg, g.dmin[pix * g.range_ps], g.dmax[pix * g.range_ps], g.off32 != 0,
+                                  gcost[i]);
         }
     }
     if (GEN && gmode != 0) {

@@ -445,6 +445,7 @@ struct GetcostConvArgs {
     int hw; const float* weight; const float* bias; int cout; int relu; float* out;
     // split-resident outputs (effi_encoder_inputs_bf16x3_sr; nullptr: the fp32 maps above): see effi_sr_store4, common.hpp
     unsigned short* out_sr; unsigned short* out7_sr; int w, sr_hp, sr_wp;
+    int off32;               // both volumes span less than 2^31 bytes (effi_vol_fits32): 32-bit tap offsets
 };
 
 template <int NQ>
@@ -459,8 +460,8 @@ __device__ __forceinline__ void getcost_conv1x1_block(const GetcostConvArgs& g, 
     const int p = bx * TPB + threadIdx.x;
     if (p >= hw) return;
     float cost[2 * NQ];
-    effi_getcost_pixel<NQ>(inv_depth[p], input_is_depth, disp_range, n_range, interval[0], cur_vol + p * cps, cds, Dcur, reg_vol + p * rps_, rds,
-                           Dreg, dmin[p * range_ps], dmax[p * range_ps], cost);
+    effi_getcost_pixel<NQ>(inv_depth[p], input_is_depth, disp_range, n_range, interval[0], cur_vol, p * cps, cds, Dcur, reg_vol, p * rps_, rds,
+                           Dreg, dmin[p * range_ps], dmax[p * range_ps], g.off32 != 0, cost);
     for (int c0 = 0; c0 < cout; c0 += 8) {                 // cout % 8 == 0 (checked by the caller)
         float acc[8];
 #pragma unroll
@@ -831,8 +832,9 @@ extern "C" int effi_getcost_conv1x1_f32(const float* inv_depth, const float* dis
     if (cout % 8) return EFFI_ERR_UNSUPPORTED;
     const dim3 grid(effi_cdiv((long)h * w, TPB));
     hipStream_t st = effi_s(stream);
-    const GetcostConvArgs g{inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
-                            Dreg, dmin, dmax, range_ps, h * w, weight, bias, cout, relu, out};
+    GetcostConvArgs g{inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
+                      Dreg, dmin, dmax, range_ps, h * w, weight, bias, cout, relu, out};
+    g.off32 = effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds);
 #define EFFI_GC(NQ) hipLaunchKernelGGL(getcost_conv1x1_kernel<NQ>, grid, dim3(TPB), 0, st, g)
     switch (nq) {
         case 2: EFFI_GC(2); break;
@@ -864,7 +866,8 @@ static int encoder_inputs_launch(bool x3, const float* inv_depth, const float* d
     hipStream_t st = effi_s(stream);
     const GetcostConvArgs g{inv_depth, disp_range, n_range, 0, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
                             Dreg, dmin, dmax, range_ps, h * w, weight_c1, bias_c1, cout, 1, out_c1,
-                            reinterpret_cast<unsigned short*>(sr_c1), reinterpret_cast<unsigned short*>(sr_d1), w, hp, wp};
+                            reinterpret_cast<unsigned short*>(sr_c1), reinterpret_cast<unsigned short*>(sr_d1), w, hp, wp,
+                            effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds)};
 #define EFFI_EI(CO)                                                                                                                     \
     do {                                                                                                                                \
         if (x3) hipLaunchKernelGGL((encoder_inputs_kernel<3, CO, true>), grid, dim3(TPB), 0, st, g, weight_d1, bias_d1, h, w, out_d1, gx, gy, n7);  \
