@@ -1732,74 +1732,33 @@ __global__ __launch_bounds__(256) void conv2d_cout1_k3_kernel(const Conv2dArgs a
 // beat 16-channel chunks, persistent workgroups and a same-accumulator ("run-ordered") MFMA schedule -- each of
 // those costs registers, i.e. waves per SIMD, and the kernel is bound by its LDS->MFMA phase, not by global
 // latency -- so only that configuration is instantiated; CC / PERSIST stay as parameters for future A/B runs.
-template <int KS, int NT, int MR, int EPI>
-int launch2d_v2(const Conv2dArgs& a, hipStream_t st) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    hipLaunchKernelGGL((conv2d_mfma_v2_kernel<KS, NT, MR, EPI, 8, false>), dim3(ntiles), dim3(256), 0, st, a, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
+// Batched (ConvBatch): the rows-per-wave rule on the tile count of ALL images.  A pixel's accumulation order is (k-group, tap) whatever
+// the rows per wave, the chunk size or the kernel (v2 / the 16 x 16 kernel of unaligned rows), so image i has the bits of the
+// single-image launch whichever shape either rule picks.  Batched kernels exist for the epilogues of the feature pyramid.
 template <int KS, int NT, int EPI>
-int launch2d(const Conv2dArgs& a, hipStream_t st) {
-    const int mr = effi_pick_generic(KS, a.h, a.w, 1).rows;          // (launch_form.hpp; 0: rows of w % 4 != 0)
-    if (mr != 0) {
-        if (mr == 4) return launch2d_v2<KS, NT, 4, EPI>(a, st);
-        if (mr == 2) return launch2d_v2<KS, NT, 2, EPI>(a, st);
-        return launch2d_v2<KS, NT, (KS == 3 ? 1 : 2), EPI>(a, st);
+int launch2d(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    constexpr bool kBatch = EPI == EFFI_EPI_PLAIN || EPI == EFFI_EPI_ADD_UP2 || EPI == EFFI_EPI_NHWC;
+    if (bt && !kBatch) return EFFI_ERR_UNSUPPORTED;
+    const unsigned n = bt ? bt->n_img : 1;
+    const int rows = effi_pick_generic(KS, a.h, a.w, n).rows;          // (launch_form.hpp; 0: rows of w % 4 != 0)
+    if (rows == 0) {
+        const dim3 grid(effi_cdiv(a.w, 16), effi_cdiv(a.h, 16), n);
+        if (!bt) return effi_launch<conv2d_mfma_kernel<KS, NT, EPI>>(grid, 256, st, a);
+        if constexpr (EPI == EFFI_EPI_PLAIN) return effi_launch<conv2d_mfma_batch_kernel<KS, NT, EPI>>(grid, 256, st, a, *bt);
+        return EFFI_ERR_BADARG;                    // (the entry has rejected w % 4 != 0 for every other epilogue)
     }
-    dim3 grid(effi_cdiv(a.w, 16), effi_cdiv(a.h, 16));
-    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, NT, EPI>), grid, dim3(256), 0, st, a);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_switch<1, 2, 4>(rows, [&](auto MR) {
+        constexpr int mr = (KS != 3 && MR() == 1) ? 2 : MR();          // (a 1x1 convolution takes at least two rows)
+        const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * mr);
+        if constexpr (kBatch)
+            if (bt) return effi_launch<conv2d_mfma_v2_batch_kernel<KS, NT, mr, EPI, 8>>(dim3(ntiles, n), 256, st, a, *bt, tiles_x, ntiles);
+        return effi_launch<conv2d_mfma_v2_kernel<KS, NT, mr, EPI, 8, false>>(dim3(ntiles), 256, st, a, tiles_x, ntiles);
+    });
 }
 
-// Batched forms (ConvBatch): launch2d's rows-per-wave rule on the tile count of ALL images.  A pixel's accumulation order is (k-group,
-// tap) whatever the rows per wave, the chunk size or the kernel (v2 / the 16 x 16 kernel of unaligned rows), so image i has the bits
-// of the single-image launch whichever shape either rule picks.
-template <int KS, int NT, int MR, int EPI>
-int launch2d_v2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    hipLaunchKernelGGL((conv2d_mfma_v2_batch_kernel<KS, NT, MR, EPI, 8>), dim3(ntiles, b.n_img), dim3(256), 0, st, a, b, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-template <int KS, int NT, int EPI>
-int launch2d_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const int mr = effi_pick_generic(KS, a.h, a.w, b.n_img).rows;
-    if (mr != 0) {
-        if (mr == 4) return launch2d_v2_batch<KS, NT, 4, EPI>(a, b, st);
-        if (mr == 2) return launch2d_v2_batch<KS, NT, 2, EPI>(a, b, st);
-        return launch2d_v2_batch<KS, NT, (KS == 3 ? 1 : 2), EPI>(a, b, st);
-    }
-    if constexpr (EPI == EFFI_EPI_PLAIN) {
-        dim3 grid(effi_cdiv(a.w, 16), effi_cdiv(a.h, 16), b.n_img);
-        hipLaunchKernelGGL((conv2d_mfma_batch_kernel<KS, NT, EPI>), grid, dim3(256), 0, st, a, b);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    return EFFI_ERR_BADARG;                    // (the entry has rejected w % 4 != 0 for every other epilogue)
-}
-
-template <int KS, int EPI>
-int dispatch_nt_batch(const Conv2dArgs& a, const ConvBatch& b, int nt, hipStream_t st) {
-    switch (nt) {
-        case 1: return launch2d_batch<KS, 1, EPI>(a, b, st);
-        case 2: return launch2d_batch<KS, 2, EPI>(a, b, st);
-        case 3: return launch2d_batch<KS, 3, EPI>(a, b, st);
-        case 4: return launch2d_batch<KS, 4, EPI>(a, b, st);
-        case 6: return launch2d_batch<KS, 6, EPI>(a, b, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-}
-
-template <int KS, int EPI>
-int dispatch_nt(const Conv2dArgs& a, int nt, hipStream_t st) {
-    switch (nt) {
-        case 1: return launch2d<KS, 1, EPI>(a, st);
-        case 2: return launch2d<KS, 2, EPI>(a, st);
-        case 3: return launch2d<KS, 3, EPI>(a, st);
-        case 4: return launch2d<KS, 4, EPI>(a, st);
-        case 6: return launch2d<KS, 6, EPI>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+template <int KS, int EPI, int... NTS>
+int dispatch2d(const Conv2dArgs& a, int nt, hipStream_t st, const ConvBatch* bt) {
+    return effi_switch_nt<NTS...>(nt, [&](auto NT) { return launch2d<KS, NT(), EPI>(a, st, bt); });
 }
 
 }  // namespace
@@ -1820,27 +1779,24 @@ __global__ __launch_bounds__(256) void conv3d_planes_mfma_batch_kernel(const Con
 }
 }  // namespace
 
-template <int NT, int MR, bool ALIGNED>
-static int launch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    if (bt)
-        hipLaunchKernelGGL((conv3d_planes_mfma_batch_kernel<NT, MR, ALIGNED, 1>), dim3(ntiles, a.zcount, bt->n_img), dim3(256), 0, st, a,
-                           *bt, tiles_x, ntiles);
-    else
-    hipLaunchKernelGGL((conv2d_mfma_v2_kernel<3, NT, MR, EFFI_EPI_PLAIN, 8, false, ALIGNED>), dim3(ntiles, a.zcount), dim3(256), 0, st,
-                       a, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
+// Stride S = 1, and the stride-2 form (models/module.py:442,445: conv2 8->16, conv4 16->32; output plane z reads input planes 2z-1,
+// 2z, 2z+1, at most two rows per wave).
 // (batched: the rule on the workgroups of all samples; a pixel's accumulation order does not depend on the rows per wave)
-template <int NT>
-static int dispatch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const long planes = (long)a.zcount * (bt ? bt->n_img : 1);
-    const bool al = (a.w & 3) == 0;
-    const int mr = effi_pick_planes(a.h, a.w, planes, 4).rows;       // (launch_form.hpp)
-    if (mr == 4) return al ? launch3d_planes<NT, 4, true>(a, st, bt) : launch3d_planes<NT, 4, false>(a, st, bt);
-    if (mr == 2) return al ? launch3d_planes<NT, 2, true>(a, st, bt) : launch3d_planes<NT, 2, false>(a, st, bt);
-    return al ? launch3d_planes<NT, 1, true>(a, st, bt) : launch3d_planes<NT, 1, false>(a, st, bt);
+template <int NT, int S>
+static int launch3d_planes(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    const unsigned n = bt ? bt->n_img : 1;
+    const bool al = (a.w & 3) == 0 && (S == 1 || (a.win & 3) == 0);
+    const int rows = effi_pick_planes(a.h, a.w, (long)a.zcount * n, S == 1 ? 4 : 2).rows;       // (launch_form.hpp)
+    auto launch = [&](auto MR) {
+        return effi_switch<0, 1>(al, [&](auto AL) {
+            constexpr bool aligned = AL() != 0;
+            const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR());
+            if (bt) return effi_launch<conv3d_planes_mfma_batch_kernel<NT, MR(), aligned, S>>(dim3(ntiles, a.zcount, n), 256, st, a, *bt, tiles_x, ntiles);
+            return effi_launch<conv2d_mfma_v2_kernel<3, NT, MR(), EFFI_EPI_PLAIN, 8, false, aligned, S>>(dim3(ntiles, a.zcount), 256, st, a, tiles_x, ntiles);
+        });
+    };
+    if constexpr (S == 1) return effi_switch<1, 2, 4>(rows, launch);
+    else return effi_switch<1, 2>(rows, launch);
 }
 
 // the sample strides of a 3-D *_batch entry with ONE input tensor behind all three plane sources
@@ -1854,110 +1810,42 @@ static bool fill_vol_batch(ConvBatch& b, int n_smp, long in_sstride, long out_ss
 }
 
 #ifndef EFFI_BF16_ONLY
-static int conv3d_k3s1_mfma_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w, int relu,
-                                 float* out, const ConvBatch* bt, effi_stream_t stream) {
+template <int S>
+static int conv3d_k3_mfma_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w, int relu,
+                               float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack || !bias || !out || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (cout != 16 && cout != 32) return EFFI_ERR_UNSUPPORTED;
-    Conv2dArgs a;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {       // source s = plane z + s - 1 of the same tensor
-        a.src[i] = in;
-        a.ch[i] = cin;
-    }
+    Conv2dArgs a{};
+    conv_sources(a, &in, &cin, 1, true, CH_ANY);
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) a.ch[i] = cin;      // source s = input plane S z + s - 1 of the same tensor
     a.cin = 3 * cin;
-    a.kgroups = (a.cin + 3) / 4;
-    a.wpack = wpack;
-    a.bias = bias;
-    a.cout = cout;
-    a.h = h;
-    a.w = w;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    if (S == 1) conv_volume(a, D, h, w);
+    else conv_volume_s2(a, D, h, w);
+    conv_weights(a, wpack, bias, cout, relu ? EFFI_ACT_RELU : EFFI_ACT_NONE);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = (long)D * h * w;
-    a.ostride = (long)D * h * w;
-    a.zcount = a.zin = D;
-    a.hin = h;
-    a.win = w;
-    return cout == 16 ? dispatch3d_planes<1>(a, effi_s(stream), bt) : dispatch3d_planes<2>(a, effi_s(stream), bt);
+    return cout == 16 ? launch3d_planes<1, S>(a, effi_s(stream), bt) : launch3d_planes<2, S>(a, effi_s(stream), bt);
 }
 extern "C" int effi_conv3d_k3s1_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
                                          int h, int w, int relu, float* out, effi_stream_t stream) {
-    return conv3d_k3s1_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
+    return conv3d_k3_mfma_impl<1>(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
 }
 extern "C" int effi_conv3d_k3s1_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h,
                                                int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
                                                effi_stream_t stream) {
     ConvBatch b;
     if (!fill_vol_batch(b, n_smp, in_sstride, out_sstride)) return EFFI_ERR_BADARG;
-    return conv3d_k3s1_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
-}
-#endif
-
-// Stride-2 form (models/module.py:442,445: conv2 8->16, conv4 16->32): output plane z reads input planes 2z-1, 2z, 2z+1.
-template <int NT, int MR, bool ALIGNED>
-static int launch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    if (bt)
-        hipLaunchKernelGGL((conv3d_planes_mfma_batch_kernel<NT, MR, ALIGNED, 2>), dim3(ntiles, a.zcount, bt->n_img), dim3(256), 0, st, a,
-                           *bt, tiles_x, ntiles);
-    else
-    hipLaunchKernelGGL((conv2d_mfma_v2_kernel<3, NT, MR, EFFI_EPI_PLAIN, 8, false, ALIGNED, 2>), dim3(ntiles, a.zcount), dim3(256), 0,
-                       st, a, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-template <int NT>
-static int dispatch3d_planes_s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
-    const long planes = (long)a.zcount * (bt ? bt->n_img : 1);
-    const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (effi_pick_planes(a.h, a.w, planes, 2).rows == 2) return al ? launch3d_planes_s2<NT, 2, true>(a, st, bt) : launch3d_planes_s2<NT, 2, false>(a, st, bt);
-    return al ? launch3d_planes_s2<NT, 1, true>(a, st, bt) : launch3d_planes_s2<NT, 1, false>(a, st, bt);
-}
-
-#ifndef EFFI_BF16_ONLY
-static int conv3d_k3s2_mfma_impl(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h, int w, int relu,
-                                 float* out, const ConvBatch* bt, effi_stream_t stream) {
-    if (!in || !wpack || !bias || !out || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    if (cout != 16 && cout != 32) return EFFI_ERR_UNSUPPORTED;
-    Conv2dArgs a;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {       // source s = input plane 2z + s - 1 of the same tensor
-        a.src[i] = in;
-        a.ch[i] = cin;
-    }
-    a.cin = 3 * cin;
-    a.kgroups = (a.cin + 3) / 4;
-    a.wpack = wpack;
-    a.bias = bias;
-    a.cout = cout;
-    a.hin = h;
-    a.win = w;
-    a.h = (h - 1) / 2 + 1;
-    a.w = (w - 1) / 2 + 1;
-    a.zin = D;
-    a.zcount = (D - 1) / 2 + 1;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
-    a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = (long)D * h * w;
-    a.ostride = (long)a.zcount * a.h * a.w;
-    return cout == 16 ? dispatch3d_planes_s2<1>(a, effi_s(stream), bt) : dispatch3d_planes_s2<2>(a, effi_s(stream), bt);
+    return conv3d_k3_mfma_impl<1>(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 extern "C" int effi_conv3d_k3s2_mfma_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int D,
                                          int h, int w, int relu, float* out, effi_stream_t stream) {
-    return conv3d_k3s2_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
+    return conv3d_k3_mfma_impl<2>(in, cin, wpack, bias, cout, D, h, w, relu, out, nullptr, stream);
 }
 extern "C" int effi_conv3d_k3s2_mfma_f32_batch(const float* in, int cin, const float* wpack, const float* bias, int cout, int D, int h,
                                                int w, int relu, float* out, int n_smp, long in_sstride, long out_sstride,
                                                effi_stream_t stream) {
     ConvBatch b;
     if (!fill_vol_batch(b, n_smp, in_sstride, out_sstride)) return EFFI_ERR_BADARG;
-    return conv3d_k3s2_mfma_impl(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
+    return conv3d_k3_mfma_impl<2>(in, cin, wpack, bias, cout, D, h, w, relu, out, n_smp > 1 ? &b : nullptr, stream);
 }
 #endif
 
@@ -1982,91 +1870,52 @@ static int conv2d_f32_impl(const float* const* srcs, const int* src_channels, in
                            float* out0, float* out1, const ConvBatch* bt, effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack || !bias || !out0) return EFFI_ERR_BADARG;
     if (cout < 1 || h < 1 || w < 1 || (ks != 1 && ks != 3)) return EFFI_ERR_BADARG;
-    Conv2dArgs a;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : nullptr;
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        a.cin += a.ch[i];
-    }
-    a.kgroups = (a.cin + 3) / 4;
-    a.wpack = wpack;
-    a.bias = bias;
-    a.cout = cout;
-    a.h = h;
-    a.w = w;
-    a.act = act;
-    a.hd = cout / 2;
+    Conv2dArgs a{};
+    const int rc = conv_sources(a, srcs, src_channels, n_src, false, CH_ANY);
+    if (rc != EFFI_OK) return rc;
+    conv_map(a, h, w);
+    conv_weights(a, wpack, bias, cout, act);
+    a.hd = cout / 2;                           // GRU z | r: the first half of the output channels is z
     a.aux0 = aux0;
     a.aux1 = aux1;
     a.disp_range = disp_range;
     a.n_range = n_range;
     a.out0 = out0;
     a.out1 = out1;
-    a.cstride = (long)h * w;
-    a.ostride = (long)h * w;
-    a.zcount = 0;
-    a.hin = h;
-    a.win = w;
     const int nt = (cout + 15) / 16;
     hipStream_t st = effi_s(stream);
-    if (bt) {                                  // several images: the epilogues of the feature pyramid
-        if (cout == 1 && ks == 3 && (long)h * w >= 262144) return EFFI_ERR_UNSUPPORTED;        // (the vector-ALU kernel's territory)
-        switch (epilogue) {
-            case EFFI_EPI_PLAIN:
-                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-                return ks == 3 ? dispatch_nt_batch<3, EFFI_EPI_PLAIN>(a, *bt, nt, st) : dispatch_nt_batch<1, EFFI_EPI_PLAIN>(a, *bt, nt, st);
-            case EFFI_EPI_ADD_UP2:
-                if (ks != 1 || !aux0 || (h & 1) || (w & 3)) return EFFI_ERR_BADARG;
-                return dispatch_nt_batch<1, EFFI_EPI_ADD_UP2>(a, *bt, nt, st);
-            case EFFI_EPI_NHWC:
-                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH || (w & 3)) return EFFI_ERR_BADARG;
-                return ks == 3 ? dispatch_nt_batch<3, EFFI_EPI_NHWC>(a, *bt, nt, st) : dispatch_nt_batch<1, EFFI_EPI_NHWC>(a, *bt, nt, st);
-            case EFFI_EPI_GRU_ZR:
-            case EFFI_EPI_GRU_Q:
-            case EFFI_EPI_HEAD:
-                return EFFI_ERR_UNSUPPORTED;
-            default:
-                return EFFI_ERR_BADARG;
-        }
-    }
-    if (cout == 1 && ks == 3 && (long)h * w >= 262144 && (epilogue == EFFI_EPI_PLAIN || epilogue == EFFI_EPI_HEAD)) {
+    const bool big1 = cout == 1 && ks == 3 && (long)h * w >= 262144;
+    if (bt && big1) return EFFI_ERR_UNSUPPORTED;                       // (the vector-ALU kernel's territory)
+    if (big1 && (epilogue == EFFI_EPI_PLAIN || epilogue == EFFI_EPI_HEAD)) {
         // single output channel on a large map: vector-ALU kernel (an MFMA tile would be 15/16 padding);
         // it reads plain [cin][9] weights that the host appends behind the packed block (packing.py).
         // Small maps keep the MFMA kernel, whose finer tiling still fills the chip.
         if (epilogue == EFFI_EPI_HEAD && (!aux0 || !out1 || !disp_range || n_range < 2)) return EFFI_ERR_BADARG;
         const float* wraw = wpack + (long)a.kgroups * 9 * 64;
-        dim3 grid(effi_cdiv(w, 64), effi_cdiv(h, 16));
-        if (epilogue == EFFI_EPI_HEAD)
-            hipLaunchKernelGGL(conv2d_cout1_k3_kernel<EFFI_EPI_HEAD>, grid, dim3(256), 0, st, a, wraw);
-        else
-            hipLaunchKernelGGL(conv2d_cout1_k3_kernel<EFFI_EPI_PLAIN>, grid, dim3(256), 0, st, a, wraw);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+        const dim3 grid(effi_cdiv(w, 64), effi_cdiv(h, 16));
+        return epilogue == EFFI_EPI_HEAD ? effi_launch<conv2d_cout1_k3_kernel<EFFI_EPI_HEAD>>(grid, 256, st, a, wraw)
+                                         : effi_launch<conv2d_cout1_k3_kernel<EFFI_EPI_PLAIN>>(grid, 256, st, a, wraw);
     }
-    switch (epilogue) {
+    switch (epilogue) {                        // (several images, bt: the epilogues of the feature pyramid)
         case EFFI_EPI_PLAIN:
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-            return ks == 3 ? dispatch_nt<3, EFFI_EPI_PLAIN>(a, nt, st) : dispatch_nt<1, EFFI_EPI_PLAIN>(a, nt, st);
+            return ks == 3 ? dispatch2d<3, EFFI_EPI_PLAIN, 1, 2, 3, 4, 6>(a, nt, st, bt) : dispatch2d<1, EFFI_EPI_PLAIN, 1, 2, 3, 4, 6>(a, nt, st, bt);
         case EFFI_EPI_ADD_UP2:
             if (ks != 1 || !aux0 || (h & 1) || (w & 3)) return EFFI_ERR_BADARG;
-            return dispatch_nt<1, EFFI_EPI_ADD_UP2>(a, nt, st);
+            return dispatch2d<1, EFFI_EPI_ADD_UP2, 1, 2, 3, 4, 6>(a, nt, st, bt);
         case EFFI_EPI_NHWC:
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH || (w & 3)) return EFFI_ERR_BADARG;
-            return ks == 3 ? dispatch_nt<3, EFFI_EPI_NHWC>(a, nt, st) : dispatch_nt<1, EFFI_EPI_NHWC>(a, nt, st);
+            return ks == 3 ? dispatch2d<3, EFFI_EPI_NHWC, 1, 2, 3, 4, 6>(a, nt, st, bt) : dispatch2d<1, EFFI_EPI_NHWC, 1, 2, 3, 4, 6>(a, nt, st, bt);
         case EFFI_EPI_GRU_ZR:
+            if (bt) return EFFI_ERR_UNSUPPORTED;
             if (ks != 3 || !aux0 || !out1 || (cout % 32) != 0) return EFFI_ERR_BADARG;
-            if (nt == 2) return launch2d<3, 2, EFFI_EPI_GRU_ZR>(a, st);
-            if (nt == 4) return launch2d<3, 4, EFFI_EPI_GRU_ZR>(a, st);
-            if (nt == 6) return launch2d<3, 6, EFFI_EPI_GRU_ZR>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return dispatch2d<3, EFFI_EPI_GRU_ZR, 2, 4, 6>(a, nt, st, bt);
         case EFFI_EPI_GRU_Q:
+            if (bt) return EFFI_ERR_UNSUPPORTED;
             if (ks != 3 || !aux0 || !aux1 || (cout % 16) != 0) return EFFI_ERR_BADARG;
-            if (nt == 1) return launch2d<3, 1, EFFI_EPI_GRU_Q>(a, st);
-            if (nt == 2) return launch2d<3, 2, EFFI_EPI_GRU_Q>(a, st);
-            if (nt == 3) return launch2d<3, 3, EFFI_EPI_GRU_Q>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return dispatch2d<3, EFFI_EPI_GRU_Q, 1, 2, 3>(a, nt, st, bt);
         case EFFI_EPI_HEAD:
+            if (bt) return EFFI_ERR_UNSUPPORTED;
             if (ks != 3 || cout != 1 || !aux0 || !out1 || !disp_range || n_range < 2) return EFFI_ERR_BADARG;
             return launch2d<3, 1, EFFI_EPI_HEAD>(a, st);
         default:
@@ -2096,35 +1945,19 @@ extern "C" int effi_conv2d_f32_batch(const float* const* srcs, const int* src_ch
 #endif
 
 // ---- 5x5 stride-2 convolution (feature pyramid down-sampling) ---------------------------------------------------
-template <int NT, int MR, bool ALIGNED>
-static int launch_k5s2(const Conv2dArgs& a, hipStream_t st) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    hipLaunchKernelGGL((conv2d_mfma_v2_kernel<5, NT, MR, EFFI_EPI_PLAIN, 4, false, ALIGNED, 2>), dim3(ntiles), dim3(256), 0, st, a,
-                       tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
+// Batched: the same rule on the tile count of all images (bitwise the single-image result: see launch2d).
 template <int NT>
-static int dispatch_k5s2(const Conv2dArgs& a, hipStream_t st) {
+static int launch_k5s2(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    const unsigned n = bt ? bt->n_img : 1;
     const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (effi_pick_planes(a.h, a.w, 1, 2).rows == 2) return al ? launch_k5s2<NT, 2, true>(a, st) : launch_k5s2<NT, 2, false>(a, st);
-    return al ? launch_k5s2<NT, 1, true>(a, st) : launch_k5s2<NT, 1, false>(a, st);
-}
-
-// Batched form: the same rule on the tile count of all images (bitwise the single-image result: see launch2d_batch).
-template <int NT, int MR, bool ALIGNED>
-static int launch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR);
-    hipLaunchKernelGGL((conv2d_mfma_v2_batch_kernel<5, NT, MR, EFFI_EPI_PLAIN, 4, ALIGNED, 2>), dim3(ntiles, b.n_img), dim3(256), 0, st, a, b,
-                       tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-template <int NT>
-static int dispatch_k5s2_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const bool al = (a.win & 3) == 0 && (a.w & 3) == 0;
-    if (effi_pick_planes(a.h, a.w, b.n_img, 2).rows == 2) return al ? launch_k5s2_batch<NT, 2, true>(a, b, st) : launch_k5s2_batch<NT, 2, false>(a, b, st);
-    return al ? launch_k5s2_batch<NT, 1, true>(a, b, st) : launch_k5s2_batch<NT, 1, false>(a, b, st);
+    return effi_switch<1, 2>(effi_pick_planes(a.h, a.w, n, 2).rows, [&](auto MR) {
+        return effi_switch<0, 1>(al, [&](auto AL) {
+            constexpr bool aligned = AL() != 0;
+            const int tiles_x = effi_cdiv(a.w, 16), ntiles = tiles_x * effi_cdiv(a.h, 4 * MR());
+            if (bt) return effi_launch<conv2d_mfma_v2_batch_kernel<5, NT, MR(), EFFI_EPI_PLAIN, 4, aligned, 2>>(dim3(ntiles, n), 256, st, a, *bt, tiles_x, ntiles);
+            return effi_launch<conv2d_mfma_v2_kernel<5, NT, MR(), EFFI_EPI_PLAIN, 4, false, aligned, 2>>(dim3(ntiles), 256, st, a, tiles_x, ntiles);
+        });
+    });
 }
 
 #ifndef EFFI_BF16_ONLY
@@ -2132,44 +1965,13 @@ static int conv2d_k5s2_f32_impl(const float* in, int cin, const float* wpack, co
                                 int win, int act, float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack || !bias || !out || cin < 1 || cout < 1 || hin < 1 || win < 1) return EFFI_ERR_BADARG;
     if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-    Conv2dArgs a;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i == 0) ? in : nullptr;
-        a.ch[i] = (i == 0) ? cin : 0;
-    }
-    a.cin = cin;
-    a.kgroups = (cin + 3) / 4;
-    a.wpack = wpack;
-    a.bias = bias;
-    a.cout = cout;
-    a.hin = hin;
-    a.win = win;
-    a.h = (hin - 1) / 2 + 1;
-    a.w = (win - 1) / 2 + 1;
-    a.act = act;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    Conv2dArgs a{};
+    conv_sources(a, &in, &cin, 1, false, CH_ANY);
+    conv_map_s2(a, hin, win);
+    conv_weights(a, wpack, bias, cout, act);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = (long)hin * win;
-    a.ostride = (long)a.h * a.w;
-    a.zcount = 0;
     hipStream_t st = effi_s(stream);
-    if (bt) {
-        switch ((cout + 15) / 16) {
-            case 1: return dispatch_k5s2_batch<1>(a, *bt, st);
-            case 2: return dispatch_k5s2_batch<2>(a, *bt, st);
-            case 4: return dispatch_k5s2_batch<4>(a, *bt, st);
-            default: return EFFI_ERR_UNSUPPORTED;
-        }
-    }
-    switch ((cout + 15) / 16) {
-        case 1: return dispatch_k5s2<1>(a, st);
-        case 2: return dispatch_k5s2<2>(a, st);
-        case 4: return dispatch_k5s2<4>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 4>((cout + 15) / 16, [&](auto NT) { return launch_k5s2<NT()>(a, st, bt); });
 }
 
 extern "C" int effi_conv2d_k5s2_f32(const float* in, int cin, const float* wpack, const float* bias, int cout, int hin,
@@ -2358,49 +2160,22 @@ __global__ __launch_bounds__(256) void conv3d_s2_bf16x3_batch_kernel(const Conv2
 
 }  // namespace
 
-// (the rows-per-wave rule of launch_s2_x3 on the workgroups of all samples: bitwise the single-sample result either way)
-template <int NT>
-static int launch_s2_x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, int ngroups, hipStream_t st) {
-    const int cols = effi_cdiv(a.w, 16);
-    const long planes = (long)a.zcount * b.n_img;
-    if (planes > 65535) return EFFI_ERR_UNSUPPORTED;
-    if (effi_pick_s2_x3(a.h, a.w, ngroups, planes).rows == 2) {
-        const int ntiles = cols * effi_cdiv(a.h, 8);
-        hipLaunchKernelGGL((conv3d_s2_bf16x3_batch_kernel<NT, 2>), dim3(ntiles, ngroups, (unsigned)planes), dim3(256), 0, st, a, b, cols, ntiles);
-    } else {
-        const int ntiles = cols * effi_cdiv(a.h, 4);
-        hipLaunchKernelGGL((conv3d_s2_bf16x3_batch_kernel<NT, 1>), dim3(ntiles, ngroups, (unsigned)planes), dim3(256), 0, st, a, b, cols, ntiles);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
+// ZB: the z-batched 3-D form.  Batched 2-D (images) and sample-batched 3-D form: the rows-per-wave rule on the workgroup count of all
+// images / all planes of all samples (bitwise the single-image result: the accumulation order of a pixel is (octet, K-step, hi/lo
+// term) for either tile height).
 template <int KS, int NT, bool ZB>
-static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st) {
-    const int cols = effi_cdiv(a.w, 16);
-    const unsigned planes = ZB ? (unsigned)a.zcount : 1u;
-    if (effi_pick_s2_x3(a.h, a.w, ngroups, planes).rows == 2) {
-        const int ntiles = cols * effi_cdiv(a.h, 8);
-        hipLaunchKernelGGL((conv2d_s2_bf16x3_kernel<KS, NT, 2, ZB>), dim3(ntiles, ngroups, planes), dim3(256), 0, st, a, cols, ntiles);
-    } else {
-        const int ntiles = cols * effi_cdiv(a.h, 4);
-        hipLaunchKernelGGL((conv2d_s2_bf16x3_kernel<KS, NT, 1, ZB>), dim3(ntiles, ngroups, planes), dim3(256), 0, st, a, cols, ntiles);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-// Batched 2-D form: the rows-per-wave rule on the workgroup count of all images (bitwise the single-image result: the accumulation
-// order of a pixel is (octet, K-step, hi/lo term) for either tile height).
-template <int KS, int NT>
-static int launch_s2_x3_batch(const Conv2dArgs& a, const ConvBatch& b, int ngroups, hipStream_t st) {
-    const int cols = effi_cdiv(a.w, 16);
-    if (effi_pick_s2_x3(a.h, a.w, ngroups, b.n_img).rows == 2) {
-        const int ntiles = cols * effi_cdiv(a.h, 8);
-        hipLaunchKernelGGL((conv2d_s2_bf16x3_batch_kernel<KS, NT, 2>), dim3(ntiles, ngroups, b.n_img), dim3(256), 0, st, a, b, cols, ntiles);
-    } else {
-        const int ntiles = cols * effi_cdiv(a.h, 4);
-        hipLaunchKernelGGL((conv2d_s2_bf16x3_batch_kernel<KS, NT, 1>), dim3(ntiles, ngroups, b.n_img), dim3(256), 0, st, a, b, cols, ntiles);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+static int launch_s2_x3(const Conv2dArgs& a, int ngroups, hipStream_t st, const ConvBatch* bt = nullptr) {
+    const unsigned n = bt ? bt->n_img : 1;
+    const long planes = ZB ? (long)a.zcount * n : 1;
+    if (bt && planes > 65535) return EFFI_ERR_UNSUPPORTED;
+    return effi_switch<1, 2>(effi_pick_s2_x3(a.h, a.w, ngroups, ZB ? planes : n).rows, [&](auto MR) {
+        const int cols = effi_cdiv(a.w, 16), ntiles = cols * effi_cdiv(a.h, 4 * MR());
+        if (bt) {
+            if constexpr (ZB) return effi_launch<conv3d_s2_bf16x3_batch_kernel<NT, MR()>>(dim3(ntiles, ngroups, (unsigned)planes), 256, st, a, *bt, cols, ntiles);
+            else return effi_launch<conv2d_s2_bf16x3_batch_kernel<KS, NT, MR()>>(dim3(ntiles, ngroups, n), 256, st, a, *bt, cols, ntiles);
+        }
+        return effi_launch<conv2d_s2_bf16x3_kernel<KS, NT, MR(), ZB>>(dim3(ntiles, ngroups, (unsigned)planes), 256, st, a, cols, ntiles);
+    });
 }
 
 static int conv2d_k5s2_x3_impl(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
@@ -2408,36 +2183,15 @@ static int conv2d_k5s2_x3_impl(const float* in, int cin, const void* wpack_bf16,
     if (!in || !wpack_bf16 || !bias || !out || cin < 1 || cout < 1 || hin < 1 || win < 1) return EFFI_ERR_BADARG;
     if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
     if ((win & 3) || cout > 128) return EFFI_ERR_UNSUPPORTED;
-    Conv2dArgs a;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = in;
-        a.ch[i] = (i == 0) ? cin : 0;
-    }
-    a.cin = cin;
-    a.kgroups = 0;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.hin = hin;
-    a.win = win;
-    a.h = (hin - 1) / 2 + 1;
-    a.w = (win - 1) / 2 + 1;
-    a.act = act;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    Conv2dArgs a{};
+    conv_sources(a, &in, &cin, 1, true, CH_ANY);
+    conv_map_s2(a, hin, win);
+    if (!(a.zeros = effi_zero_page())) return EFFI_ERR_WORKSPACE;
+    conv_weights_x3(a, wpack_bf16, bias, cout, act);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = (long)hin * win;
-    a.ostride = (long)a.h * a.w;
-    a.zcount = a.zin = 0;
     hipStream_t st = effi_s(stream);
-    const int nt = (cout + 15) / 16;
-    if (bt) return nt == 1 ? launch_s2_x3_batch<5, 1>(a, *bt, 1, st) : launch_s2_x3_batch<5, 2>(a, *bt, (nt + 1) / 2, st);
-    if (nt == 1) return launch_s2_x3<5, 1, false>(a, 1, st);
-    return launch_s2_x3<5, 2, false>(a, (nt + 1) / 2, st);   // weights packed in groups of two N-tiles (zero-padded)
+    const int nt = (cout + 15) / 16;           // from two N-tiles on: weights packed in groups of two (zero-padded)
+    return nt == 1 ? launch_s2_x3<5, 1, false>(a, 1, st, bt) : launch_s2_x3<5, 2, false>(a, (nt + 1) / 2, st, bt);
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k5s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int hin,
@@ -2457,37 +2211,15 @@ static int conv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf16,
                                float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!in || !wpack_bf16 || !bias || !out || cin < 1 || cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if ((w & 3) || cout > 64) return EFFI_ERR_UNSUPPORTED;
-    Conv2dArgs a;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = in;
-        a.ch[i] = (i == 0) ? cin : 0;
-    }
-    a.cin = cin;                                 // channels per input plane
-    a.kgroups = 0;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.hin = h;
-    a.win = w;
-    a.h = (h - 1) / 2 + 1;
-    a.w = (w - 1) / 2 + 1;
-    a.zin = D;
-    a.zcount = (D - 1) / 2 + 1;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    Conv2dArgs a{};
+    conv_sources(a, &in, &cin, 1, true, CH_ANY);           // a.cin: channels per input plane
+    conv_volume_s2(a, D, h, w);
+    if (!(a.zeros = effi_zero_page())) return EFFI_ERR_WORKSPACE;
+    conv_weights_x3(a, wpack_bf16, bias, cout, relu ? EFFI_ACT_RELU : EFFI_ACT_NONE);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = (long)D * h * w;
-    a.ostride = (long)a.zcount * a.h * a.w;
     hipStream_t st = effi_s(stream);
     const int nt = (cout + 15) / 16;
-    if (bt) return nt == 1 ? launch_s2_x3_zb_batch<1>(a, *bt, 1, st) : launch_s2_x3_zb_batch<2>(a, *bt, (nt + 1) / 2, st);
-    if (nt == 1) return launch_s2_x3<3, 1, true>(a, 1, st);
-    return launch_s2_x3<3, 2, true>(a, (nt + 1) / 2, st);
+    return nt == 1 ? launch_s2_x3<3, 1, true>(a, 1, st, bt) : launch_s2_x3<3, 2, true>(a, (nt + 1) / 2, st, bt);
 }
 
 extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
@@ -2504,33 +2236,20 @@ extern "C" int EFFI_FN(effi_conv3d_k3s2_bf16x3_f32_batch)(const float* in, int c
 }
 
 
+// The planar split-precision 3x3 layer, plain epilogue (as fill_sr, conv2d_sr.hip, for the split-resident maps): the pair's two
+// halves as they stand, the other entries override what they mean.
 static int fill_bf16x3_plain(Conv2dArgs& a, const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
                              const float* bias, int cout, int h, int w, int act, float* out0) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack_bf16 || !bias || !out0) return EFFI_ERR_BADARG;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : srcs[0];
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i + 1 < n_src && (src_channels[i] & 7)) return EFFI_ERR_UNSUPPORTED;
-        a.cin += a.ch[i];
-    }
+    a = Conv2dArgs{};
+    const int rc = conv_sources(a, srcs, src_channels, n_src, true, CH_OCTETS);
+    if (rc != EFFI_OK) return rc;
+    if (!(a.zeros = effi_zero_page())) return EFFI_ERR_WORKSPACE;
+    conv_weights_x3(a, wpack_bf16, bias, cout, act);
+    conv_map(a, h, w);
     a.kgroups = (a.cin + 3) / 4;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = act;
-    a.hd = cout / 2;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    a.hd = cout / 2;                           // GRU z | r: the first half of the output channels is z
     a.out0 = out0;
-    a.out1 = nullptr;
-    a.cstride = a.ostride = (long)h * w;
-    a.zcount = a.zin = 0;
     return EFFI_OK;
 }
 
@@ -2547,13 +2266,7 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_pair_f32)(const float* const* srcs_
     rc = fill_bf16x3_plain(a1, srcs_b, src_channels_b, n_src_b, wpack_b, bias_b, cout, h, w, act, out_b);
     if (rc != EFFI_OK) return rc;
     hipStream_t st = effi_s(stream);
-    switch ((cout + 15) / 16) {
-        case 1: return launch_bf16x3_pair<1>(a0, a1, st);
-        case 2: return launch_bf16x3_pair<2>(a0, a1, st);
-        case 3: return launch_bf16x3_pair<3>(a0, a1, st);
-        case 4: return launch_bf16x3_pair<4>(a0, a1, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3, 4>((cout + 15) / 16, [&](auto NT) { return launch_bf16x3_pair<NT()>(a0, a1, st); });
 }
 
 // bt == nullptr: the single-image entry
@@ -2565,81 +2278,37 @@ static int conv2d_k3_x3_impl(const float* const* srcs, const int* src_channels, 
     if (cout < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (w & 3) return EFFI_ERR_UNSUPPORTED;                 // rows must be float4-aligned (callers fall back to the fp32 kernel)
     Conv2dArgs a;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : srcs[0];
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i + 1 < n_src && (src_channels[i] & 7)) return EFFI_ERR_UNSUPPORTED;   // an octet of channels lies in one source
-        a.cin += a.ch[i];
-    }
-    a.kgroups = (a.cin + 3) / 4;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = act;
-    a.hd = cout / 2;
+    const int rc = fill_bf16x3_plain(a, srcs, src_channels, n_src, wpack_bf16, bias, cout, h, w, act, out0);
+    if (rc != EFFI_OK) return rc;
     a.aux0 = aux0;
     a.aux1 = aux1;
     a.disp_range = disp_range;
     a.n_range = n_range;
-    a.out0 = out0;
     a.out1 = out1;
-    a.cstride = a.ostride = (long)h * w;
-    a.zcount = 0;
     const int nt = (cout + 15) / 16;
     hipStream_t st = effi_s(stream);
-    if (bt) {                                  // several images: the epilogues of the feature pyramid
-        switch (epilogue) {
-            case EFFI_EPI_PLAIN:
-                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-                return dispatch_bf16x3_batch<EFFI_EPI_PLAIN>(a, *bt, nt, st);
-            case EFFI_EPI_NHWC:
-                if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-                return dispatch_bf16x3_batch<EFFI_EPI_NHWC>(a, *bt, nt, st);
-            case EFFI_EPI_ADD_SHUF2:
-            case EFFI_EPI_NHWC_ADD_SHUF2:
-                if (!aux0 || (h & 1) || (w & 1) || act != EFFI_ACT_NONE) return EFFI_ERR_BADARG;
-                if (nt == 1) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3_batch<1, EFFI_EPI_ADD_SHUF2>(a, *bt, st)
-                                                                   : launch_bf16x3_batch<1, EFFI_EPI_NHWC_ADD_SHUF2>(a, *bt, st);
-                if (nt == 2) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3_batch<2, EFFI_EPI_ADD_SHUF2>(a, *bt, st)
-                                                                   : launch_bf16x3_batch<2, EFFI_EPI_NHWC_ADD_SHUF2>(a, *bt, st);
-                return EFFI_ERR_UNSUPPORTED;
-            default:
-                return EFFI_ERR_UNSUPPORTED;
-        }
-    }
-    switch (epilogue) {
+    switch (epilogue) {                        // (several images, bt: the epilogues of the feature pyramid)
         case EFFI_EPI_PLAIN:
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-            return dispatch_bf16x3<EFFI_EPI_PLAIN>(a, nt, st);
+            return effi_switch_nt<1, 2, 3, 4, 6>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_PLAIN>(a, st, bt); });
         case EFFI_EPI_NHWC:
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-            return dispatch_bf16x3<EFFI_EPI_NHWC>(a, nt, st);
+            return effi_switch_nt<1, 2, 3, 4, 6>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_NHWC>(a, st, bt); });
         case EFFI_EPI_ADD_SHUF2:
         case EFFI_EPI_NHWC_ADD_SHUF2:
             if (!aux0 || (h & 1) || (w & 1) || act != EFFI_ACT_NONE) return EFFI_ERR_BADARG;
-            if (nt == 1) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3<1, EFFI_EPI_ADD_SHUF2>(a, st)
-                                                               : launch_bf16x3<1, EFFI_EPI_NHWC_ADD_SHUF2>(a, st);
-            if (nt == 2) return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3<2, EFFI_EPI_ADD_SHUF2>(a, st)
-                                                               : launch_bf16x3<2, EFFI_EPI_NHWC_ADD_SHUF2>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return effi_switch_nt<1, 2>(nt, [&](auto NT) {
+                return epilogue == EFFI_EPI_ADD_SHUF2 ? launch_bf16x3<NT(), EFFI_EPI_ADD_SHUF2>(a, st, bt)
+                                                     : launch_bf16x3<NT(), EFFI_EPI_NHWC_ADD_SHUF2>(a, st, bt);
+            });
         case EFFI_EPI_GRU_ZR:
+            if (bt) return EFFI_ERR_UNSUPPORTED;
             if (!aux0 || !out1 || (cout % 32) != 0) return EFFI_ERR_BADARG;
-            if (nt == 2) return launch_bf16x3<2, EFFI_EPI_GRU_ZR>(a, st);
-            if (nt == 4) return launch_bf16x3<4, EFFI_EPI_GRU_ZR>(a, st);
-            if (nt == 6) return launch_bf16x3<6, EFFI_EPI_GRU_ZR>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return effi_switch_nt<2, 4, 6>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_GRU_ZR>(a, st); });
         case EFFI_EPI_GRU_Q:
+            if (bt) return EFFI_ERR_UNSUPPORTED;
             if (!aux0 || !aux1 || (cout % 16) != 0) return EFFI_ERR_BADARG;
-            if (nt == 1) return launch_bf16x3<1, EFFI_EPI_GRU_Q>(a, st);
-            if (nt == 2) return launch_bf16x3<2, EFFI_EPI_GRU_Q>(a, st);
-            if (nt == 3) return launch_bf16x3<3, EFFI_EPI_GRU_Q>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return effi_switch_nt<1, 2, 3>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_GRU_Q>(a, st); });
         default:
             return EFFI_ERR_UNSUPPORTED;
     }
@@ -2674,41 +2343,18 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_bf16x3_f32)(const float* const* srcs, c
     if (cout1 < 1 || cout2 < 1 || h < 1 || w < 1 || c_extra < 0 || (c_extra > 0 && !extra)) return EFFI_ERR_BADARG;
     if ((w & 3) || cout1 > 96 || c_extra > 16 || cout2 > 96) return EFFI_ERR_UNSUPPORTED;
     Conv2dArgs a;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : srcs[0];
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i + 1 < n_src && (src_channels[i] & 7)) return EFFI_ERR_UNSUPPORTED;
-        a.cin += a.ch[i];
-    }
+    const int rc = fill_bf16x3_plain(a, srcs, src_channels, n_src, wpack_bf16, bias, cout1, h, w, relu ? EFFI_ACT_RELU : EFFI_ACT_NONE, out);
+    if (rc != EFFI_OK) return rc;
+    // EPI_K1 reuses: kgroups = ReLU between the two convolutions, hd = extra (context) channels of the 1x1 layer behind aux0 (a valid
+    // dummy without them), aux1 = its weights, disp_range = its bias, n_range = its output channels
     a.kgroups = relu1 ? 1 : 0;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout1;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
     a.hd = c_extra;
     a.aux0 = c_extra ? extra : bias2;
     a.aux1 = reinterpret_cast<const float*>(w2pack_bf16);
     a.disp_range = bias2;
     a.n_range = cout2;
-    a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = a.ostride = (long)h * w;
-    a.zcount = a.zin = 0;
     hipStream_t st = effi_s(stream);
-    switch ((cout1 + 15) / 16) {
-        case 1: return launch_bf16x3<1, EFFI_EPI_K1>(a, st);
-        case 2: return launch_bf16x3<2, EFFI_EPI_K1>(a, st);
-        case 3: return launch_bf16x3<3, EFFI_EPI_K1>(a, st);
-        case 4: return launch_bf16x3<4, EFFI_EPI_K1>(a, st);
-        case 6: return launch_bf16x3<6, EFFI_EPI_K1>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3, 4, 6>((cout1 + 15) / 16, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_K1>(a, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2946,13 +2592,10 @@ static int conv2d_k3_twice_impl(const float* in, int cin, const void* w1_bf16, c
         if ((long)n_img * ntiles > 0x7fffffffL || in_istride < 0 || out_istride < 0) return EFFI_ERR_BADARG;
         const long nall = (long)n_img * ntiles;
         const int nwg = nall < 1024 ? (int)nall : 1024;
-        hipLaunchKernelGGL(conv2d_k3_twice_oct_kernel<true>, dim3(nwg), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles, n_img, in_istride,
-                           out_istride);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+        return effi_launch<conv2d_k3_twice_oct_kernel<true>>(dim3(nwg), 256, effi_s(stream), a, tiles_x, ntiles, n_img, in_istride, out_istride);
     }
     const int nwg = ntiles < 1024 ? ntiles : 1024;         // 4 persistent workgroups per CU (38 KB of LDS each)
-    hipLaunchKernelGGL(conv2d_k3_twice_oct_kernel<false>, dim3(nwg), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles, 1, 0L, 0L);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_launch<conv2d_k3_twice_oct_kernel<false>>(dim3(nwg), 256, effi_s(stream), a, tiles_x, ntiles, 1, 0L, 0L);
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k3_twice_bf16x3_f32)(const float* in, int cin, const void* w1_bf16, const float* bias1,
@@ -2987,8 +2630,7 @@ extern "C" int EFFI_FN(effi_encoder_tail_bf16x3_f32)(const float* cor1, const fl
     a.zeros = effi_zero_page();
     if (!a.zeros) return EFFI_ERR_WORKSPACE;
     const int tiles_x = effi_cdiv(w, 16), ntiles = tiles_x * effi_cdiv(h, 12);
-    hipLaunchKernelGGL((encoder_tail_bf16x3_kernel<1, 1>), dim3(ntiles), dim3(256), 0, effi_s(stream), a, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_launch<encoder_tail_bf16x3_kernel<1, 1>>(dim3(ntiles), 256, effi_s(stream), a, tiles_x, ntiles);
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
@@ -3001,79 +2643,37 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_f32)(const float* const* sr
     if (cout1 < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if ((w & 3) || cout1 > 96) return EFFI_ERR_UNSUPPORTED;
     Conv2dArgs a;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : srcs[0];
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i + 1 < n_src && (src_channels[i] & 7)) return EFFI_ERR_UNSUPPORTED;
-        a.cin += a.ch[i];
-    }
+    const int rc = fill_bf16x3_plain(a, srcs, src_channels, n_src, wpack_bf16, bias, cout1, h, w, EFFI_ACT_NONE, out_depth);
+    if (rc != EFFI_OK) return rc;
+    // EPI_K1UP reuses: kgroups, aux1, disp_range, n_range as EPI_K1 (36 = 4 x 9 up-sampling weights per pixel); aux0 = the inverse-depth
+    // map, xptr0 / zin = the hypotheses' inverse-depth range and its length
     a.kgroups = 1;                          // ReLU between the 3x3 and the 1x1 convolution (models/update.py:110)
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout1;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = EFFI_ACT_NONE;
     a.hd = 0;
     a.aux0 = inv_depth;
     a.aux1 = reinterpret_cast<const float*>(w2pack_bf16);
     a.disp_range = bias2;
     a.n_range = 36;
-    a.out0 = out_depth;
     a.out1 = out_depth_inv;
-    a.cstride = a.ostride = (long)h * w;
-    a.zcount = 0;
     a.zin = n_range;
     a.xptr0 = disp_range;
     hipStream_t st = effi_s(stream);
-    switch ((cout1 + 15) / 16) {
-        case 2: return launch_bf16x3<2, EFFI_EPI_K1UP>(a, st);
-        case 4: return launch_bf16x3<4, EFFI_EPI_K1UP>(a, st);
-        case 6: return launch_bf16x3<6, EFFI_EPI_K1UP>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<2, 4, 6>((cout1 + 15) / 16, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_K1UP>(a, st); });
 }
 
 static int conv3d_k3s1_x3_impl(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16, const float* bias,
                                int cout, int D, int h, int w, int relu, float* out, const ConvBatch* bt, effi_stream_t stream) {
     if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !wpack_bf16 || !bias || !out) return EFFI_ERR_BADARG;
     if (cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    Conv2dArgs a;                                          // any w: quads that straddle a row end are staged element by element
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : srcs[0];
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i + 1 < n_src && (src_channels[i] & 7)) return EFFI_ERR_UNSUPPORTED;
-        a.cin += a.ch[i];
-    }
+    Conv2dArgs a{};                                        // any w: quads that straddle a row end are staged element by element
+    const int rc = conv_sources(a, srcs, src_channels, n_src, true, CH_OCTETS);
+    if (rc != EFFI_OK) return rc;
     if (a.cin & 7) return EFFI_ERR_UNSUPPORTED;            // an octet of (plane, channel) lies in one plane
-    a.kgroups = 0;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    if (!(a.zeros = effi_zero_page())) return EFFI_ERR_WORKSPACE;
+    conv_weights_x3(a, wpack_bf16, bias, cout, relu ? EFFI_ACT_RELU : EFFI_ACT_NONE);
+    conv_volume(a, D, h, w);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = a.ostride = (long)D * h * w;
-    a.zcount = D;
     hipStream_t st = effi_s(stream);
-    switch ((cout + 15) / 16) {
-        case 1: return bt ? launch_bf16x3_zb_batch<1>(a, *bt, st) : launch_bf16x3<1, EFFI_EPI_PLAIN, true>(a, st);
-        case 2: return bt ? launch_bf16x3_zb_batch<2>(a, *bt, st) : launch_bf16x3<2, EFFI_EPI_PLAIN, true>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2>((cout + 15) / 16, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_PLAIN, true>(a, st, bt); });
 }
 
 extern "C" int EFFI_FN(effi_conv3d_k3s1_bf16x3_f32)(const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
@@ -3102,65 +2702,32 @@ static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pa
     const long tiles = (long)cols * effi_cdiv(a.h, 4 * mr);
     const dim3 grid((unsigned)tiles, (unsigned)effi_cdiv(D, zt), pair ? 2 : (bt ? bt->n_img : 1));
     // (option roll_rp = 0, with packing.py: the one-row-per-tile operand, A/B runs)
-    if (bt) {               // a window's plane run and the rows per wave do not enter an output's accumulation order
-        if (rp) {
-            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_batch_kernel<NOCT, 4>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
-            else hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_batch_kernel<NOCT, 2>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
-        } else {
-            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_bf16x3_batch_kernel<NOCT, NT, 4>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
-            else hipLaunchKernelGGL((conv3d_roll_bf16x3_batch_kernel<NOCT, NT, 2>), grid, dim3(256), 0, st, a, *bt, cols, (int)tiles, zt);
-        }
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    if (rp) {
-        if (pair) {
-            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_pair_kernel<NOCT, 4>), grid, dim3(256), 0, st, a, *pair, cols, (int)tiles, zt);
-            else hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_pair_kernel<NOCT, 2>), grid, dim3(256), 0, st, a, *pair, cols, (int)tiles, zt);
-        } else {
-            if (mr == 4) hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_kernel<NOCT, 4>), grid, dim3(256), 0, st, a, cols, (int)tiles, zt);
-            else hipLaunchKernelGGL((conv3d_roll_rp_bf16x3_kernel<NOCT, 2>), grid, dim3(256), 0, st, a, cols, (int)tiles, zt);
-        }
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    if (pair) {
-        if (mr == 4) hipLaunchKernelGGL((conv3d_roll_bf16x3_pair_kernel<NOCT, NT, 4>), grid, dim3(256), 0, st, a, *pair, cols, (int)tiles, zt);
-        else hipLaunchKernelGGL((conv3d_roll_bf16x3_pair_kernel<NOCT, NT, 2>), grid, dim3(256), 0, st, a, *pair, cols, (int)tiles, zt);
-    } else {
-        if (mr == 4) hipLaunchKernelGGL((conv3d_roll_bf16x3_kernel<NOCT, NT, 4>), grid, dim3(256), 0, st, a, cols, (int)tiles, zt);
-        else hipLaunchKernelGGL((conv3d_roll_bf16x3_kernel<NOCT, NT, 2>), grid, dim3(256), 0, st, a, cols, (int)tiles, zt);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    // batched: a window's plane run and the rows per wave do not enter an output's accumulation order
+    return effi_switch<2, 4>(mr, [&](auto MR) {
+        constexpr int m = MR();
+        const int ntiles = (int)tiles;
+        if (bt) return rp ? effi_launch<conv3d_roll_rp_bf16x3_batch_kernel<NOCT, m>>(grid, 256, st, a, *bt, cols, ntiles, zt)
+                          : effi_launch<conv3d_roll_bf16x3_batch_kernel<NOCT, NT, m>>(grid, 256, st, a, *bt, cols, ntiles, zt);
+        if (pair) return rp ? effi_launch<conv3d_roll_rp_bf16x3_pair_kernel<NOCT, m>>(grid, 256, st, a, *pair, cols, ntiles, zt)
+                            : effi_launch<conv3d_roll_bf16x3_pair_kernel<NOCT, NT, m>>(grid, 256, st, a, *pair, cols, ntiles, zt);
+        return rp ? effi_launch<conv3d_roll_rp_bf16x3_kernel<NOCT, m>>(grid, 256, st, a, cols, ntiles, zt)
+                  : effi_launch<conv3d_roll_bf16x3_kernel<NOCT, NT, m>>(grid, 256, st, a, cols, ntiles, zt);
+    });
 }
 
 static int fill_roll_args(Conv2dArgs& a, const float* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
                           const float* bias, int cout, int D, int h, int w, int relu, float* out) {
     if (!srcs || !src_channels || n_src < 1 || n_src > 2 || !wpack_bf16 || !bias || !out) return EFFI_ERR_BADARG;
     if (cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = (i < n_src) ? srcs[i] : nullptr;
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        a.cin += a.ch[i];
-    }
+    a = Conv2dArgs{};
+    const int rc = conv_sources(a, srcs, src_channels, n_src, false, CH_ANY);
+    if (rc != EFFI_OK) return rc;
     if ((w & 3) || (a.cin != 8 && a.cin != 16) || (a.ch[0] & 7) || cout > 32) return EFFI_ERR_UNSUPPORTED;
     if (n_src == 1) a.src[1] = a.src[0];
-    a.kgroups = 0;
-    a.zeros = effi_zero_page();
-    if (!a.zeros) return EFFI_ERR_WORKSPACE;
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = relu ? EFFI_ACT_RELU : EFFI_ACT_NONE;
-    a.hd = 0;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
+    if (!(a.zeros = effi_zero_page())) return EFFI_ERR_WORKSPACE;
+    conv_weights_x3(a, wpack_bf16, bias, cout, relu ? EFFI_ACT_RELU : EFFI_ACT_NONE);
+    conv_volume(a, D, h, w);
     a.out0 = out;
-    a.out1 = nullptr;
-    a.cstride = a.ostride = (long)D * h * w;
-    a.zcount = a.zin = D;
     return EFFI_OK;
 }
 
@@ -3221,9 +2788,7 @@ extern "C" int EFFI_FN(effi_csp_gen_roll_bf16x3_pair_f32)(const float* x, int D,
     const CspGenCall ca{prior_a, w0_a, b0_a, wc_a, bc_a, reinterpret_cast<const float*>(w1_a), b1_a, out_a};
     const CspGenCall cb{prior_b, w0_b, b0_b, wc_b, bc_b, reinterpret_cast<const float*>(w1_b), b1_b, out_b};
     const int cols = effi_cdiv(w, 16), tiles = cols * effi_cdiv(h, 8);
-    hipLaunchKernelGGL(csp_gen_roll_rp_kernel, dim3((unsigned)tiles, 1, 2), dim3(256), 0, effi_s(stream), x, H, W, ca, cb, D, h, w, cols, tiles);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<csp_gen_roll_rp_kernel>(dim3((unsigned)tiles, 1, 2), 256, effi_s(stream), x, H, W, ca, cb, D, h, w, cols, tiles);
 }
 
 static int deconv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D, int h, int w,
@@ -3248,25 +2813,18 @@ static int deconv3d_k3s2_x3_impl(const float* in, int cin, const void* wpack_bf1
     const int tiles_x = effi_cdiv(w, 16);
     const bool al = (w & 3) == 0, half = cout <= 8;       // cout <= 8: packing with 9 fragments per chunk (see the kernel)
     hipStream_t st = effi_s(stream);
-    const bool mr2 = effi_pick_deconv_x3(cout, h, w, D, n_smp, effi_form_opts()).rows == 2;     // (launch_form.hpp: the rounds model)
-    const dim3 grid(tiles_x * effi_cdiv(h, mr2 ? 8 : 4), D, n_smp);
-#define EFFI_DC(MRV, ALV, HFV)                                                                                                     \
-    do {                                                                                                                           \
-        if (n_smp > 1)                                                                                                             \
-            hipLaunchKernelGGL((deconv3d_s2_bf16x3_batch_kernel<MRV, ALV, HFV>), grid, dim3(256), 0, st, a, in_ss, skip_ss, out_ss, \
-                               tiles_x, (int)grid.x);                                                                              \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((deconv3d_s2_bf16x3_kernel<MRV, ALV, HFV>), grid, dim3(256), 0, st, a, tiles_x, (int)grid.x);         \
-    } while (0)
-    if (mr2) {
-        if (al) { if (half) EFFI_DC(2, true, true); else EFFI_DC(2, true, false); }
-        else { if (half) EFFI_DC(2, false, true); else EFFI_DC(2, false, false); }
-    } else {
-        if (al) { if (half) EFFI_DC(1, true, true); else EFFI_DC(1, true, false); }
-        else { if (half) EFFI_DC(1, false, true); else EFFI_DC(1, false, false); }
-    }
-#undef EFFI_DC
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    const int rows = effi_pick_deconv_x3(cout, h, w, D, n_smp, effi_form_opts()).rows;          // (launch_form.hpp: the rounds model)
+    const dim3 grid(tiles_x * effi_cdiv(h, 4 * rows), D, n_smp);
+    return effi_switch<1, 2>(rows, [&](auto MR) {
+        return effi_switch<0, 1>(al, [&](auto AL) {
+            return effi_switch<0, 1>(half, [&](auto HALF) {
+                constexpr bool aligned = AL() != 0, hf = HALF() != 0;
+                if (n_smp > 1)
+                    return effi_launch<deconv3d_s2_bf16x3_batch_kernel<MR(), aligned, hf>>(grid, 256, st, a, in_ss, skip_ss, out_ss, tiles_x, (int)grid.x);
+                return effi_launch<deconv3d_s2_bf16x3_kernel<MR(), aligned, hf>>(grid, 256, st, a, tiles_x, (int)grid.x);
+            });
+        });
+    });
 }
 
 extern "C" int EFFI_FN(effi_deconv3d_k3s2_bf16x3_f32)(const float* in, int cin, const void* wpack_bf16, const float* bias, int cout, int D,
@@ -3288,13 +2846,6 @@ extern "C" int effi_conv2d_c1k7_relu_f32(const float* in, const float* weight, c
     if (!in || !weight || !bias || !out || h < 1 || w < 1) return EFFI_ERR_BADARG;
     dim3 grid(effi_cdiv(w, EFFI_C1K7_TX), effi_cdiv(h, EFFI_C1K7_TY), cout / 16);
     hipStream_t st = effi_s(stream);
-    switch (cout) {
-        case 16: hipLaunchKernelGGL(conv2d_c1k7_relu_kernel<16>, grid, dim3(256), 0, st, in, weight, bias, h, w, out); break;
-        case 32: hipLaunchKernelGGL(conv2d_c1k7_relu_kernel<32>, grid, dim3(256), 0, st, in, weight, bias, h, w, out); break;
-        case 48: hipLaunchKernelGGL(conv2d_c1k7_relu_kernel<48>, grid, dim3(256), 0, st, in, weight, bias, h, w, out); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_switch_or<16, 32, 48>(EFFI_ERR_UNSUPPORTED, cout, [&](auto COUT) { return effi_launch<conv2d_c1k7_relu_kernel<COUT()>>(grid, 256, st, in, weight, bias, h, w, out); });
 }
 #endif

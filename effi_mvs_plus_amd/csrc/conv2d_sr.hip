@@ -19,35 +19,16 @@ int fill_sr(Conv2dArgs& a, const void* const* srcs, const int* src_channels, int
     const bool wide_possible = w >= 512 || effi_option(EFFI_OPT_WIDE_TILES) == 1;
     if (hp < ((h + 15) & ~15) + 2 || wp < (wide_possible ? ((w + 63) & ~63) : ((w + 15) & ~15)) + 2) return EFFI_ERR_BADARG;
     if ((long)hp * wp * 4 >= (1L << 31)) return EFFI_ERR_UNSUPPORTED;                          // 32-bit unit offsets inside a chunk
-    a.cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src[i] = reinterpret_cast<const float*>((i < n_src) ? srcs[i] : srcs[0]);
-        a.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        if (i < n_src && (src_channels[i] & 15)) return EFFI_ERR_UNSUPPORTED;                  // a 16-channel chunk lies in one source
-        if (i < n_src && (reinterpret_cast<uintptr_t>(srcs[i]) & 15)) return EFFI_ERR_BADARG;
-        a.cin += a.ch[i];
-    }
+    a = Conv2dArgs{};
+    const int rc = conv_sources(a, srcs, src_channels, n_src, true, CH_SR);
+    if (rc != EFFI_OK) return rc;
     if ((long)cout * hp * wp >= (1L << 31)) return EFFI_ERR_UNSUPPORTED;     // the batched epilogue's 32-bit unit / Q4 offsets
+    conv_map(a, h, w);
+    conv_weights_x3(a, wpack_bf16, bias, cout, EFFI_ACT_NONE);               // (a.zeros stays null: padding is the maps' zero border)
     a.kgroups = (a.cin + 3) / 4;
-    a.zeros = nullptr;                       // not read: padding is the maps' zero border
-    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
-    a.bias = bias;
-    a.cout = cout;
-    a.h = a.hin = h;
-    a.w = a.win = w;
-    a.act = EFFI_ACT_NONE;
-    a.hd = cout / 2;
-    a.aux0 = a.aux1 = a.disp_range = nullptr;
-    a.n_range = 0;
-    a.out0 = a.out1 = nullptr;
-    a.cstride = a.ostride = (long)h * w;
-    a.zcount = a.zin = 0;
-    a.xptr0 = nullptr;
+    a.hd = cout / 2;                         // GRU z | r: the first half of the output channels is z
     a.sr_hp = hp;
     a.sr_wp = wp;
-    a.out_sr = nullptr;
-    a.aux_q4 = 0;
     return EFFI_OK;
 }
 
@@ -77,19 +58,13 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_sr)(const void* const* srcs, const 
     switch (epilogue) {
         case EFFI_EPI_PLAIN:                  // out_sr = act(conv); out0 (or NULL) = the same values as an fp32 map
             if (act < EFFI_ACT_NONE || act > EFFI_ACT_TANH) return EFFI_ERR_BADARG;
-            return dispatch_bf16x3<EFFI_EPI_PLAIN, true>(a, nt, st);
+            return effi_switch_nt<1, 2, 3, 4, 6>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_PLAIN, false, true>(a, st); });
         case EFFI_EPI_GRU_ZR:                 // out0 = z (fp32), out_sr = r * h; aux0 = h (fp32)
             if (!aux0 || !out0 || (cout % 32) != 0) return EFFI_ERR_BADARG;
-            if (nt == 2) return launch_bf16x3<2, EFFI_EPI_GRU_ZR, false, true>(a, st);
-            if (nt == 4) return launch_bf16x3<4, EFFI_EPI_GRU_ZR, false, true>(a, st);
-            if (nt == 6) return launch_bf16x3<6, EFFI_EPI_GRU_ZR, false, true>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return effi_switch_nt<2, 4, 6>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_GRU_ZR, false, true>(a, st); });
         case EFFI_EPI_GRU_Q:                  // out0 (fp32) and out_sr = (1 - z) h + z tanh(conv); aux0 = h, aux1 = z (fp32)
             if (!aux0 || !aux1 || !out0) return EFFI_ERR_BADARG;
-            if (nt == 1) return launch_bf16x3<1, EFFI_EPI_GRU_Q, false, true>(a, st);
-            if (nt == 2) return launch_bf16x3<2, EFFI_EPI_GRU_Q, false, true>(a, st);
-            if (nt == 3) return launch_bf16x3<3, EFFI_EPI_GRU_Q, false, true>(a, st);
-            return EFFI_ERR_UNSUPPORTED;
+            return effi_switch_nt<1, 2, 3>(nt, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_GRU_Q, false, true>(a, st); });
         default:
             return EFFI_ERR_UNSUPPORTED;
     }
@@ -111,13 +86,7 @@ extern "C" int EFFI_FN(effi_conv2d_k3_bf16x3_pair_sr)(const void* const* srcs_a,
     a0.out_sr = reinterpret_cast<unsigned short*>(out_sr_a);
     a1.out_sr = reinterpret_cast<unsigned short*>(out_sr_b);
     hipStream_t st = effi_s(stream);
-    switch (cout / 16) {
-        case 1: return launch_bf16x3_pair<1, true>(a0, a1, st);
-        case 2: return launch_bf16x3_pair<2, true>(a0, a1, st);
-        case 3: return launch_bf16x3_pair<3, true>(a0, a1, st);
-        case 4: return launch_bf16x3_pair<4, true>(a0, a1, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3, 4>(cout / 16, [&](auto NT) { return launch_bf16x3_pair<NT(), true>(a0, a1, st); });
 }
 
 // encoder_inputs + the pair above in ONE launch (models/update.py:86-91): relu(convc2(relu(convc1(GetCost(inv_depth))))) -> out_sr_c2,
@@ -150,12 +119,7 @@ extern "C" int EFFI_FN(effi_encoder_pair_gen_bf16x3_sr)(const float* inv_depth, 
                        weight_c1, bias_c1, weight_d1, bias_d1, hd,
                        effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds)};
     hipStream_t st = effi_s(stream);
-    switch (cout / 16) {
-        case 1: return launch_bf16x3_encgen_pair<1>(a0, a1, g, st);
-        case 2: return launch_bf16x3_encgen_pair<2>(a0, a1, g, st);
-        case 3: return launch_bf16x3_encgen_pair<3>(a0, a1, g, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3>(cout / 16, [&](auto NT) { return launch_bf16x3_encgen_pair<NT()>(a0, a1, g, st); });
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k3_k1_bf16x3_sr)(const void* const* srcs, const int* src_channels, int n_src, const void* wpack_bf16,
@@ -179,14 +143,7 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_bf16x3_sr)(const void* const* srcs, con
     a.out0 = out;
     a.out_sr = reinterpret_cast<unsigned short*>(out_sr);
     hipStream_t st = effi_s(stream);
-    switch ((cout1 + 15) / 16) {
-        case 1: return launch_bf16x3<1, EFFI_EPI_K1, false, true>(a, st);
-        case 2: return launch_bf16x3<2, EFFI_EPI_K1, false, true>(a, st);
-        case 3: return launch_bf16x3<3, EFFI_EPI_K1, false, true>(a, st);
-        case 4: return launch_bf16x3<4, EFFI_EPI_K1, false, true>(a, st);
-        case 6: return launch_bf16x3<6, EFFI_EPI_K1, false, true>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3, 4, 6>((cout1 + 15) / 16, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_K1, false, true>(a, st); });
 }
 
 // The depth head in ONE launch (models/update.py:15,21,125-127): effi_conv2d_k3_k1_bf16x3_sr with the nine tap projections of conv2
@@ -215,12 +172,7 @@ extern "C" int EFFI_FN(effi_depth_head_bf16x3_sr)(const void* const* srcs, const
     a.zin = n_range;
     a.xptr0 = disp_range;
     hipStream_t st = effi_s(stream);
-    switch ((cout1 + 15) / 16) {
-        case 1: return launch_bf16x3_head<1>(a, tile, st);
-        case 2: return launch_bf16x3_head<2>(a, tile, st);
-        case 3: return launch_bf16x3_head<3>(a, tile, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<1, 2, 3>((cout1 + 15) / 16, [&](auto NT) { return launch_bf16x3_head<NT()>(a, tile, st); });
 }
 
 extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_sr)(const void* const* srcs, const int* src_channels, int n_src,
@@ -244,12 +196,7 @@ extern "C" int EFFI_FN(effi_conv2d_k3_k1_up2x_bf16x3_sr)(const void* const* srcs
     a.zin = n_range;
     a.xptr0 = disp_range;
     hipStream_t st = effi_s(stream);
-    switch ((cout1 + 15) / 16) {
-        case 2: return launch_bf16x3<2, EFFI_EPI_K1UP, false, true>(a, st);
-        case 4: return launch_bf16x3<4, EFFI_EPI_K1UP, false, true>(a, st);
-        case 6: return launch_bf16x3<6, EFFI_EPI_K1UP, false, true>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch_nt<2, 4, 6>((cout1 + 15) / 16, [&](auto NT) { return launch_bf16x3<NT(), EFFI_EPI_K1UP, false, true>(a, st); });
 }
 
 #include "gru_fused.hpp"

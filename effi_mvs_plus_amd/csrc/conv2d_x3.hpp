@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include "launch_form.hpp"
+#include <type_traits>
 
 // This file is compiled twice (csrc/Makefile): as it stands, and with -DEFFI_BF16_ONLY, which keeps only the *_bf16x3_* entry points,
 // appends _bf16 to their names and drops the two lo terms of every split product (hi*hi only: plain bf16 operands, fp32
@@ -1122,158 +1123,189 @@ __global__ __launch_bounds__(256) void conv2d_k3_bf16x3_encgen_pair_kernel(const
                                                                              (int)blockIdx.y);
 }
 
+// ---- the host layer of the convolution entries (conv2d.hip, conv2d_sr.hip, gru_fused.hpp) ------------------------------------------
+// An entry is: validation, the argument filler, the fields it deliberately overrides, the dispatch.  A dispatch turns its runtime
+// choices (N-tile count, rows per wave, wide / aligned / half forms) into template arguments with effi_switch and launches with
+// effi_launch; a launcher takes the image / sample batch as ``const ConvBatch* bt`` (nullptr: the single-image kernel) and refuses
+// with EFFI_ERR_UNSUPPORTED what has no batched kernel.
+
+// f(std::integral_constant<int, V>) for the V of Vs... that equals v; ``miss`` when there is none
+template <int... Vs, class F>
+static int effi_switch_or(int miss, long v, F&& f) {
+    int rc = miss;
+    (void)(... || (v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false));
+    return rc;
+}
+// rows per wave, tile forms and flags: a value outside the set is a bad argument (of an option, as a rule)
+template <int... Vs, class F>
+static int effi_switch(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_BADARG, v, f); }
+// N-tile counts (and other sizes a kernel is instantiated for): a layer outside the set is unsupported
+template <int... Vs, class F>
+static int effi_switch_nt(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_UNSUPPORTED, v, f); }
+
+template <auto KERNEL, class... Args>
+static int effi_launch(dim3 grid, int threads, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, st, args...);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+
+// The argument filler: ``Conv2dArgs a{}`` (every field zero / null), then one setter each for the source list, the geometry and the
+// weights; outputs, auxiliaries and whatever an entry reuses for a meaning of its own are assigned by the entry.
+// Source list.  Both of its rules are read by kernels, so they stay per entry: the unused slots are null or alias source 0 (the split
+// kernels form addresses from every slot), and the channel counts are free (CH_ANY), whole octets in all but the last source
+// (CH_OCTETS: an octet of channels lies in one source) or whole 16-channel chunks of 16-byte aligned split-resident maps (CH_SR).
+// The entry has checked srcs, ch and n_src; source i is checked in the order null / no channels, channel rule, alignment.
+enum ConvChRule { CH_ANY, CH_OCTETS, CH_SR };
+template <class T>
+static int conv_sources(Conv2dArgs& a, const T* const* srcs, const int* ch, int n_src, bool alias0, ConvChRule rule) {
+    a.cin = 0;
+    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
+        a.src[i] = reinterpret_cast<const float*>(i < n_src ? srcs[i] : (alias0 ? srcs[0] : nullptr));
+        a.ch[i] = i < n_src ? ch[i] : 0;
+        if (i >= n_src) continue;
+        if (!srcs[i] || ch[i] < 1) return EFFI_ERR_BADARG;
+        if (rule == CH_OCTETS && i + 1 < n_src && (ch[i] & 7)) return EFFI_ERR_UNSUPPORTED;
+        if (rule == CH_SR && (ch[i] & 15)) return EFFI_ERR_UNSUPPORTED;
+        if (rule == CH_SR && (reinterpret_cast<uintptr_t>(srcs[i]) & 15)) return EFFI_ERR_BADARG;
+        a.cin += ch[i];
+    }
+    return EFFI_OK;
+}
+// Geometry: a plain 2-D map, a stride-2 map (output (hin - 1) / 2 + 1), a volume of D planes as z-batched 2-D maps, a stride-2 volume.
+static void conv_map(Conv2dArgs& a, int h, int w) {
+    a.h = a.hin = h;
+    a.w = a.win = w;
+    a.cstride = a.ostride = (long)h * w;
+}
+static void conv_map_s2(Conv2dArgs& a, int hin, int win) {
+    a.hin = hin;
+    a.win = win;
+    a.h = (hin - 1) / 2 + 1;
+    a.w = (win - 1) / 2 + 1;
+    a.cstride = (long)hin * win;
+    a.ostride = (long)a.h * a.w;
+}
+static void conv_volume(Conv2dArgs& a, int D, int h, int w) {
+    conv_map(a, h, w);
+    a.zcount = a.zin = D;
+    a.cstride = a.ostride = (long)D * h * w;
+}
+static void conv_volume_s2(Conv2dArgs& a, int D, int hin, int win) {
+    conv_map_s2(a, hin, win);
+    a.zin = D;
+    a.zcount = (D - 1) / 2 + 1;
+    a.cstride = (long)D * hin * win;
+    a.ostride = (long)a.zcount * a.h * a.w;
+}
+// Weights, bias, activation: the fp32 MFMA kernels walk ceil(cin / 4) K groups.  (The planar split-precision kernels read their
+// padding from the zero page, which their entries fetch into a.zeros; the split-resident maps carry a zero border instead.)
+static void conv_weights(Conv2dArgs& a, const float* wpack, const float* bias, int cout, int act) {
+    a.kgroups = (a.cin + 3) / 4;
+    a.wpack = wpack;
+    a.bias = bias;
+    a.cout = cout;
+    a.act = act;
+}
+static void conv_weights_x3(Conv2dArgs& a, const void* wpack_bf16, const float* bias, int cout, int act) {
+    a.wpack = reinterpret_cast<const float*>(wpack_bf16);
+    a.bias = bias;
+    a.cout = cout;
+    a.act = act;
+}
+
 // ---- split-bf16 3x3 convolution entry --------------------------------------------------------------------------
 // The rows-per-wave, wide-tile and eight-wave rules are the pick functions of launch_form.hpp (effi_pick_x3 and its twins); the
 // environment overrides of their thresholds are for A/B runs of the rule (with several views in flight the chip is filled by other
 // views' kernels, which favours the larger tiles earlier).  (Persistent workgroups with cross-tile prefetch were built and measured
 // twice: no gain, more registers.)
-template <int NT, int EPI, bool ZB = false, bool SR = false>
-static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
-    const long planes = ZB ? a.zcount : 1;
-    const EffiForm f = effi_pick_x3(NT, a.h, a.w, planes, ZB, SR, effi_form_opts());
-    const int mr = f.rows;
-    const bool wide = f.variant != 0;
-    if (wide) {
-        const int tiles_x = effi_cdiv(a.w, 16 * mr), ntiles = tiles_x * effi_cdiv(a.h, 4);
-        const dim3 grid(ntiles, (unsigned)planes);
-        if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 4, EPI, ZB, true, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-        else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, ZB, true, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-        else hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 1, EPI, ZB, true, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    if constexpr (SR) {
-        if (f.waves == 8) {               // eight waves per workgroup (launch_form.hpp: effi_pick_x3)
-            const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 8 * mr);
-            const dim3 grid(ntiles, 1);
-            if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, false, false, true, 8>), grid, dim3(512), 0, st, a, tiles_x, ntiles);
-            else hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 1, EPI, false, false, true, 8>), grid, dim3(512), 0, st, a, tiles_x, ntiles);
-            return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-        }
-    }
-    const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 4 * mr);
-    const dim3 grid(ntiles, (unsigned)planes);
-    if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 4, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-    else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-    else hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 1, EPI, ZB, false, SR>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-// Batched form (conv2d_k3_bf16x3_batch_kernel): the rule of launch_bf16x3 on the tile count of ALL images -- what was an under-filled
-// one-row launch per image becomes one launch of larger tiles.  A pixel's accumulation order (chunk, K-step, hi/lo term) does not
-// depend on the tile shape, so the result is bitwise the single-image one whatever shape either rule picks.
-template <int NT, int EPI>
-static int launch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16);
-    const EffiForm f = effi_pick_x3_batch(NT, a.h, a.w, b.n_img, effi_form_opts());
-    const int mr = f.rows;
-    if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
-    const bool wide = f.variant != 0;
-    const int tiles_x = wide ? effi_cdiv(a.w, 16 * mr) : (int)cols, ntiles = tiles_x * effi_cdiv(a.h, wide ? 4 : 4 * mr);
-    const dim3 grid(ntiles, (unsigned)b.n_img);
-    if (wide) {
-        if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 4, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-        else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 2, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-        else hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 1, EPI, true>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-    } else {
-        if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 4, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-        else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 2, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-        else hipLaunchKernelGGL((conv2d_k3_bf16x3_batch_kernel<NT, 1, EPI, false>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
 
 // Sample batch of the z-batched form (effi_conv3d_k3s1_bf16x3_f32_batch): grid (ntiles, planes, n_smp), blockIdx.z = sample; tile and
-// plane come from blockIdx.x / blockIdx.y as in conv2d_k3_bf16x3_kernel.  Rows per wave by the rule of launch_bf16x3 on the tiles of
-// all samples (never the wide tiles: the z-batched form does not take them).
+// plane come from blockIdx.x / blockIdx.y as in conv2d_k3_bf16x3_kernel.
 template <int NT, int MR>
 __global__ __launch_bounds__(256) void conv3d_k3_bf16x3_zb_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles) {
     conv2d_k3_bf16x3_tile<NT, MR, EFFI_EPI_PLAIN, true, false, false, 4>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, blockIdx.x,
                                                                          gridDim.x, blockIdx.y);
 }
-template <int NT>
-static int launch_bf16x3_zb_batch(const Conv2dArgs& a, const ConvBatch& b, hipStream_t st) {
-    const long cols = effi_cdiv(a.w, 16), planes = (long)a.zcount * b.n_img;
-    const int mr = effi_pick_x3_zb_batch(NT, a.h, a.w, planes, effi_form_opts()).rows;
-    if (mr != 1 && mr != 2 && mr != 4) return EFFI_ERR_BADARG;
-    const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a.h, 4 * mr);
-    const dim3 grid(ntiles, (unsigned)a.zcount, (unsigned)b.n_img);
-    if (mr == 4) hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 4>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-    else if (mr == 2) hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 2>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-    else hipLaunchKernelGGL((conv3d_k3_bf16x3_zb_batch_kernel<NT, 1>), grid, dim3(256), 0, st, a, b, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
 
-template <int EPI>
-static int dispatch_bf16x3_batch(const Conv2dArgs& a, const ConvBatch& b, int nt, hipStream_t st) {
-    switch (nt) {
-        case 1: return launch_bf16x3_batch<1, EPI>(a, b, st);
-        case 2: return launch_bf16x3_batch<2, EPI>(a, b, st);
-        case 3: return launch_bf16x3_batch<3, EPI>(a, b, st);
-        case 4: return launch_bf16x3_batch<4, EPI>(a, b, st);
-        case 6: return launch_bf16x3_batch<6, EPI>(a, b, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+// One launcher for the single, the batched (conv2d_k3_bf16x3_batch_kernel) and the sample-batched z-batched form
+// (conv3d_k3_bf16x3_zb_batch_kernel).  Batched: the same rule on the tile count of ALL images / of all planes of all samples -- what
+// was an under-filled one-row launch per image becomes one launch of larger tiles (never the wide ones when z-batched).  A pixel's
+// accumulation order (chunk, K-step, hi/lo term) does not depend on the tile shape, so the result is bitwise the single-image one
+// whatever shape either rule picks.  Batched kernels exist for what the batched entries take: planar maps with the pyramid's
+// epilogues (pixel shuffle: up to two N-tiles), the z-batched form with the plain one.
+template <int NT, int EPI, bool ZB = false, bool SR = false>
+static int launch_bf16x3(const Conv2dArgs& a, hipStream_t st, const ConvBatch* bt = nullptr) {
+    constexpr bool kShuf = EPI == EFFI_EPI_ADD_SHUF2 || EPI == EFFI_EPI_NHWC_ADD_SHUF2;
+    constexpr bool kBatch = !SR && (ZB ? EPI == EFFI_EPI_PLAIN : (EPI == EFFI_EPI_PLAIN || EPI == EFFI_EPI_NHWC || (kShuf && NT <= 2)));
+    if (bt && !kBatch) return EFFI_ERR_UNSUPPORTED;
+    const EffiFormOpts o = effi_form_opts();
+    const long planes = ZB ? a.zcount : 1, n = bt ? bt->n_img : 1;
+    const EffiForm f = !bt ? effi_pick_x3(NT, a.h, a.w, planes, ZB, SR, o)
+                           : (ZB ? effi_pick_x3_zb_batch(NT, a.h, a.w, planes * n, o) : effi_pick_x3_batch(NT, a.h, a.w, n, o));
+    return effi_switch<1, 2, 4>(f.rows, [&](auto MR) {
+        return effi_switch<0, 1>(f.variant, [&](auto WIDE) {
+            constexpr int mr = MR();
+            constexpr bool wide = WIDE() != 0;
+            const int tiles_x = effi_cdiv(a.w, wide ? 16 * mr : 16), ntiles = tiles_x * effi_cdiv(a.h, wide ? 4 : 4 * mr);
+            if constexpr (kBatch) {
+                if (bt) {
+                    if constexpr (!ZB)
+                        return effi_launch<conv2d_k3_bf16x3_batch_kernel<NT, mr, EPI, wide>>(dim3(ntiles, (unsigned)n), 256, st, a, *bt, tiles_x, ntiles);
+                    else if constexpr (!wide)
+                        return effi_launch<conv3d_k3_bf16x3_zb_batch_kernel<NT, mr>>(dim3(ntiles, (unsigned)a.zcount, (unsigned)n), 256, st, a, *bt,
+                                                                                   tiles_x, ntiles);
+                    else
+                        return EFFI_ERR_BADARG;        // (effi_pick_x3_zb_batch never picks the wide tile: no such kernel)
+                }
+            }
+            if constexpr (SR && !wide && mr <= 2) {
+                if (f.waves == 8) {               // eight waves per workgroup (launch_form.hpp: effi_pick_x3)
+                    const int ntiles8 = tiles_x * effi_cdiv(a.h, 8 * mr);
+                    return effi_launch<conv2d_k3_bf16x3_kernel<NT, mr, EPI, false, false, true, 8>>(dim3(ntiles8, 1), 512, st, a, tiles_x, ntiles8);
+                }
+            }
+            return effi_launch<conv2d_k3_bf16x3_kernel<NT, mr, EPI, ZB, wide, SR>>(dim3(ntiles, (unsigned)planes), 256, st, a, tiles_x, ntiles);
+        });
+    });
 }
 
 // One-launch depth head (EFFI_EPI_K1HEAD, split-resident input): workgroups of ``tile`` = 2 (8 x 16 pixels, four waves), 4 (16 x 16,
 // four waves) or 8 (16 x 16, eight waves) computed pixels, of which the interior (rows - 2) x 14 are outputs.
 template <int NT>
 static int launch_bf16x3_head(const Conv2dArgs& a, int tile, hipStream_t st) {
-    const int tr = tile == 2 ? 8 : 16;
-    const int tiles_x = effi_cdiv(a.w, 14), ntiles = tiles_x * effi_cdiv(a.h, tr - 2);
-    const dim3 grid(ntiles, 1);
-    if (tile == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EFFI_EPI_K1HEAD, false, false, true, 4>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-    else if (tile == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 4, EFFI_EPI_K1HEAD, false, false, true, 4>), grid, dim3(256), 0, st, a, tiles_x, ntiles);
-    else if (tile == 8) hipLaunchKernelGGL((conv2d_k3_bf16x3_kernel<NT, 2, EFFI_EPI_K1HEAD, false, false, true, 8>), grid, dim3(512), 0, st, a, tiles_x, ntiles);
-    else return EFFI_ERR_BADARG;
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-
-template <int EPI, bool SR = false>
-static int dispatch_bf16x3(const Conv2dArgs& a, int nt, hipStream_t st) {
-    switch (nt) {
-        case 1: return launch_bf16x3<1, EPI, false, SR>(a, st);
-        case 2: return launch_bf16x3<2, EPI, false, SR>(a, st);
-        case 3: return launch_bf16x3<3, EPI, false, SR>(a, st);
-        case 4: return launch_bf16x3<4, EPI, false, SR>(a, st);
-        case 6: return launch_bf16x3<6, EPI, false, SR>(a, st);
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
+    return effi_switch<2, 4, 8>(tile, [&](auto TILE) {
+        constexpr int mr = TILE() == 4 ? 4 : 2, nw = TILE() == 8 ? 8 : 4, tr = TILE() == 2 ? 8 : 16;
+        const int tiles_x = effi_cdiv(a.w, 14), ntiles = tiles_x * effi_cdiv(a.h, tr - 2);
+        return effi_launch<conv2d_k3_bf16x3_kernel<NT, mr, EFFI_EPI_K1HEAD, false, false, true, nw>>(dim3(ntiles, 1), 64 * nw, st, a, tiles_x, ntiles);
+    });
 }
 
 // Pair launch (see conv2d_k3_bf16x3_pair_kernel): tile shape chosen as launch_bf16x3 does for two planes.
 template <int NT, bool SR = false>
 static int launch_bf16x3_pair(const Conv2dArgs& a0, const Conv2dArgs& a1, hipStream_t st) {
-    const long cols = effi_cdiv(a0.w, 16);
     const EffiForm f = effi_pick_x3_pair(NT, a0.h, a0.w, SR, effi_form_opts());
-    const int mr = f.rows;
-    if (f.variant != 0) {
-        const int tiles_x = effi_cdiv(a0.w, 64), ntiles = tiles_x * effi_cdiv(a0.h, 4);
-        hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 4, true, SR>), dim3(ntiles, 2), dim3(256), 0, st, a0, a1, tiles_x, ntiles);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    if constexpr (SR) {
-        if (f.waves == 8) {
-            const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a0.h, 8 * mr);
-            const dim3 grid(ntiles, 2);
-            if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 2, false, true, 8>), grid, dim3(512), 0, st, a0, a1, tiles_x, ntiles);
-            else hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 1, false, true, 8>), grid, dim3(512), 0, st, a0, a1, tiles_x, ntiles);
-            return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_switch<1, 2, 4>(f.rows, [&](auto MR) {
+        constexpr int mr = MR();
+        if constexpr (mr == 4) {
+            if (f.variant != 0) {             // 4 x 64 tiles
+                const int tiles_x = effi_cdiv(a0.w, 64), ntiles = tiles_x * effi_cdiv(a0.h, 4);
+                return effi_launch<conv2d_k3_bf16x3_pair_kernel<NT, 4, true, SR>>(dim3(ntiles, 2), 256, st, a0, a1, tiles_x, ntiles);
+            }
         }
-    }
-    const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a0.h, 4 * mr);
-    const dim3 grid(ntiles, 2);
-    if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 4, false, SR>), grid, dim3(256), 0, st, a0, a1, tiles_x, ntiles);
-    else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 2, false, SR>), grid, dim3(256), 0, st, a0, a1, tiles_x, ntiles);
-    else hipLaunchKernelGGL((conv2d_k3_bf16x3_pair_kernel<NT, 1, false, SR>), grid, dim3(256), 0, st, a0, a1, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+        const int tiles_x = effi_cdiv(a0.w, 16), ntiles = tiles_x * effi_cdiv(a0.h, 4 * mr);
+        if constexpr (SR && mr <= 2) {
+            if (f.waves == 8) {
+                const int ntiles8 = tiles_x * effi_cdiv(a0.h, 8 * mr);
+                return effi_launch<conv2d_k3_bf16x3_pair_kernel<NT, mr, false, true, 8>>(dim3(ntiles8, 2), 512, st, a0, a1, tiles_x, ntiles8);
+            }
+        }
+        return effi_launch<conv2d_k3_bf16x3_pair_kernel<NT, mr, false, SR>>(dim3(ntiles, 2), 256, st, a0, a1, tiles_x, ntiles);
+    });
 }
 
 // Generated-input pair (conv2d_k3_bf16x3_encgen_pair_kernel): the MR rule of launch_bf16x3_pair, 4 waves.
 template <int NT>
 static int launch_bf16x3_encgen_pair(const Conv2dArgs& a0, const Conv2dArgs& a1, const EncGenArgs& g, hipStream_t st) {
-    const long cols = effi_cdiv(a0.w, 16);
     int mr = effi_pick_x3_rows(NT, a0.h, a0.w, 2, effi_form_opts());
     // always 16-column tiles: the generated image pays per STAGED pixel (24 volume taps each), and a 4 x 64 tile stages 1.55 x its
     // pixels against 1.27 x for 16 x 16 (592x800, hd 16: 55 us per launch with wide tiles, 47 us without; the loaded form gains 5 %
@@ -1281,13 +1313,10 @@ static int launch_bf16x3_encgen_pair(const Conv2dArgs& a0, const Conv2dArgs& a1,
     // "4 rows per wave" is 3 here: 14 x 18 = 252 staged pixels are ONE lookup per thread; 18 x 18 = 324 make 68 threads do a second
     // one while 188 wait (option enc_gen_mr3 = 0: 4 rows)
     if (mr == 4 && effi_opt_or(EFFI_OPT_ENC_GEN_MR3, 1) != 0) mr = 3;
-    const int tiles_x = (int)cols, ntiles = tiles_x * effi_cdiv(a0.h, 4 * mr);
-    const dim3 grid(ntiles, 2);
-    if (mr == 4) hipLaunchKernelGGL((conv2d_k3_bf16x3_encgen_pair_kernel<NT, 4, false>), grid, dim3(256), 0, st, a0, a1, g, tiles_x, ntiles);
-    else if (mr == 3) hipLaunchKernelGGL((conv2d_k3_bf16x3_encgen_pair_kernel<NT, 3, false>), grid, dim3(256), 0, st, a0, a1, g, tiles_x, ntiles);
-    else if (mr == 2) hipLaunchKernelGGL((conv2d_k3_bf16x3_encgen_pair_kernel<NT, 2, false>), grid, dim3(256), 0, st, a0, a1, g, tiles_x, ntiles);
-    else hipLaunchKernelGGL((conv2d_k3_bf16x3_encgen_pair_kernel<NT, 1, false>), grid, dim3(256), 0, st, a0, a1, g, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_switch<1, 2, 3, 4>(mr, [&](auto MR) {
+        const int tiles_x = effi_cdiv(a0.w, 16), ntiles = tiles_x * effi_cdiv(a0.h, 4 * MR());
+        return effi_launch<conv2d_k3_bf16x3_encgen_pair_kernel<NT, MR(), false>>(dim3(ntiles, 2), 256, st, a0, a1, g, tiles_x, ntiles);
+    });
 }
 
 }  // namespace

@@ -242,8 +242,7 @@ __global__ __launch_bounds__(256) void gru_zr_q_fused_kernel(const GruFusedArgs 
 template <int NH>
 static int launch_gru_fused(const GruFusedArgs& g, hipStream_t st) {
     const int tiles_x = effi_cdiv(g.w, 14), ntiles = tiles_x * effi_cdiv(g.h, 14);
-    hipLaunchKernelGGL((gru_zr_q_fused_kernel<NH>), dim3(ntiles), dim3(256), 0, st, g, tiles_x, ntiles);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+    return effi_launch<gru_zr_q_fused_kernel<NH>>(dim3(ntiles), 256, st, g, tiles_x, ntiles);
 }
 
 }  // namespace

@@ -76,14 +76,14 @@ static inline EffiForm effi_pick_x3(int nt, int h, int w, long planes, bool zb, 
     return EffiForm{mr, 16, 4, 1, 0};
 }
 
-// launch_bf16x3_batch: the rule of launch_bf16x3 on the tile count of ALL images
+// launch_bf16x3 with an image batch: the single-image rule on the tile count of ALL images
 static inline EffiForm effi_pick_x3_batch(int nt, int h, int w, long n_img, const EffiFormOpts& o) {
     const int mr = effi_pick_x3_rows(nt, h, w, n_img, o);
     const bool wide = o.wide_tiles >= 0 ? o.wide_tiles != 0 : (mr == 4 && w >= 512);
     return wide ? EffiForm{mr, 16 * mr, 4, 1, 1} : EffiForm{mr, 16, 4, 1, 0};
 }
 
-// launch_bf16x3_zb_batch: the tiles of all planes of all samples; never the wide tiles
+// launch_bf16x3, z-batched form with a sample batch: the tiles of all planes of all samples; never the wide tiles
 static inline EffiForm effi_pick_x3_zb_batch(int nt, int h, int w, long planes, const EffiFormOpts& o) {
     return EffiForm{effi_pick_x3_rows(nt, h, w, planes, o), 16, 4, 1, 0};
 }
@@ -96,7 +96,7 @@ static inline EffiForm effi_pick_x3_pair(int nt, int h, int w, bool sr, const Ef
     return EffiForm{mr, 16, 4, 1, 0};
 }
 
-// ---- generic fp32 MFMA convolution (conv2d.hip: launch2d, launch2d_batch) ---------------------------------------------------------
+// ---- generic fp32 MFMA convolution (conv2d.hip: launch2d, single image or batch) ---------------------------------------------------
 // rows per wave: the largest of {4, 2, 1} that still yields >= 2 workgroups per CU (256 CUs) over the tiles of all images; a 1x1
 // convolution takes at least two rows (and four from 256 tiles); rows of w % 4 != 0 take the 16 x 16 kernel
 static inline EffiForm effi_pick_generic(int ks, int h, int w, long n_img) {
@@ -110,7 +110,7 @@ static inline EffiForm effi_pick_generic(int ks, int h, int w, long n_img) {
     return EffiForm{mr, 16, 4, 1, 0};
 }
 
-// ---- fp32 z-batched 3-D forms (dispatch3d_planes, dispatch3d_planes_s2), 5x5 stride 2 (dispatch_k5s2) ------------------------------
+// ---- fp32 z-batched 3-D forms (launch3d_planes, stride 1 and 2), 5x5 stride 2 (launch_k5s2) ----------------------------------------
 // rows per wave: keep >= 2 workgroups per CU over all planes (of all samples) / all images; the stride-2 forms stop at two rows
 static inline EffiForm effi_pick_planes(int h, int w, long planes, int max_rows) {
     const long cols = effi_cdiv(w, 16);
@@ -119,7 +119,7 @@ static inline EffiForm effi_pick_planes(int h, int w, long planes, int max_rows)
     return EffiForm{1, 16, 4, 1, 0};
 }
 
-// ---- split-precision stride-2 forms (launch_s2_x3, _batch, _zb_batch) -------------------------------------------------------------
+// ---- split-precision stride-2 forms (launch_s2_x3: 2-D, z-batched, either one batched) --------------------------------------------
 // two rows per wave from 400 workgroups: tiles x N-tile groups x planes (of all samples) or images
 static inline EffiForm effi_pick_s2_x3(int h, int w, int ngroups, long planes) {
     const int cols = effi_cdiv(w, 16);
