@@ -237,6 +237,22 @@ LOOKUP_ROUNDINGS = 4        # vol_lookup1d (lookup1d_index): 1/q, 1/dmax, their 
 #   step = (smax - smin) / (nq - 1), k * step, smin + k * step: 3 roundings of terms <= the sum: 11u of (dv + half) <= 11 * (5/3) u of
 #   s >= dv - half = 3/4 dv, i.e. 19u; hypothesis depth 1/s, then the look-up's own 1/q, 1/dmax, difference: 23u.  With K = 2 in front
 #   the proposed count of 12 stands for 24u: kept.
+# Re-counted against effi_getcost_pixel (common.hpp), the GetCost of the fused entries (tests/test_gpu_getcost_readout.py), whose three
+# reciprocals on the way (dv, 1/s, 1/q) and 1/dmax are effi_lk_rcp, <= 1 ulp = 2u each, a = dv, H = half <= a / 4, n = nq:
+#   depth: 5u (scale_inv_depth as above) + 1/s0 (IEEE, u) = 6u; dv = rcp(depth): 8u a.
+#   smin = (dv - H)(1 + d1), smax = (dv + H)(1 + d2): the error of dv is COMMON to both, so smax - smin = 2H + d2 (dv + H) - d1 (dv - H) is
+#   off by 2u a, + u 2H of the subtraction; step: the division (IEEE) and k * step add 2u of k * step <= 2H.  The largest error, at
+#   k = n - 1: 8u a + u (a - H) [smin] + 2u a + 2u H + 4u H [k * step] + u (a + H) [the sum] = u (12 a + 6 H) <= 13.5u a.
+#   Relative to s = a - H + 2 H k / (n - 1) it is largest at k = 0: (8 a + (a - H) + (a - H)) / (a - H) <= 8 * 4/3 + 2 = 12.7u
+#   (k = n - 1: (12 a + 6 H) / (a + H) <= 12u): <= 13u of s.
+#   1/s and the look-up's 1/q: 2u each, 17u of |1/q|; 1/dmax: 2u of |1/dmax|; the difference: u (|1/q| + |1/dmax|):
+#   <= 18u (|1/q| + |1/dmax|) <= K * 12 u = 24u.  The count of 12 with K = 2 stands for effi_getcost_pixel as well; depth input
+#   (input_is_depth) starts from dv = rcp(x), 2u instead of 8u.
+#   den's two reciprocals are effi_lk_rcp too: K u (|1/dmin| + |1/dmax|) / den, the second term of lookup_box, is their 1 ulp exactly.
+#   The grid chain of lookup1d_index with effi_lk_div (<= 1 ulp) for both quotients: den's two roundings, the quotient (2u), * (Dp-1)
+#   = 5u |t|; 2t / (Dp-1) (2u |t|), - 1 (u |t - (Dp-1)/2|), + 1 and * (Dp-1) (u |t| each): 10u |t| + u Dp / 2 against the
+#   8u (|t| + Dp) of lookup_box; the 2u |t| it may lack come out of the 6u (|1/q| + |1/dmax|) (Dp-1) / den >= 6u |t| that the
+#   numerator's 24u leave over its 18u.
 GETCOST_ROUNDINGS = 12
 
 
