@@ -54,6 +54,12 @@ SIGNATURES = {
     # optimizer step (csrc/optim.hip)
     "effi_adamw_max_tensors": [],
     "effi_adamw_multi_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _d, _d, _d, _vp],
+    # global gradient norm, clipped / guarded step (csrc/optim.hip); effi_gradnorm_chunks returns long: restype set in lib()
+    "effi_gradnorm_max_tensors": [],
+    "effi_gradnorm_chunks": [_vp, _i],
+    "effi_gradnorm_partial_f32": [_vp, _vp, _i, _vp, _vp],
+    "effi_gradnorm_finish_f32": [_vp, _l, _d, _vp, _vp, _vp],
+    "effi_adamw_multi_clip_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _d, _d, _d, _vp, _i, _vp],
     "effi_fusion_vis_filter_f32": [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp],
     "effi_fusion_points_f32": [_i, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_dtu_reproject_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
@@ -238,6 +244,7 @@ def lib():
         handle.effi_option_unset.restype = _l
         handle.effi_metrics_scratch_bytes.argtypes = [_l, _i, _i]
         handle.effi_metrics_scratch_bytes.restype = _l
+        handle.effi_gradnorm_chunks.restype = _l        # a count, or -1: not a status code
         _lib = handle
     return _lib
 

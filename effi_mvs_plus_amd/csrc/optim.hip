@@ -32,6 +32,27 @@
 // tensor otherwise -- weight gradients are slices of arena blocks and a user's tensor may be a view at an odd offset, so alignment
 // is a per-tensor run-time fact.  Writes stay inside [ptr, ptr + numel) of p, exp_avg, exp_avg_sq and the one element of step;
 // g is only read.
+//
+// Global gradient norm, clipping and the non-finite guard (torch.nn.utils.clip_grad_norm_ between backward() and step(), and the
+// skipped step of a gradient scaler, inside the step).  gradnorm_partial_kernel: the same chunking over up to GN_MAX_T gradients per
+// call, one workgroup per chunk; per element sq = (double)g * (double)g, which is EXACT (a 24-bit by 24-bit product fits in 53
+// bits); a thread adds its elements in a fixed order in double, the 64 lanes of a wave are folded by a fixed shuffle tree, the four
+// waves through LDS, and thread 0 writes partial[blockIdx.x] as a double.  No atomics: the order of every addition is a function of
+// the layout alone, so two runs agree bitwise; every slot is written on every call, so the workspace is never zeroed.
+// gradnorm_finish_kernel (one workgroup) adds the n_partial doubles -- a strided pass per thread, then the same tree -- and then, in
+// this order:
+//     norm  = (float)sqrt(total)                 (double sqrt, one rounding to fp32)
+//     den   = norm + 1e-6f                       (fp32)
+//     coef  = (float)max_norm / den              (fp32, correctly rounded)
+//     coef  = coef > 1.0f ? 1.0f : coef          (NaN stays NaN)
+//     finite = isfinite(norm)
+// and writes clip[0] = norm, clip[1] = coef, clip[2] = finite ? 1 : 0, clip[3] = 0; a given `skipped` counter (int64) is incremented
+// when !finite.  The sum itself cannot overflow in double (2^31 chunks of 2048 squares below 2^256), so "non-finite" is an inf or a
+// NaN among the gradients -- or a norm above FLT_MAX, which rounds to inf in fp32 and counts as non-finite as well.
+// The clipped step (CLIP = true instantiations): a workgroup reads clip[1] and clip[2] once, next to its scalars; with `skip` set and
+// clip[2] == 0 it returns before it writes anything, and the step kernel increments no counter; otherwise each element uses
+// g' = g * coef (one fp32 rounding) in the list above.  coef == 1.0f gives g' == g bitwise: a step that does not clip is the
+// unclipped step.
 #include "common.hpp"
 
 #include <climits>
@@ -54,11 +75,18 @@ struct AdamWArgs {              // by-value kernel argument
     double lr, beta1, beta2, eps, wd;
     const float* lr_dev;
     int n;
+    const float* clip;          // the clipped entry only: the four floats gradnorm_finish_kernel wrote
+    int skip;                   // the clipped entry only: leave everything as it is when clip[2] == 0
 };
 static_assert(sizeof(AdamWArgs) <= 3584, "kernel arguments: HIP allows 4 KB; keep a margin for the hidden ones");
 static_assert(AW_CHUNK % 4 == 0 && AW_CHUNK % AW_THREADS == 0, "a chunk starts 16-byte aligned in an aligned tensor");
 
+// CLIP = false is the unclipped entry's kernel: a.clip and a.skip are not looked at
+template <bool CLIP>
 __global__ __launch_bounds__(64) void adamw_step_kernel(AdamWArgs a) {
+    if constexpr (CLIP) {
+        if (a.skip && a.clip[2] == 0.0f) return;
+    }
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < a.n) a.step[i][0] += 1.0f;
 }
@@ -86,8 +114,10 @@ __device__ __forceinline__ void adamw_element(const AdamWScalars& k, float& p, f
     v = v1;
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(AW_THREADS) void adamw_update_kernel(AdamWArgs a) {
     __shared__ AdamWScalars ks;
+    __shared__ float kclip[2];                  // CLIP: coefficient, finite flag
     const int c = blockIdx.x;
     int lo = 0, hi = a.n - 1;                   // first tensor whose running sum exceeds c (uniform)
     while (lo < hi) {
@@ -111,9 +141,15 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_update_kernel(AdamWArgs a) {
         ks.a = (float)(lr / bc1);
         ks.c2 = (float)sqrt(bc2);
         ks.e = (float)a.eps;
+        if constexpr (CLIP) kclip[0] = a.clip[1], kclip[1] = a.clip[2];
     }
     __syncthreads();
     const AdamWScalars k = ks;
+    float coef = 1.0f;
+    if constexpr (CLIP) {
+        if (a.skip && kclip[1] == 0.0f) return;     // uniform: nothing of this chunk is written
+        coef = kclip[0];
+    }
     float* __restrict__ p = a.p[t] + i0;
     const float* __restrict__ g = a.g[t] + i0;
     float* __restrict__ m = a.m[t] + i0;
@@ -124,9 +160,10 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_update_kernel(AdamWArgs a) {
         const int n4 = len >> 2;
         for (int j = threadIdx.x; j < n4; j += AW_THREADS) {
             float4 pv = reinterpret_cast<const float4*>(p)[j];
-            const float4 gv = reinterpret_cast<const float4*>(g)[j];
+            float4 gv = reinterpret_cast<const float4*>(g)[j];
             float4 mv = reinterpret_cast<const float4*>(m)[j];
             float4 vv = reinterpret_cast<const float4*>(v)[j];
+            if constexpr (CLIP) gv.x = gv.x * coef, gv.y = gv.y * coef, gv.z = gv.z * coef, gv.w = gv.w * coef;
             adamw_element(k, pv.x, gv.x, mv.x, vv.x);
             adamw_element(k, pv.y, gv.y, mv.y, vv.y);
             adamw_element(k, pv.z, gv.z, mv.z, vv.z);
@@ -138,8 +175,9 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_update_kernel(AdamWArgs a) {
         done = n4 << 2;
     }
     for (int j = done + threadIdx.x; j < len; j += AW_THREADS) {
-        float pj = p[j], mj = m[j], vj = v[j];
-        adamw_element(k, pj, g[j], mj, vj);
+        float pj = p[j], mj = m[j], vj = v[j], gj = g[j];
+        if constexpr (CLIP) gj = gj * coef;
+        adamw_element(k, pj, gj, mj, vj);
         p[j] = pj;
         m[j] = mj;
         v[j] = vj;
@@ -170,7 +208,154 @@ int aw_pack(float* const* p, const float* const* g, float* const* exp_avg, float
     return EFFI_OK;
 }
 
+// ---- global gradient norm ----
+constexpr int GN_MAX_T = 128;                   // gradients per call: 20 bytes each in the argument
+
+struct GradNormArgs {           // by-value kernel argument
+    const float* g[GN_MAX_T];
+    long numel[GN_MAX_T];
+    int chunk_end[GN_MAX_T];    // running sum of chunks, as AdamWArgs::chunk_end
+    double* partial;            // one double per chunk of this call
+    int n;
+};
+static_assert(sizeof(GradNormArgs) <= 3584, "kernel arguments: HIP allows 4 KB; keep a margin for the hidden ones");
+
+// sum over the workgroup in a fixed order: lanes by a shuffle tree, waves through LDS; the result is valid in thread 0
+__device__ __forceinline__ double gn_block_sum(double acc, double* ws) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+static_assert(AW_THREADS == 256, "gn_block_sum folds four waves");
+
+__device__ __forceinline__ double gn_sq(float g) { return (double)g * (double)g; }
+
+__global__ __launch_bounds__(AW_THREADS) void gradnorm_partial_kernel(GradNormArgs a) {
+    __shared__ double ws[AW_THREADS / 64];
+    const int c = blockIdx.x;
+    int lo = 0, hi = a.n - 1;                   // first tensor whose running sum exceeds c (uniform)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a.chunk_end[mid] > c) hi = mid;
+        else lo = mid + 1;
+    }
+    const int t = lo;
+    const long numel = a.numel[t];
+    const long i0 = (long)(c - (t ? a.chunk_end[t - 1] : 0)) * AW_CHUNK;
+    // (i0 >= numel cannot happen for a table gn_pack built; a wrong one reads nothing and still writes its slot)
+    const int len = i0 >= numel ? 0 : (int)(numel - i0 < AW_CHUNK ? numel - i0 : AW_CHUNK);
+    const float* __restrict__ g = a.g[t] + i0;
+    double acc = 0.0;
+    int done = 0;
+    if (((uintptr_t)a.g[t] & 15) == 0) {
+        const int n4 = len >> 2;
+        for (int j = threadIdx.x; j < n4; j += AW_THREADS) {
+            const float4 gv = reinterpret_cast<const float4*>(g)[j];
+            acc += gn_sq(gv.x);
+            acc += gn_sq(gv.y);
+            acc += gn_sq(gv.z);
+            acc += gn_sq(gv.w);
+        }
+        done = n4 << 2;
+    }
+    for (int j = done + threadIdx.x; j < len; j += AW_THREADS) acc += gn_sq(g[j]);
+    const double total = gn_block_sum(acc, ws);
+    if (threadIdx.x == 0) a.partial[c] = total;
+}
+
+__global__ __launch_bounds__(AW_THREADS) void gradnorm_finish_kernel(const double* __restrict__ partial, long n_partial, float max_norm,
+                                                                     float* __restrict__ clip, long long* __restrict__ skipped) {
+    __shared__ double ws[AW_THREADS / 64];
+    double acc = 0.0;
+    for (long j = threadIdx.x; j < n_partial; j += AW_THREADS) acc += partial[j];
+    const double total = gn_block_sum(acc, ws);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(total);
+        const float den = norm + 1e-6f;
+        float coef = max_norm / den;
+        coef = coef > 1.0f ? 1.0f : coef;
+        const bool finite = isfinite(norm);
+        clip[0] = norm, clip[1] = coef, clip[2] = finite ? 1.0f : 0.0f, clip[3] = 0.0f;
+        if (skipped && !finite) skipped[0] += 1;
+    }
+}
+
+// chunks of n tensors, or -1: a null array, n < 0, a negative size, more than INT_MAX chunks
+long gn_chunks(const long* numel, int n) {
+    if (n < 0 || (n > 0 && !numel)) return -1;
+    long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 0) return -1;
+        total += numel[i] / AW_CHUNK + (numel[i] % AW_CHUNK != 0);
+        if (total > INT_MAX) return -1;
+    }
+    return total;
+}
+
+int gn_pack(const float* const* g, const long* numel, int n, double* partial, GradNormArgs* out, int* chunks) {
+    if (!g || !numel || n < 1 || n > GN_MAX_T) return EFFI_ERR_BADARG;
+    GradNormArgs a = {};
+    long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!g[i] || numel[i] < 0) return EFFI_ERR_BADARG;
+        total += numel[i] / AW_CHUNK + (numel[i] % AW_CHUNK != 0);
+        if (total > INT_MAX) return EFFI_ERR_BADARG;            // the grid's x extent
+        a.g[i] = g[i];
+        a.numel[i] = numel[i];
+        a.chunk_end[i] = (int)total;
+    }
+    if (total > 0 && !partial) return EFFI_ERR_BADARG;
+    a.partial = partial;
+    a.n = n;
+    *out = a;
+    *chunks = (int)total;
+    return EFFI_OK;
+}
+
 }  // namespace
+
+extern "C" int effi_gradnorm_max_tensors(void) { return GN_MAX_T; }
+
+extern "C" long effi_gradnorm_chunks(const long* numel, int n) { return gn_chunks(numel, n); }
+
+extern "C" int effi_gradnorm_partial_f32(const float* const* g, const long* numel, int n, double* partial, effi_stream_t stream) {
+    GradNormArgs a;
+    int chunks = 0;
+    const int rc = gn_pack(g, numel, n, partial, &a, &chunks);
+    if (rc != EFFI_OK) return rc;
+    if (chunks > 0) hipLaunchKernelGGL(gradnorm_partial_kernel, dim3(chunks), dim3(AW_THREADS), 0, effi_s(stream), a);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_gradnorm_finish_f32(const double* partial, long n_partial, double max_norm, float* clip, long long* skipped,
+                                        effi_stream_t stream) {
+    if (!clip || n_partial < 0 || (n_partial > 0 && !partial) || !(max_norm >= 0.0)) return EFFI_ERR_BADARG;
+    hipLaunchKernelGGL(gradnorm_finish_kernel, dim3(1), dim3(AW_THREADS), 0, effi_s(stream), partial, n_partial, (float)max_norm, clip,
+                       skipped);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
+
+extern "C" int effi_adamw_multi_clip_f32(float* const* p, const float* const* g, float* const* exp_avg, float* const* exp_avg_sq,
+                                         float* const* step, const long* numel, int n, double lr, const float* lr_dev, double beta1,
+                                         double beta2, double eps, double weight_decay, const float* clip, int skip_nonfinite,
+                                         effi_stream_t stream) {
+    if (!clip) return EFFI_ERR_BADARG;
+    AdamWArgs a;
+    int chunks = 0;
+    const int rc = aw_pack(p, g, exp_avg, exp_avg_sq, step, numel, n, lr, lr_dev, beta1, beta2, eps, weight_decay, &a, &chunks);
+    if (rc != EFFI_OK) return rc;
+    a.clip = clip;
+    a.skip = skip_nonfinite != 0;
+    hipStream_t st = effi_s(stream);
+    hipLaunchKernelGGL(adamw_step_kernel<true>, dim3(effi_cdiv(n, 64)), dim3(64), 0, st, a);
+    if (chunks > 0) hipLaunchKernelGGL(adamw_update_kernel<true>, dim3(chunks), dim3(AW_THREADS), 0, st, a);
+    EFFI_LAUNCH_CHECK();
+    return EFFI_OK;
+}
 
 extern "C" int effi_adamw_max_tensors(void) { return AW_MAX_T; }
 
@@ -182,8 +367,8 @@ extern "C" int effi_adamw_multi_f32(float* const* p, const float* const* g, floa
     const int rc = aw_pack(p, g, exp_avg, exp_avg_sq, step, numel, n, lr, lr_dev, beta1, beta2, eps, weight_decay, &a, &chunks);
     if (rc != EFFI_OK) return rc;
     hipStream_t st = effi_s(stream);
-    hipLaunchKernelGGL(adamw_step_kernel, dim3(effi_cdiv(n, 64)), dim3(64), 0, st, a);
-    if (chunks > 0) hipLaunchKernelGGL(adamw_update_kernel, dim3(chunks), dim3(AW_THREADS), 0, st, a);
+    hipLaunchKernelGGL(adamw_step_kernel<false>, dim3(effi_cdiv(n, 64)), dim3(64), 0, st, a);
+    if (chunks > 0) hipLaunchKernelGGL(adamw_update_kernel<false>, dim3(chunks), dim3(AW_THREADS), 0, st, a);
     EFFI_LAUNCH_CHECK();
     return EFFI_OK;
 }

@@ -1486,11 +1486,69 @@ def _adamw_slices(n, k):
     return [(s, min(n, s + k)) for s in range(0, n, k)]
 
 
-def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay):
+def gradnorm_max_tensors():
+    """Most gradients one ``effi_gradnorm_partial_f32`` call takes (host-only query: needs no GPU)."""
+    return int(_lib.lib().effi_gradnorm_max_tensors())
+
+
+def grad_norm_multi(grads, max_norm=float("inf"), clip=None, skipped=None):
+    """The 2-norm over all elements of a list of fp32 device tensors and the coefficient that clips it to ``max_norm`` (what
+    ``torch.nn.utils.clip_grad_norm_`` computes; the gradients are only read): one launch per ``gradnorm_max_tensors()`` tensors
+    and one that finishes.  -> clip, a 4-element fp32 device tensor [norm, min(1, max_norm / (norm + 1e-6)), 1 if the norm is
+    finite else 0, 0] (``clip``: such a tensor to write into).  ``skipped`` (optional one-element int64 device tensor) += 1 when
+    the norm is not finite.  Deterministic: exact squares, double sums in a fixed order, no atomics (csrc/optim.hip).  An empty
+    list has norm 0; it needs ``clip`` to say which device."""
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"grad_norm_multi: max_norm >= 0 expected (inf: never clip), got {max_norm}")
+    n = len(grads)
+    if n == 0 and clip is None:
+        raise ValueError("grad_norm_multi: an empty list needs the clip tensor: it names the device")
+    f32 = torch.float32
+    dev = _t(grads[0] if n else clip, "grads[0]" if n else "clip").device
+    idx = dev.index
+    ptrs, numel = [], []
+    for i, g in enumerate(grads):
+        # the checks of _t, once per call instead of once per tensor; _t words the refusal
+        if not isinstance(g, torch.Tensor) or g.dtype is not f32 or g.get_device() != idx or not g.is_contiguous():
+            _t(g, f"grads[{i}]")
+            raise ValueError(f"grad_norm_multi: grads[{i}] lives on {g.device}, grads[0] on {dev}: one device per call")
+        ptrs.append(g.data_ptr())
+        numel.append(g.numel())
+    if clip is None:
+        clip = torch.empty(4, dtype=f32, device=dev)
+    else:
+        _t(clip, "clip")
+        if clip.numel() != 4 or clip.device != dev:
+            raise ValueError("grad_norm_multi: clip is four fp32 elements on the gradients' device")
+    if skipped is not None:
+        if not isinstance(skipped, torch.Tensor) or skipped.dtype is not torch.int64 or skipped.numel() != 1 or skipped.device != dev:
+            raise ValueError("grad_norm_multi: skipped is one int64 element on the gradients' device")
+    L, st = _lib.lib(), _stream()
+    total = int(L.effi_gradnorm_chunks((C.c_long * max(n, 1))(*numel), n))
+    if total < 0:
+        raise ValueError("grad_norm_multi: more than 2^31 - 1 chunks of 2048 elements")
+    partial = torch.empty(total, dtype=torch.float64, device=dev)          # every slot is written by the launches below
+    base = 0
+    for s, e in _adamw_slices(n, gradnorm_max_tensors()):
+        sizes = (C.c_long * (e - s))(*numel[s:e])
+        # an empty tensor has no storage and the entry refuses null pointers: it gets the clip tensor's address, never read through
+        arr = (C.c_void_p * (e - s))(*[p or clip.data_ptr() for p in ptrs[s:e]])
+        check(L.effi_gradnorm_partial_f32(arr, sizes, e - s, C.c_void_p(partial.data_ptr() + 8 * base) if total else None, st),
+              "effi_gradnorm_partial_f32")
+        base += int(L.effi_gradnorm_chunks(sizes, e - s))
+    check(L.effi_gradnorm_finish_f32(_p(partial) if total else None, total, max_norm, _p(clip), _p(skipped), st), "effi_gradnorm_finish_f32")
+    return clip
+
+
+def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay, clip=None, skip_nonfinite=False):
     """One AdamW step (train.py:263,441; torch.optim.AdamW, amsgrad=False, maximize=False) IN PLACE over lists of tensors: two launches
     per ``adamw_max_tensors()`` tensors.  params / exp_avgs / exp_avg_sqs are updated, steps (0-dim fp32 device tensors, one per
     parameter) are incremented first, grads are only read.  lr: a number, or a one-element fp32 device tensor the kernel reads when
-    it runs (a captured step then follows a scheduler that fills it)."""
+    it runs (a captured step then follows a scheduler that fills it).  ``clip`` (the tensor of ``grad_norm_multi``): every gradient
+    element is read as g * clip[1]; with ``skip_nonfinite`` nothing at all is written, counters included, when clip[2] == 0."""
+    if clip is None and skip_nonfinite:
+        raise ValueError("adamw_multi: skip_nonfinite needs the clip tensor of grad_norm_multi")
     n = len(params)
     if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
         raise ValueError("adamw_multi: one gradient, exp_avg, exp_avg_sq and step per parameter expected")
@@ -1521,12 +1579,20 @@ def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, e
         lr_dev = _t(lr, "lr")
         if lr_dev.numel() != 1 or lr_dev.device != dev:
             raise ValueError("adamw_multi: a tensor lr is one fp32 element on the parameters' device")
-    fn, st = _lib.lib().effi_adamw_multi_f32, _stream()
+    if clip is not None:
+        _t(clip, "clip")
+        if clip.numel() != 4 or clip.device != dev:
+            raise ValueError("adamw_multi: clip is the four fp32 elements of grad_norm_multi on the parameters' device")
+    st = _stream()
     lrv = 0.0 if lr_dev is not None else float(lr)
     for s, e in _adamw_slices(n, adamw_max_tensors()):
         arr = C.c_void_p * (e - s)
-        check(fn(arr(*pp[s:e]), arr(*pg[s:e]), arr(*pm[s:e]), arr(*pv[s:e]), arr(*ps[s:e]), (C.c_long * (e - s))(*numel[s:e]), e - s, lrv,
-                 _p(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), st), "effi_adamw_multi_f32")
+        args = (arr(*pp[s:e]), arr(*pg[s:e]), arr(*pm[s:e]), arr(*pv[s:e]), arr(*ps[s:e]), (C.c_long * (e - s))(*numel[s:e]), e - s, lrv,
+                _p(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay))
+        if clip is None:
+            check(_lib.lib().effi_adamw_multi_f32(*args, st), "effi_adamw_multi_f32")
+        else:
+            check(_lib.lib().effi_adamw_multi_clip_f32(*args, _p(clip), int(bool(skip_nonfinite)), st), "effi_adamw_multi_clip_f32")
 
 
 def depth_metrics(est, gt, mask, thresholds=(), bands=(), acc=None):

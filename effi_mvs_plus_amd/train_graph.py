@@ -139,6 +139,9 @@ class GraphedTrainStep:
         with torch.cuda.graph(self.graph):
             self.loss = self._step()
         self._drop_caches()                                       # nothing outside the graph keeps pointing into its memory pool
+        skipped = getattr(optimizer, "skipped_steps", None)       # FusedAdamW's non-finite guard: warm-up steps do not count
+        if torch.is_tensor(skipped):
+            skipped.zero_()
         self.replays = 0
 
     @staticmethod

@@ -1029,6 +1029,41 @@ int effi_adamw_multi_f32(float* const* p, const float* const* g, float* const* e
                          const long* numel, int n, double lr, const float* lr_dev, double beta1, double beta2, double eps,
                          double weight_decay, effi_stream_t stream);
 
+/* ---- Global gradient norm, clipping and the non-finite guard inside the optimizer step (what torch.nn.utils.clip_grad_norm_ between
+ * backward() and step() does, without rewriting the gradients, plus a step that leaves the weights alone when the norm is not
+ * finite), csrc/optim.hip.  Three calls: partial sums per chunk of 2048 elements, the finish, the clipped step.
+ * effi_gradnorm_max_tensors(): the most gradients one effi_gradnorm_partial_f32 call takes (the table travels in the kernel argument).
+ * effi_gradnorm_chunks(numel, n): HOST-ONLY, any n >= 0: the number of partial slots (doubles) these tensors take, sum of
+ *   ceil(numel[i] / 2048); -1 for n < 0, a null array with n > 0, numel[i] < 0 or more than 2^31 - 1 chunks.
+ * effi_gradnorm_partial_f32: g / numel are HOST arrays of n entries (1 <= n <= effi_gradnorm_max_tensors()), copied into the kernel
+ *   argument as effi_adamw_multi_f32 copies its own: device pointers of numel[i] >= 0 fp32 elements each, any alignment (128-bit loads
+ *   where a tensor is 16-byte aligned).  Writes partial[0 .. effi_gradnorm_chunks(numel, n)) (DEVICE, fp64): slot c = the sum over
+ *   chunk c of (double)g * (double)g -- exact products, double accumulation in a fixed order (per thread, a shuffle tree over the
+ *   wave, the waves through LDS), no atomics: bitwise repeatable.  Every slot is written on every call: the workspace needs no
+ *   zeroing.  A longer list is several calls with partial advanced by the chunks of the calls before.  g is only read.
+ *   EFFI_ERR_BADARG before any launch: n out of range, a null array, a null pointer or numel[i] < 0 among the first n, more than
+ *   2^31 - 1 chunks, a null partial when there is at least one chunk.
+ * effi_gradnorm_finish_f32: one workgroup adds the n_partial doubles in a fixed order (n_partial = 0: partial may be null, the norm is
+ *   0) and writes clip[0..3] (DEVICE, fp32): clip[0] = norm = (float)sqrt(total) (double square root, one rounding),
+ *   clip[1] = coef = min(1, (float)max_norm / (norm + 1e-6f)) in fp32, one rounding per operation (a NaN coefficient stays NaN),
+ *   clip[2] = 1 if norm is finite, else 0, clip[3] = 0.  skipped (optional DEVICE pointer to one int64) += 1 when norm is not finite.
+ *   The double sum cannot overflow; a norm above FLT_MAX becomes inf in clip[0] and counts as non-finite, as an inf or a NaN among
+ *   the gradients does.  max_norm = +inf: never clip (coef = 1 for every finite norm).
+ *   EFFI_ERR_BADARG before any launch: a null clip, n_partial < 0, a null partial with n_partial > 0, max_norm < 0 or NaN.
+ * effi_adamw_multi_clip_f32: effi_adamw_multi_f32 with every gradient element read as g * clip[1] (one fp32 rounding; clip[1] == 1
+ *   leaves g bitwise, so a step that does not clip is effi_adamw_multi_f32's step); g itself is only read.  clip: DEVICE pointer to the
+ *   four floats of effi_gradnorm_finish_f32, read by every workgroup when it runs.  skip_nonfinite != 0: when clip[2] == 0 nothing is
+ *   written at all -- no parameter, no moment, no step counter.
+ *   EFFI_ERR_BADARG before any launch: a null clip, and every case of effi_adamw_multi_f32. */
+int effi_gradnorm_max_tensors(void);
+long effi_gradnorm_chunks(const long* numel, int n);
+int effi_gradnorm_partial_f32(const float* const* g, const long* numel, int n, double* partial, effi_stream_t stream);
+int effi_gradnorm_finish_f32(const double* partial, long n_partial, double max_norm, float* clip, long long* skipped,
+                             effi_stream_t stream);
+int effi_adamw_multi_clip_f32(float* const* p, const float* const* g, float* const* exp_avg, float* const* exp_avg_sq, float* const* step,
+                              const long* numel, int n, double lr, const float* lr_dev, double beta1, double beta2, double eps,
+                              double weight_decay, const float* clip, int skip_nonfinite, effi_stream_t stream);
+
 /* ---- tuning / A-B switches.  A table of named integers, initialised ONCE per process from the environment (variable EFFI_<NAME in
  * upper case>) and changed afterwards only through effi_set_option; no entry point reads the environment.  Names: warp_lds_kb
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """One training step (forward in train mode -> mvs_loss -> backward -> AdamW step, train.py:229-263) at a DTU training shape:
 the HIP training path of this package against torch autograd through the oracle's op sequence with stock PyTorch-ROCm operators
-(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B] [--optimizer torch|fused]
+(MIOpen convolutions, grid_sample) on the same GPU, same weights, same sample.   usage: bench_train.py [H W N B] [--optimizer torch|fused] [--clip-grad-norm X]
 --optimizer fused: the HIP legs step effi_mvs_plus_amd.optim.FusedAdamW (csrc/optim.hip) instead of torch.optim.AdamW (default: torch).
+--clip-grad-norm X (with --optimizer fused): FusedAdamW(max_grad_norm=X), the global-norm clip inside the step.
 Environment: BENCH_TRAIN_NO_GRAPH, BENCH_TRAIN_HIP_ONLY, BENCH_TRAIN_DEPTH_RANGE=static|sample (the graphed step's mode)."""
 import os
 import sys
@@ -48,6 +49,13 @@ def main():
         del argv[i:i + 2]
     if optimizer not in ("torch", "fused"):
         raise SystemExit("--optimizer torch|fused")
+    clip = None
+    if "--clip-grad-norm" in argv:
+        i = argv.index("--clip-grad-norm")
+        clip = float(argv[i + 1])
+        del argv[i:i + 2]
+        if optimizer != "fused":
+            raise SystemExit("--clip-grad-norm needs --optimizer fused (the clip is part of FusedAdamW's step)")
     H, W, N, B = (int(v) for v in (argv[:4] + ["512", "640", "5", "1"][len(argv):]))
     nd = "48,8,8"
     net, sd = build_model(nd, seed=2, device=DEV)
@@ -60,11 +68,11 @@ def main():
     net.train()
     if optimizer == "fused":
         from effi_mvs_plus_amd.optim import FusedAdamW
-        make_opt = lambda capturable: FusedAdamW(net.parameters(), lr=1e-5)                          # noqa: E731
+        make_opt = lambda capturable: FusedAdamW(net.parameters(), lr=1e-5, max_grad_norm=clip)      # noqa: E731
     else:
         make_opt = lambda capturable: torch.optim.AdamW(net.parameters(), lr=1e-5, **({"capturable": True} if capturable else {}))   # noqa: E731
     opt = make_opt(False)
-    print(f"optimizer: {optimizer} ({type(opt).__module__}.{type(opt).__name__})")
+    print(f"optimizer: {optimizer} ({type(opt).__module__}.{type(opt).__name__})" + (f", max_grad_norm={clip}" if clip is not None else ""))
 
     def hip_step():
         opt.zero_grad(set_to_none=True)

@@ -5,7 +5,9 @@ reads every sample's own depth range on the device -> ``train_graph.train_epoch`
 
 usage: finetune_blend.py --trainpath DIR --trainlist FILE --logdir DIR [--loadckpt CKPT] [--ndepths 48,8,8] [--numdepth 384]
                          [--trainviews 3] [--batch_size 4] [--lr 0.001] [--wd 0.001] [--epochs 16] [--num_workers 4]
-                         [--optimizer torch|fused]   (fused: optim.FusedAdamW on csrc/optim.hip; its checkpoints load into torch's AdamW)"""
+                         [--optimizer torch|fused]   (fused: optim.FusedAdamW on csrc/optim.hip; its checkpoints load into torch's AdamW)
+                         [--clip-grad-norm X] [--skip-nonfinite]   (with --optimizer fused: clip the gradients by their global norm, and
+                         leave the weights alone on a step whose gradient norm is not finite; both inside the captured step)"""
 import argparse
 import os
 import sys
@@ -40,7 +42,15 @@ def parse_args(argv=None):
     p.add_argument("--num_workers", type=int, default=4, help=f"DataLoader workers (at most {MAX_WORKERS})")
     p.add_argument("--optimizer", choices=("torch", "fused"), default="torch",
                    help="torch: torch.optim.AdamW(capturable=True); fused: effi_mvs_plus_amd.optim.FusedAdamW (the HIP kernel)")
+    p.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                   help="--optimizer fused: FusedAdamW(max_grad_norm=X), the global-norm clip of clip_grad_norm_ inside the step")
+    p.add_argument("--skip-nonfinite", action="store_true",
+                   help="--optimizer fused: a step whose gradient norm is inf or NaN changes nothing and is counted")
     args = p.parse_args(argv)
+    if args.optimizer != "fused" and (args.clip_grad_norm is not None or args.skip_nonfinite):
+        p.error("--clip-grad-norm and --skip-nonfinite need --optimizer fused: a captured step cannot clip with torch's optimizer")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm >= 0:
+        p.error("--clip-grad-norm must be a number >= 0")
     if not 0 <= args.num_workers <= MAX_WORKERS:
         p.error(f"--num_workers must be in 0..{MAX_WORKERS}")
     if args.batch_size < 1 or args.epochs < 1:
@@ -60,7 +70,8 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.loadckpt, map_location="cpu")["model"])
     model = model.to(dev).train()
     if args.optimizer == "fused":
-        optimizer = train_graph.FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8)
+        optimizer = train_graph.FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8,
+                                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     else:
         optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.wd, eps=1e-8, capturable=True)   # train.py:441-442
     dataset = blend.MVSDataset(args.trainpath, args.trainlist, "finetune", args.trainviews, args.numdepth, device="host")
@@ -82,6 +93,9 @@ def main(argv=None):
                    "{}/model_{:0>6}.ckpt".format(args.logdir, epoch_idx))
         print("Epoch {}/{}, {} steps, lr {:.6f}, mean train loss = {:.3f}".format(epoch_idx, args.epochs, steps,
                                                                                  float(optimizer.param_groups[0]["lr"]), mean_loss))
+        if getattr(optimizer, "skipped_steps", None) is not None:    # (train_epoch has synchronised: these reads wait for nothing)
+            print("  last gradient norm = {:.4g}, steps skipped for a non-finite norm so far = {}".format(
+                float(optimizer.grad_norm), int(optimizer.skipped_steps)))
 
 
 if __name__ == "__main__":
