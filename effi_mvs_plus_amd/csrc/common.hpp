@@ -32,6 +32,7 @@ enum EffiOption {
     EFFI_OPT_ENC_GEN_MR3,        // generated-input pair kernel: 0 = 4 rows per wave where the rule says so (default: 3)
     EFFI_OPT_C3_LEAN,            // 3-D end layers (1 -> 8, 8 -> 1 channels): 0 = the general vector-ALU bodies instead of the dedicated kernels
     EFFI_OPT_DYN_WIN,            // stage-2/3 warp kernel: unset = LDS-window form with its full window, n > 0 = window of n pixels, 0 = window form on global loads, -1 = the gather kernel
+    EFFI_OPT_ROLL_SLIDE,         // row-pair rolling 3-D convolution: 0 = the three-slot body (each plane's fragments read once per output) instead of the sliding-plane one
     EFFI_OPT_COUNT
 };
 constexpr long EFFI_OPT_UNSET = -0x7fffffffL;

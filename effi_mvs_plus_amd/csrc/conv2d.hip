@@ -923,14 +923,29 @@ __device__ __forceinline__ void conv3d_roll_bf16x3_body(const Conv2dArgs a, int 
     }
 }
 
+// the call of a pair launch that workgroup z works on: the second differs in sources, weights, bias and output
+__device__ __forceinline__ Conv2dArgs conv_roll_pair_call(const Conv2dArgs& a, const Conv2dArgs& b) {
+    Conv2dArgs c = a;
+    if (blockIdx.z) {
+#pragma unroll
+        for (int i = 0; i < EFFI_MAX_SRC; ++i) c.src[i] = b.src[i];
+        c.wpack = b.wpack;
+        c.bias = b.bias;
+        c.out0 = b.out0;
+    }
+    return c;
+}
+
 // cout <= 8: the upper half of the 16-row MFMA tile would multiply zero weights.  ROW-PAIR form: rows 0-7 of the tile are the output
 // channels of image row y, rows 8-15 the same channels of row y + 1, and the K index runs over the 4 x 3 window of taps both rows see:
 // K = (dz, dy in 0..3, dx, octet), 36 NOCT items = 9 NOCT K-steps for TWO rows instead of 2 x 7 NOCT (the weights of row y are
 // zero at dy = 3, those of row y + 1 at dy = 0; packing.pack_conv3d_roll_bf16x3 emits this operand when cout <= 8): 36 % fewer
 // MFMAs and A-fragment reads.  The B operand is 9 NOCT x 2 KB, so with 16 input channels the plane slots are stored 20 pixels wide
 // (columns x0 - 2 .. x0 + 17 of the 24 fetched) to keep two workgroups per CU.
+// This is the THREE-SLOT body: planes z - 1, z, z + 1 in LDS, all three read for every output plane.  It is what option
+// roll_slide = 0 launches (kernels conv3d_roll_rp3_bf16x3*): the bitwise cross-check and A/B form of the sliding-plane body below.
 template <int NOCT, int MR>
-__device__ __forceinline__ void conv3d_roll_rp_bf16x3_body(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
+__device__ __forceinline__ void conv3d_roll_rp3_bf16x3_body(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
     static_assert(MR % 2 == 0, "rows go in pairs");
     constexpr int TR = 4 * MR, AR = TR + 2, AW = (NOCT == 2) ? 20 : 24, AQ = 6, XOFF = (NOCT == 2) ? 1 : 3, XLEFT = 4;
     constexpr int CSH = (NOCT == 2) ? 2 : 0;                           // columns dropped on the left of the fetched 24
@@ -1067,29 +1082,208 @@ __device__ __forceinline__ void conv3d_roll_rp_bf16x3_body(const Conv2dArgs a, i
     }
 }
 
+// the three-slot body under kernel names of its own (option roll_slide = 0)
 template <int NOCT, int MR>
-__global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_kernel(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
+__global__ __launch_bounds__(256) void conv3d_roll_rp3_bf16x3_kernel(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
+    conv3d_roll_rp3_bf16x3_body<NOCT, MR>(a, tiles_x, ntiles, zt);
+}
+
+template <int NOCT, int MR>
+__global__ __launch_bounds__(256) void conv3d_roll_rp3_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles, int zt) {
+    conv3d_roll_rp3_bf16x3_body<NOCT, MR>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, zt);
+}
+
+template <int NOCT, int MR>
+__global__ __launch_bounds__(256) void conv3d_roll_rp3_bf16x3_pair_kernel(const Conv2dArgs a, const Conv2dArgs b, int tiles_x, int ntiles,
+                                                                         int zt) {
+    conv3d_roll_rp3_bf16x3_body<NOCT, MR>(conv_roll_pair_call(a, b), tiles_x, ntiles, zt);
+}
+
+// The SLIDING-PLANE form of the row-pair kernel (the default; option roll_slide = 0 selects the three-slot body above, the cross-check
+// and A/B form).  The K order (dz, dy, dx, octet) has 12 NOCT items = NJ = 3 NOCT whole K-steps per dz, and a fragment's offset inside
+// a slot does not depend on dz, so the fragment of plane p at in-dz step j is the SAME data in its three uses (dz = 0 of output p + 1,
+// dz = 1 of output p, dz = 2 of output p - 1).  The body above reads it three times, once per output; here a step reads the NJ x MP
+// fragment pairs of ONE plane once and multiplies them into three accumulator sets with the weight fragments j, NJ + j and 2 NJ + j:
+// a third of the LDS fragment reads, 3 MP independent MFMA chains instead of MP, two plane slots instead of three and one barrier per
+// plane instead of two.  Step t = 0 .. n + 1 of a run [z0, z0 + n), plane p = z0 - 1 + t:
+//   1 stash plane p + 1 (in registers since step t - 1) into slot (t + 1) & 1       2 request plane p + 2
+//   3 read plane p's fragments from slot t & 1, multiply them into the accumulators of outputs t (zeroed here), t - 1 and t - 2
+//   4 store output t - 2 (bias and activation: the epilogue of the body above)       5 barrier
+// Every output receives exactly the MFMAs it receives above, in the same order (dz ascending over three consecutive steps, inside a
+// step j ascending, inside j hi*hi, lo*hi, hi*lo): the result is bitwise the same.  Outputs outside the run get no MFMA: the first two
+// and the last two steps are instantiated without their blocks (MASK), the interior step is branch-free, and a workgroup issues
+// n * 9 NOCT * MP * 3 MFMAs per wave as above.  Planes outside [0, D) come from the zero page.
+// Hazards: slot (t + 1) & 1, written in step t, was last read in step t - 1, and every wave has passed that step's barrier; step t + 1
+// reads it behind step t's barrier; the first slot is written ahead of a barrier of its own.  n and with it the steps and their
+// masks are workgroup-uniform, so every wave meets every barrier.
+// Registers (weights 72 NOCT, plane in flight 32, accumulators 12 MP, fragments 8) are what this form is short of; it keeps the
+// occupancy of the body above (3 waves per SIMD with 8 input channels, 2 with 16: amdgpu_waves_per_eu on the kernels is the guard,
+// the compiler's resource remarks show no scratch) through: the row pairs of a step taken one after the other (one fragment pair in
+// flight), the accumulators renamed at the end of a step instead of three rotated copies of the step (the MFMAs write straight into
+// the renamed registers; rotated copies cost 26-56 spilled registers), and a sched_barrier that keeps the plane request ahead of the
+// multiplies (the scheduler otherwise sinks it behind them to save its 32 registers, and the next stash waits for HBM).
+template <int NOCT, int MR>
+__device__ __forceinline__ void conv3d_roll_rp_bf16x3_body(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
+    static_assert(MR % 2 == 0, "rows go in pairs");
+    constexpr int TR = 4 * MR, AR = TR + 2, AW = (NOCT == 2) ? 20 : 24, AQ = 6, XOFF = (NOCT == 2) ? 1 : 3, XLEFT = 4;
+    constexpr int CSH = (NOCT == 2) ? 2 : 0;                           // columns dropped on the left of the fetched 24
+    constexpr int APIX = AR * AW, NQ = AR * AQ, NITEMS = NQ * NOCT;
+    constexpr int NJ = 3 * NOCT, NKS = 3 * NJ;                         // K-steps per dz, K-steps in all
+    constexpr int SLOT = NOCT * APIX * 8;                              // bf16 elements per plane slot
+    constexpr int MP = MR / 2;
+    static_assert(NITEMS <= 256, "one staging item per thread");
+    __shared__ __attribute__((aligned(16))) unsigned short lds_ah[2 * SLOT];
+    __shared__ __attribute__((aligned(16))) unsigned short lds_al[2 * SLOT];
+
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int h = a.h, w = a.w, D = a.zcount;
+    const long hw = (long)h * w;
+    const int tile = effi_xcd_remap(blockIdx.x, gridDim.x);
+    if (tile >= ntiles) return;
+    const int ty_ = tile / tiles_x;
+    const int x0 = (tile - ty_ * tiles_x) * 16, y0 = ty_ * TR;
+    const int z0 = blockIdx.y * zt, n = min(zt, D - z0);               // the run [z0, z0 + n), n >= 1: workgroup-uniform
+
+    const bool stager = tid < NITEMS;
+    const int pq = stager ? tid % NQ : 0, soct = stager ? tid / NQ : 0;
+    const int srow = pq / AQ, sqx = pq - srow * AQ;
+    const int sgy = y0 - 1 + srow, sgx = x0 - XLEFT + 4 * sqx;
+    const int s_off = (stager & (sgy >= 0) & (sgy < h) & (sgx >= 0) & (sgx < w)) ? sgy * w + sgx : -1;
+    const int s_col = 4 * sqx - CSH;                                   // slot column of the quad's first pixel (may be -2 / 18)
+    const int s_lds = (soct * APIX + srow * AW + s_col) * 8;
+    const float* s_src = (soct * 8 < a.ch[0]) ? a.src[0] + (long)(soct * 8) * a.cstride
+                                              : a.src[1] + (long)(soct * 8 - a.ch[0]) * a.cstride;
+
+    // one plane in flight in registers, requested one step ahead (raw loads; padding comes from the zero page)
+    f32x4 pa[8];
+    auto prefetch = [&](int z) {
+        const bool ok = (s_off >= 0) & (z >= 0) & (z < D);
+        const float* base = ok ? s_src + ((long)z * hw + s_off) : a.zeros;
+        const long step = ok ? a.cstride : 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pa[e] = *reinterpret_cast<const f32x4*>(base + (long)e * step);
+    };
+    auto stash = [&](int slot) {
+        if (stager) {
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                if (CSH && (s_col + px < 0 || s_col + px >= AW)) continue;     // columns outside the 20 kept
+                bf16x8 hi, lo;
+                split_octet(pa, px, hi, lo);
+                *reinterpret_cast<bf16x8*>(&lds_ah[slot * SLOT + s_lds + px * 8]) = hi;
+                if (!kHiOnly) *reinterpret_cast<bf16x8*>(&lds_al[slot * SLOT + s_lds + px * 8]) = lo;
+            }
+        }
+    };
+    bf16x8 breg_h[NKS], breg_l[NKS];                                   // the weight fragments, in registers as above
+    {
+        const unsigned short* wbf = reinterpret_cast<const unsigned short*>(a.wpack);
+#pragma unroll
+        for (int s_ = 0; s_ < NKS; ++s_) {
+            breg_h[s_] = *reinterpret_cast<const bf16x8*>(wbf + ((long)(s_ * 2 + 0) * 64 + lane) * 8);
+            if (!kHiOnly) breg_l[s_] = *reinterpret_cast<const bf16x8*>(wbf + ((long)(s_ * 2 + 1) * 64 + lane) * 8);
+        }
+    }
+    // item 4 j + lk = (dy, dx, oct) of in-dz step j: the lane's element offset inside a slot (kconst[dz * NJ + j] >> 2 above, any dz)
+    int koff[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int item = 4 * j + lk;
+        const int oct = item % NOCT, rem = item / NOCT;
+        koff[j] = ((wv * MR) * AW + li + XOFF + oct * APIX + (rem / 3) * AW + rem % 3) * 8;
+    }
+    const f32x4 rbias = *reinterpret_cast<const f32x4*>(a.bias + 4 * (lk & 1));   // once per workgroup, not per plane
+    const int x = x0 + li;
+
+    // an / am / ao: the accumulators of outputs t, t - 1, t - 2 in step t.  MASK bit k: output t - k lies in the run, its dz = k block
+    // is multiplied.  Bit 0 also says that plane p + 2 is still wanted, bits 0 | 1 that plane p + 1 is; 4 alone is the last step.
+    f32x4 an[MP], am[MP], ao[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) am[m] = ao[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    auto step = [&](auto mask_t, int t) {
+        constexpr int MASK = decltype(mask_t)::value;
+        const int p = z0 - 1 + t;
+        if (MASK & 3) stash((t + 1) & 1);
+        if (MASK & 1) prefetch(p + 2);
+        __builtin_amdgcn_sched_barrier(0);                             // the request stays ahead of the multiplies
+        const int sb = (t & 1) * SLOT;
+#pragma unroll
+        for (int m = 0; m < MP; ++m) an[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                const bf16x8 ah = *reinterpret_cast<const bf16x8*>(&lds_ah[koff[j] + sb + m * 2 * AW * 8]);
+                bf16x8 al = ah;
+                if (!kHiOnly) al = *reinterpret_cast<const bf16x8*>(&lds_al[koff[j] + sb + m * 2 * AW * 8]);
+                // hi*hi of the three outputs, then lo*hi, then hi*lo: per output the order of the body above, and two independent
+                // MFMAs between dependent ones
+#pragma unroll
+                for (int pass = 0; pass < (kHiOnly ? 1 : 3); ++pass) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        if (!(MASK >> k & 1)) continue;
+                        f32x4& acc = k == 0 ? an[m] : (k == 1 ? am[m] : ao[m]);
+                        // weights x pixels: D[cout][pixel] (transposed fragment, see conv_epilogue_store_t)
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pass == 1 ? breg_l[k * NJ + j] : breg_h[k * NJ + j], pass == 2 ? al : ah,
+                                                                      acc, 0, 0, 0);
+                    }
+                }
+            }
+        }
+        if (MASK & 4) {
+            // lane (li, lk): lk < 2 -> row y, channels 4 lk ..; lk >= 2 -> row y + 1, channels 4 (lk - 2) ..
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                const int y = y0 + wv * MR + 2 * m + (lk >> 1);
+                if (y >= h || x >= w) continue;
+                conv_epilogue_store_t<EFFI_EPI_PLAIN>(a, ao[m], 4 * (lk & 1), (long)y * w + x, hw, p - 1, 0, 0, &rbias);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MP; ++m) ao[m] = am[m], am[m] = an[m];
+        if (MASK != 4) __syncthreads();
+    };
+    using M1 = std::integral_constant<int, 1>;
+    using M2 = std::integral_constant<int, 2>;
+    using M3 = std::integral_constant<int, 3>;
+    using M4 = std::integral_constant<int, 4>;
+    using M6 = std::integral_constant<int, 6>;
+    using M7 = std::integral_constant<int, 7>;
+
+    prefetch(z0 - 1);
+    stash(0);
+    prefetch(z0);
+    __syncthreads();
+    step(M1{}, 0);
+    if (n > 1) step(M3{}, 1);
+    else step(M2{}, 1);
+    for (int t = 2; t < n; ++t) step(M7{}, t);
+    if (n > 1) step(M6{}, n);
+    step(M4{}, n + 1);
+}
+
+// (amdgpu_waves_per_eu: the occupancy of the three-slot kernels, which the sliding body must not fall below -- 3 waves per SIMD with 8
+// input channels and 2 with 16.  Plain bf16 operands halve the weight fragments and give the three-slot kernels one wave more; the
+// sliding body follows with 2 rows per wave, and with 4 it would spill 2-8 registers there, so it stays a wave below: DESIGN App. B)
+#define EFFI_ROLL_RP_WAVES __attribute__((amdgpu_waves_per_eu((NOCT == 1 ? 3 : 2) + (kHiOnly && MR == 2 ? 1 : 0))))
+template <int NOCT, int MR>
+__global__ __launch_bounds__(256) EFFI_ROLL_RP_WAVES void conv3d_roll_rp_bf16x3_kernel(const Conv2dArgs a, int tiles_x, int ntiles, int zt) {
     conv3d_roll_rp_bf16x3_body<NOCT, MR>(a, tiles_x, ntiles, zt);
 }
 
 // n_smp samples in one launch: blockIdx.z = sample (ConvBatch, conv2d_x3.hpp)
 template <int NOCT, int MR>
-__global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x, int ntiles, int zt) {
+__global__ __launch_bounds__(256) EFFI_ROLL_RP_WAVES void conv3d_roll_rp_bf16x3_batch_kernel(const Conv2dArgs a, const ConvBatch b, int tiles_x,
+                                                                                              int ntiles, int zt) {
     conv3d_roll_rp_bf16x3_body<NOCT, MR>(conv_batch_image(a, b, blockIdx.z), tiles_x, ntiles, zt);
 }
 
 template <int NOCT, int MR>
-__global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_pair_kernel(const Conv2dArgs a, const Conv2dArgs b, int tiles_x, int ntiles,
-                                                                         int zt) {
-    Conv2dArgs c = a;
-    if (blockIdx.z) {
-#pragma unroll
-        for (int i = 0; i < EFFI_MAX_SRC; ++i) c.src[i] = b.src[i];
-        c.wpack = b.wpack;
-        c.bias = b.bias;
-        c.out0 = b.out0;
-    }
-    conv3d_roll_rp_bf16x3_body<NOCT, MR>(c, tiles_x, ntiles, zt);
+__global__ __launch_bounds__(256) EFFI_ROLL_RP_WAVES void conv3d_roll_rp_bf16x3_pair_kernel(const Conv2dArgs a, const Conv2dArgs b, int tiles_x,
+                                                                                             int ntiles, int zt) {
+    conv3d_roll_rp_bf16x3_body<NOCT, MR>(conv_roll_pair_call(a, b), tiles_x, ntiles, zt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1103,7 +1297,7 @@ __global__ __launch_bounds__(256) void conv3d_roll_rp_bf16x3_pair_kernel(const C
 //   * generation: 200 work items = (row, pixel pair, octet) of the 10 x 20 slot region; per item the 27 taps in the order of
 //     conv3d_c1to8_kernel ((ky, kx) outer, kd inner, fmaf), + bias, relu, zero outside the map / the volume (conv1's padding), then
 //     the (hi, lo) split of the staging code above: the slot contents are BITWISE those of the three-launch path, and so is conv1;
-//   * the matrix part (K order, weight fragments in registers, epilogue) is that of conv3d_roll_rp_bf16x3_body<2, 2>.
+//   * the matrix part (K order, weight fragments in registers, three plane slots, epilogue) is that of conv3d_roll_rp3_bf16x3_body<2, 2>.
 // blockIdx.z picks the block (CSP_R[s] / CSP_C[s] share x).
 // ------------------------------------------------------------------------------------------------
 struct CspGenCall {
@@ -2696,7 +2890,8 @@ template <int NOCT, int NT>
 static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pair = nullptr, const ConvBatch* bt = nullptr) {
     // rows per wave (MR), planes per workgroup (ZT) and the row-pair operand: the rounds model of launch_form.hpp (effi_pick_roll)
     const int cols = effi_cdiv(a.w, 16), D = a.zcount;
-    const EffiForm f = effi_pick_roll(NOCT, NT, a.cout, a.h, a.w, D, pair ? 2 : (bt ? bt->n_img : 1), effi_form_opts());
+    const EffiFormOpts o = effi_form_opts();
+    const EffiForm f = effi_pick_roll(NOCT, NT, a.cout, a.h, a.w, D, pair ? 2 : (bt ? bt->n_img : 1), o);
     const int mr = f.rows, zt = f.planes;
     const bool rp = f.variant != 0;
     const long tiles = (long)cols * effi_cdiv(a.h, 4 * mr);
@@ -2706,6 +2901,12 @@ static int launch_roll(const Conv2dArgs& a, hipStream_t st, const Conv2dArgs* pa
     return effi_switch<2, 4>(mr, [&](auto MR) {
         constexpr int m = MR();
         const int ntiles = (int)tiles;
+        // (option roll_slide = 0: the three-slot body of the row-pair kernels, same grid and arguments, bitwise the same result)
+        if (rp && o.roll_slide == 0) {
+            if (bt) return effi_launch<conv3d_roll_rp3_bf16x3_batch_kernel<NOCT, m>>(grid, 256, st, a, *bt, cols, ntiles, zt);
+            if (pair) return effi_launch<conv3d_roll_rp3_bf16x3_pair_kernel<NOCT, m>>(grid, 256, st, a, *pair, cols, ntiles, zt);
+            return effi_launch<conv3d_roll_rp3_bf16x3_kernel<NOCT, m>>(grid, 256, st, a, cols, ntiles, zt);
+        }
         if (bt) return rp ? effi_launch<conv3d_roll_rp_bf16x3_batch_kernel<NOCT, m>>(grid, 256, st, a, *bt, cols, ntiles, zt)
                           : effi_launch<conv3d_roll_bf16x3_batch_kernel<NOCT, NT, m>>(grid, 256, st, a, *bt, cols, ntiles, zt);
         if (pair) return rp ? effi_launch<conv3d_roll_rp_bf16x3_pair_kernel<NOCT, m>>(grid, 256, st, a, *pair, cols, ntiles, zt)

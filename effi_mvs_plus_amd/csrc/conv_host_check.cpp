@@ -490,6 +490,25 @@ static void cases_x3() {
             Opt o3(EFFI_OPT_ROLL_RP, 0);
             roll(L("roll_mr%d roll_zt%d roll_rp0 cout8", mr, zt), C8, 1, 8, 8, 32, 32);
         }
+    // option roll_slide = 0 (not in the golden): the three-slot kernels under their own names, and nothing else of a record changes
+    for (int cin : {8, 16})
+        for (int entry = 0; entry < 3; ++entry) {
+            std::string rec[2];
+            for (int slide = 1; slide >= 0; --slide) {
+                Opt o(EFFI_OPT_ROLL_SLIDE, slide ? EFFI_OPT_UNSET : 0);
+                const int* ch = cin == 8 ? C8 : C16;
+                g_rec.clear();
+                const int rc = entry == 0   ? EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_f32)(S, ch, 1, W, B, 8, 8, 32, 32, 1, O0, nullptr)
+                               : entry == 1 ? EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_f32_batch)(S, ch, 1, W, B, 8, 8, 32, 32, 1, O0, 2, SS, 5000L, nullptr)
+                                            : EFFI_FN(effi_conv3d_k3s1_roll_bf16x3_pair_f32)(S, W, B, O0, S2, W2, B2, O1, ch, 1, 8, 8, 32, 32, 1, nullptr);
+                rec[slide] = rc == EFFI_OK ? g_rec : std::string("?");
+            }
+            const size_t at = rec[0].find("conv3d_roll_rp3_bf16x3_");
+            if (at == std::string::npos || rec[1].find("conv3d_roll_rp_bf16x3_") != at || std::string(rec[0]).erase(at + 14, 1) != rec[1]) {
+                std::printf("FAILED: roll_slide=0, cin %d, entry %d:%s\n   against%s\n", cin, entry, rec[0].c_str(), rec[1].c_str());
+                ++g_failures;
+            }
+        }
     roll("n_src3", C8, 3, 8, 8, 32, 32);
     roll("cin 4", ch4 + 1, 1, 8, 8, 32, 32, false);
     roll("w 18", C8, 1, 8, 8, 32, 18, false);

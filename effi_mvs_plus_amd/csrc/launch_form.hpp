@@ -15,6 +15,7 @@ struct EffiFormOpts {           // the options a rule reads, defaults of the thr
     long mr4_min, mr4_nt2_max, mr2_min;
     long wide_tiles;            // -1 = the rule
     long sr_waves, roll_mr, roll_zt, roll_rp, deconv_mr;        // EFFI_OPT_UNSET = the rule
+    long roll_slide;            // 0 = the three-slot body of the row-pair rolling kernel (same tile form, kernels of their own)
 };
 
 static inline long effi_opt_or(int id, long dflt) {
@@ -34,6 +35,7 @@ static inline EffiFormOpts effi_form_opts() {
     o.roll_zt = effi_option(EFFI_OPT_ROLL_ZT);
     o.roll_rp = effi_option(EFFI_OPT_ROLL_RP);
     o.deconv_mr = effi_option(EFFI_OPT_DECONV_MR);
+    o.roll_slide = effi_opt_or(EFFI_OPT_ROLL_SLIDE, 1);
     return o;
 }
 

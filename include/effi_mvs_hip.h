@@ -1069,7 +1069,8 @@ int effi_adamw_multi_clip_f32(float* const* p, const float* const* g, float* con
  * (stage-1 warp kernel: LDS window in KB; 0 = the window kernel on global loads, -1 = the direct-gather kernel), dyn_form (1 =
  * channel-split lanes in the stage-2/3 warp kernel), dyn_setup_exact (1 = IEEE divisions there), pixnet_mfma (0 = vector-ALU
  * view-weight net), force_mr / mr4_min / mr4_nt2_max / mr2_min / wide_tiles (tile rule of the split-precision 3x3 convolutions),
- * roll_mr / roll_zt / roll_rp / deconv_mr (tile rules of the 3-D convolutions), dyn_xchg (diagnostic builds only).
+ * roll_mr / roll_zt / roll_rp / deconv_mr (tile rules of the 3-D convolutions), roll_slide (0 = the three-slot body of the row-pair
+ * rolling 3-D convolution instead of the sliding-plane one; bitwise the same result), dyn_xchg (diagnostic builds only).
  * effi_set_option returns EFFI_ERR_BADARG for an unknown name; effi_get_option returns effi_option_unset() for an unknown or unset one;
  * effi_set_option(name, effi_option_unset()) restores "unset" (the built-in rule). */
 int effi_set_option(const char* name, long value);
