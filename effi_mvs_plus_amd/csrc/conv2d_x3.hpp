@@ -1127,27 +1127,7 @@ __global__ __launch_bounds__(256) void conv2d_k3_bf16x3_encgen_pair_kernel(const
 // An entry is: validation, the argument filler, the fields it deliberately overrides, the dispatch.  A dispatch turns its runtime
 // choices (N-tile count, rows per wave, wide / aligned / half forms) into template arguments with effi_switch and launches with
 // effi_launch; a launcher takes the image / sample batch as ``const ConvBatch* bt`` (nullptr: the single-image kernel) and refuses
-// with EFFI_ERR_UNSUPPORTED what has no batched kernel.
-
-// f(std::integral_constant<int, V>) for the V of Vs... that equals v; ``miss`` when there is none
-template <int... Vs, class F>
-static int effi_switch_or(int miss, long v, F&& f) {
-    int rc = miss;
-    (void)(... || (v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false));
-    return rc;
-}
-// rows per wave, tile forms and flags: a value outside the set is a bad argument (of an option, as a rule)
-template <int... Vs, class F>
-static int effi_switch(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_BADARG, v, f); }
-// N-tile counts (and other sizes a kernel is instantiated for): a layer outside the set is unsupported
-template <int... Vs, class F>
-static int effi_switch_nt(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_UNSUPPORTED, v, f); }
-
-template <auto KERNEL, class... Args>
-static int effi_launch(dim3 grid, int threads, hipStream_t st, const Args&... args) {
-    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, st, args...);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
+// with EFFI_ERR_UNSUPPORTED what has no batched kernel.  (effi_switch* and effi_launch: launch_form.hpp, shared with warpcorr.hip.)
 
 // The argument filler: ``Conv2dArgs a{}`` (every field zero / null), then one setter each for the source list, the geometry and the
 // weights; outputs, auxiliaries and whatever an entry reuses for a meaning of its own are assigned by the entry.

@@ -10,140 +10,49 @@
 // unset prints as 0xAA.. and not, by luck, as zero.  The made-up device addresses are copied into the arguments and never read
 // through.  Referring to the kernels makes the host object want the device image's symbol; the Makefile links with
 // --unresolved-symbols=ignore-all, and nothing registers or launches a kernel.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cxxabi.h>
-#include <string>
-#include <type_traits>
-#include <typeinfo>
-
-static std::string g_rec;                      // the launches of the case that runs
-static void put(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_rec += buf;
-}
-static std::string L(const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return buf;
-}
-
-template <auto K> struct kernel_tag {};
-template <class T> static void show(const T& v);
-template <auto K, class... A>
-static void rec_launch(dim3 grid, dim3 block, size_t shmem, const A&... args) {
-    int status = 0;
-    char* name = abi::__cxa_demangle(typeid(kernel_tag<K>).name(), nullptr, nullptr, &status);
-    std::string k = name ? name : "?";                          // "kernel_tag<&(anonymous namespace)::f<...>>" -> "f<...>"
-    std::free(name);
-    if (const size_t amp = k.find('&'); amp != std::string::npos) k = k.substr(amp + 1, k.size() - amp - 2);
-    for (size_t at; (at = k.find("(anonymous namespace)::")) != std::string::npos;) k.erase(at, 23);
-    if (k.rfind("(void ", 0) == 0) k.erase(0, 6);               // "(void f<...>(Args...))" -> "f<...>"
-    const size_t gt = k.rfind('>');
-    if (const size_t par = k.find('(', gt == std::string::npos ? 0 : gt); par != std::string::npos) k.erase(par);
-    put(" || %s grid %u,%u,%u block %u shmem %zu", k.c_str(), grid.x, grid.y, grid.z, block.x, shmem);
-    ((put(" |"), show(args)), ...);
-}
-
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) rec_launch<(kernel)>(dim3(grid), dim3(block), (shmem), __VA_ARGS__)
-#define hipPeekAtLastError() hipSuccess
-#define hipGetLastError() hipSuccess
+#include "host_check_record.hpp"           // the recorder: the launch macro is redefined from here on
 #include "conv2d.hip"
 #include "conv2d_sr.hip"
 
-// ---- what api.hip gives the library: the zero page and the option table ----------------------------------------------------------
-static const uintptr_t kBase = 0x100000000UL;                   // fake device addresses: kBase + k * 0x100
-template <class T = float> static T* P(int k) { return reinterpret_cast<T*>(kBase + 0x100UL * (unsigned)k); }
-static bool g_have_zero_page = true;
-const float* effi_zero_page() { return g_have_zero_page ? P(99) : nullptr; }
-static long g_opt[EFFI_OPT_COUNT];
-long effi_option(int id) { return g_opt[id]; }
-struct Opt {                                                    // an option for the length of a scope
-    int id;
-    Opt(int i, long v) : id(i) { g_opt[i] = v; }
-    ~Opt() { g_opt[id] = EFFI_OPT_UNSET; }
-};
-
-// ---- printing ---------------------------------------------------------------------------------------------------------------------
-// A struct's fields that are 0 / null are left out of its line (an unset one is 0xAA.. under the pattern initialisation and shows).
-static void ptr(const char* n, const void* p) {
-    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
-    if (!p) return;
-    if (v >= kBase && v < kBase + (1UL << 32)) put(" %s=@%lx", n, (unsigned long)(v - kBase));
-    else put(" %s=0x%lx", n, (unsigned long)v);
-}
-#define FI(s, f) ((s).f != 0 ? put(" " #f "=%ld", (long)(s).f) : (void)0)
-#define FP(s, f) ptr(#f, (s).f)
-static void show_one(const Conv2dArgs& a) {
+namespace {                                 // (beside the structs: the recorder's show finds these by argument-dependent lookup)
+void show_one(const Conv2dArgs& a) {
     for (int i = 0; i < EFFI_MAX_SRC; ++i) ptr(L("src%d", i).c_str(), a.src[i]);
     for (int i = 0; i < EFFI_MAX_SRC; ++i) if (a.ch[i]) put(" ch%d=%d", i, a.ch[i]);
     FI(a, cin), FI(a, kgroups), FP(a, wpack), FP(a, bias), FI(a, cout), FI(a, h), FI(a, w), FI(a, act), FI(a, hd), FP(a, aux0), FP(a, aux1);
     FP(a, disp_range), FI(a, n_range), FP(a, out0), FP(a, out1), FI(a, cstride), FI(a, ostride), FI(a, zcount), FI(a, zin), FI(a, hin);
     FI(a, win), FP(a, zeros), FP(a, xptr0), FI(a, sr_hp), FI(a, sr_wp), FP(a, out_sr), FI(a, aux_q4);
 }
-static void show_one(const ConvBatch& b) {
+void show_one(const ConvBatch& b) {
     FI(b, n_img);
     for (int i = 0; i < EFFI_MAX_SRC; ++i) if (b.src[i]) put(" src%d=%ld", i, b.src[i]);
     FI(b, aux0), FI(b, out0);
 }
-static void show_one(const EncGenArgs& g) {
+void show_one(const EncGenArgs& g) {
     FP(g, inv_depth), FP(g, disp_range), FI(g, n_range), FP(g, interval), FP(g, cur_vol), FI(g, cds), FI(g, cps), FI(g, Dcur), FP(g, reg_vol);
     FI(g, rds), FI(g, rps), FI(g, Dreg), FP(g, dmin), FP(g, dmax), FI(g, range_ps), FP(g, w_c1), FP(g, b_c1), FP(g, w_d1), FP(g, b_d1), FI(g, hd);
     FI(g, off32);
 }
-static void show_one(const DeconvArgs& a) {
+void show_one(const DeconvArgs& a) {
     FP(a, in), FP(a, wpack), FP(a, bias), FP(a, skip), FP(a, zeros), FP(a, out), FI(a, cin), FI(a, cout), FI(a, D), FI(a, h), FI(a, w), FI(a, relu);
 }
-static void show_one(const ConvTwiceArgs& a) {
+void show_one(const ConvTwiceArgs& a) {
     FP(a, src), FI(a, cin), FP(a, w_a), FP(a, bias_a), FP(a, w_b), FP(a, bias_b), FI(a, cout), FI(a, h), FI(a, w), FP(a, out), FP(a, zeros);
 }
-static void show_one(const EncTailArgs& a) {
+void show_one(const EncTailArgs& a) {
     FP(a, src_a), FP(a, src_b), FP(a, w_a), FP(a, bias_a), FP(a, w_b), FP(a, bias_b), FP(a, w_d), FP(a, bias_d), FP(a, extra), FI(a, c_extra);
     FP(a, w2), FP(a, bias2), FI(a, cout2), FI(a, h), FI(a, w), FP(a, out), FP(a, zeros);
 }
-static void show_one(const CspGenCall& c) { FP(c, prior), FP(c, w0), FP(c, b0), FP(c, wc), FP(c, bc), FP(c, w1), FP(c, b1), FP(c, out); }
-static void show_one(const GruFusedArgs& g) {
+void show_one(const CspGenCall& c) { FP(c, prior), FP(c, w0), FP(c, b0), FP(c, wc), FP(c, bc), FP(c, w1), FP(c, b1), FP(c, out); }
+void show_one(const GruFusedArgs& g) {
     FP(g, H_in), FP(g, X), FP(g, h_in), FP(g, wzr), FP(g, bzr), FP(g, wq), FP(g, bq), FP(g, h_out), FP(g, H_out), FI(g, h), FI(g, w), FI(g, hp);
     FI(g, wp);
 }
-template <class T> static void show(const T& v) {
-    if constexpr (std::is_pointer_v<T>) v ? ptr("ptr", v) : put(" null");
-    else if constexpr (std::is_integral_v<T>) put(" %ld", (long)v);
-    else show_one(v);
-}
+}  // namespace
 
-static int g_failures = 0;
-static const char* rc_name(int rc) {
-    switch (rc) {
-        case EFFI_OK: return "OK";
-        case EFFI_ERR_BADARG: return "BADARG";
-        case EFFI_ERR_UNSUPPORTED: return "UNSUPPORTED";
-        case EFFI_ERR_WORKSPACE: return "WORKSPACE";
-        case EFFI_ERR_LAUNCH: return "LAUNCH";
-        default: return "?";
-    }
-}
-static void emit(const char* entry, const std::string& label, int rc) {
-    if (rc != EFFI_OK && !g_rec.empty()) { std::printf("FAILED: %s | %s launched and returned %s\n", entry, label.c_str(), rc_name(rc)); ++g_failures; }
-    if (rc == EFFI_OK && g_rec.empty()) { std::printf("FAILED: %s | %s returned OK without a launch\n", entry, label.c_str()); ++g_failures; }
-    std::printf("%s | %s | %s%s\n", entry, label.c_str(), rc_name(rc), g_rec.c_str());
-}
 #define XSTR2(x) #x
 #define XSTR(x) XSTR2(x)
-// RUN: an entry compiled in both precisions (EFFI_FN appends _bf16 in the second); RUNF: an fp32-only entry
+// RUN: an entry compiled in both precisions (EFFI_FN appends _bf16 in the second); the recorder's RUNF: an fp32-only entry
 #define RUN(fn, label, ...) do { g_rec.clear(); const int rc_ = EFFI_FN(fn)(__VA_ARGS__); emit(XSTR(EFFI_FN(fn)), (label), rc_); } while (0)
-#define RUNF(fn, label, ...) do { g_rec.clear(); const int rc_ = fn(__VA_ARGS__); emit(#fn, (label), rc_); } while (0)
 // the one behaviour this layer changed: rows per wave outside a launcher's set are refused by every launcher (not in the golden)
 #define EXPECT_BADARG(fn, ...)                                                                                          \
     do {                                                                                                                \

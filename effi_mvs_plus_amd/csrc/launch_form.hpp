@@ -2,8 +2,33 @@
 // of the tuning options go in, the tile form comes out.  Every launcher calls the pick function of its rule and launches what it
 // returns; effi_launch_form (api.hip) calls the same functions without launching anything, so that a test can assert the form a case
 // is written for (tests/conv_cases.py: FORMS) and sweep the forms the workloads take.  There is no second copy of a rule.
+// The rules of the warp and correlation kernels (warpcorr.hip) are at the end: which kernel a stage-1 ("views") call and a call of
+// the dynamic stage take, with the size of their LDS window; csrc/warp_host_check.cpp pins them through the entries.
+// In front of the rules, the two helpers every launcher dispatches with: effi_switch (a run-time value as a template argument) and
+// effi_launch.
 #pragma once
 #include "common.hpp"
+#include <type_traits>
+
+// f(std::integral_constant<int, V>) for the V of Vs... that equals v; ``miss`` when there is none
+template <int... Vs, class F>
+static int effi_switch_or(int miss, long v, F&& f) {
+    int rc = miss;
+    (void)(... || (v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false));
+    return rc;
+}
+// rows per wave, tile forms and flags: a value outside the set is a bad argument (of an option, as a rule)
+template <int... Vs, class F>
+static int effi_switch(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_BADARG, v, f); }
+// N-tile and channel counts (and other sizes a kernel is instantiated for): a layer outside the set is unsupported
+template <int... Vs, class F>
+static int effi_switch_nt(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_UNSUPPORTED, v, f); }
+
+template <auto KERNEL, class... Args>
+static int effi_launch(dim3 grid, int threads, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, st, args...);
+    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
 
 #ifndef EFFI_C3_TX
 #define EFFI_C3_TX 32          // tile of the vector-ALU 3-D kernels (A/B builds: -DEFFI_C3_TX=64 -DEFFI_C3_TY=4)
@@ -182,4 +207,66 @@ static inline EffiForm effi_pick_c3_planes(int h, int w, int D, long ncall) {
 static inline EffiForm effi_pick_deconv_k3(int cout, int h, int w, int D, long n_smp) {
     const int tiles = effi_cdiv(w, EFFI_C3_TX) * effi_cdiv(h, EFFI_C3_TY);
     return EffiForm{1, EFFI_C3_TX, 4, (long)tiles * D * (cout / 8) * n_smp >= 512 ? 8 : 4, 0};
+}
+
+// ---- warp and correlation kernels (warpcorr.hip) ------------------------------------------------------------------------------------
+struct EffiWarpOpts {           // the options the two rules below read, as set (EFFI_OPT_UNSET = the rule)
+    long warp_lds_kb, dyn_form, dyn_setup_exact, dyn_win;
+};
+static inline EffiWarpOpts effi_warp_opts() {
+    return EffiWarpOpts{effi_option(EFFI_OPT_WARP_LDS_KB), effi_option(EFFI_OPT_DYN_FORM), effi_option(EFFI_OPT_DYN_SETUP_EXACT),
+                        effi_option(EFFI_OPT_DYN_WIN)};
+}
+
+// Window capacity of the stage-1 LDS kernels in pixels (128 B each): 72 KB leaves room for two 512-thread workgroups per CU.
+constexpr int EFFI_WIN_MAXPX = 576;
+
+// Option warp_lds_kb (effi_set_option; tests and A/B runs only): unset = the windowed kernel with its full 72 KB window;
+// 0 = the windowed kernel with every chunk sampled from global memory (same arithmetic, the bitwise cross-check);
+// -1 = the direct-gather kernel (also what C != 32 and per-pixel hypotheses use).
+static inline int effi_warp_lds_px(const EffiWarpOpts& o) {
+    if (o.warp_lds_kb == EFFI_OPT_UNSET) return EFFI_WIN_MAXPX;
+    if (o.warp_lds_kb < 0) return -1;
+    const long px = o.warp_lds_kb * 1024 / 128;
+    return px < EFFI_WIN_MAXPX ? (int)px : EFFI_WIN_MAXPX;
+}
+
+enum EffiViewsKernel { EFFI_VIEWS_GATHER, EFFI_VIEWS_WINDOW, EFFI_VIEWS_MM };
+struct EffiViewsForm {
+    EffiViewsKernel kernel;
+    int lds_px;                 // window kernels: pixels of the LDS window (0 = every chunk from global memory)
+};
+// Stage 1 (the views family, forward and backward; x3: the split-precision forward entries).  Hypotheses shared by all pixels
+// (C = 32, no per-pixel depth stride, D <= 256 -- the cascade's stage 1) serve their taps from an LDS window, and the
+// split-precision entries run them on the matrix cores (coordinates below 32000; option warp_lds_kb does not reach that kernel);
+// everything else takes the direct-gather kernels, which exist for C = 32 / 16 / 8.
+static inline EffiViewsForm effi_pick_views(bool x3, int C, long dps, int D, int h, int w, const EffiWarpOpts& o) {
+    const bool shared = C == 32 && dps == 0 && D <= 256;
+    if (x3 && shared && h < 32000 && w < 32000) return EffiViewsForm{EFFI_VIEWS_MM, 0};
+    const int lds_px = effi_warp_lds_px(o);
+    if (shared && lds_px >= 0) return EffiViewsForm{EFFI_VIEWS_WINDOW, lds_px};
+    return EffiViewsForm{EFFI_VIEWS_GATHER, 0};
+}
+
+enum EffiDynKernel { EFFI_DYN_EXACT, EFFI_DYN_SPLIT, EFFI_DYN_HYP, EFFI_DYN_WINDOW };
+struct EffiDynForm {
+    EffiDynKernel kernel;
+    int lds_px;                 // window kernel: at most this many pixels per window (0 = every view from global memory)
+};
+// The dynamic stage (stages 2 / 3), forward.
+// EXACT: the channel-split kernel with the reference's IEEE divisions op for op -- option dyn_setup_exact = 1 (A/B runs, tests), or a
+//   map too large for the 32-bit byte offsets of every other form.
+// SPLIT: the channel-split (exchange-free) kernel with the "fast" set-up arithmetic (see the kernel) -- C = 32, or option dyn_form = 1.
+// HYP: the hypothesis-per-lane kernel, the default for C = 8 / 16 (91 vs 107 us at 592x800, 60 vs 75 us at 296x400 against SPLIT).
+// WINDOW: its LDS-window form (warpcorr_dyn_win_kernel), D <= 8 (a lane holds the set-ups of its 4 / 2 hypotheses for two views)
+//   and coordinates below 32000; option dyn_win: -1 = HYP instead, 0 = the window kernel with every view sampled from global memory,
+//   n > 0 = windows of at most n pixels (tests: most boxes then overflow and mix with LDS-served views).
+// (An 8-channels-per-lane form -- one lane per pixel at C = 8, no exchange, no reduction, cheaper projection -- was built and
+// measured at 592x800: 121 us against 109 us; at 296x400, C = 16: 63 against 58.  These kernels are bound by the number of distinct
+// cache lines a wave-instruction touches in the L1 / texture path, not by instruction issue.)
+static inline EffiDynForm effi_pick_dyn(int C, int S, int D, int h, int w, const EffiWarpOpts& o) {
+    if (o.dyn_setup_exact == 1 || (long)h * w * C * 4 >= (1L << 31)) return EffiDynForm{EFFI_DYN_EXACT, 0};
+    if (o.dyn_form == 1 || (C != 8 && C != 16)) return EffiDynForm{EFFI_DYN_SPLIT, 0};
+    if (o.dyn_win == -1 || D > 8 || S > EFFI_MAX_VIEWS || h >= 32000 || w >= 32000) return EffiDynForm{EFFI_DYN_HYP, 0};
+    return EffiDynForm{EFFI_DYN_WINDOW, o.dyn_win == EFFI_OPT_UNSET ? (1 << 20) : (int)(o.dyn_win > 0 ? o.dyn_win : 0)};
 }

@@ -14,6 +14,7 @@
 // projection with a refined reciprocal + one residual step (project_xy below: correctly rounded except for rare 1-ulp cases of
 // a continuous function); the exact-division forms stay selectable (EFFI_WARP_LDS_KB=-1, EFFI_DYN_SETUP=exact).
 #include "common.hpp"
+#include "launch_form.hpp"          // (the launch rules of these kernels: effi_pick_views, effi_pick_dyn)
 #include <cstdlib>
 
 namespace {
@@ -1729,183 +1730,224 @@ __global__ __launch_bounds__(256) void warpcorr_dyn_bwd_kernel(const float* __re
     *reinterpret_cast<float4*>(grad_ref + (long)pix * C + sub4) = gr;
 }
 
+// ---- the host layer ------------------------------------------------------------------------------------------------------------------
+// An entry is: its family's call struct, filled by the one function that validates the family, and the family's launcher.  Which
+// kernel a call takes is a rule of launch_form.hpp (effi_pick_views, effi_pick_dyn); csrc/warp_host_check.cpp records every launch.
+
 template <int C> int grid_blocks(int h, int w) {
     using G = WarpGeom<C>;
     return ((w + G::TW - 1) / G::TW) * ((h + G::TH - 1) / G::TH);
 }
+int win_tiles(int h, int w) { return effi_cdiv(w, WIN_TW) * effi_cdiv(h, WIN_TH); }     // stage-1 window kernels
+int mm_tiles(int h, int w) { return effi_cdiv(w, 16) * effi_cdiv(h, 4); }               // stage-1 matrix-core kernels
 
-bool fill_views(const float* const* src, int S, EffiPtrList& l) {
-    l.tbl = nullptr;
-    if (!src || S < 1 || S > EFFI_MAX_VIEWS) return false;
+// the channel count as a template argument: f(std::integral_constant<int, C>) for C = 32 / 16 / 8, EFFI_ERR_UNSUPPORTED otherwise
+template <class F> int switch_channels(int C, F&& f) { return effi_switch_nt<32, 16, 8>(C, f); }
+
+// The kernels' view list: S source maps with the reference beside them, or (table_dev) a view table in device memory
+// (EFFI_MAX_VIEWS + 2 pointers: reference, sources, nulls) and no reference argument.
+bool fill_view_list(EffiPtrList& l, const float* ref, const float* const* src, const float* const* table_dev, int S) {
+    if (S < 1 || S > EFFI_MAX_VIEWS) return false;
     for (int i = 0; i <= EFFI_MAX_VIEWS; ++i) l.p[i] = nullptr;
+    l.tbl = table_dev;
+    if (table_dev) return true;
+    if (!ref || !src) return false;
     for (int i = 0; i < S; ++i) {
         if (!src[i]) return false;
         l.p[i] = src[i];
     }
     return true;
 }
+bool fill_out_list(EffiOutList& g, float* const* dst, int S) {
+    if (!dst) return false;
+    for (int i = 0; i <= EFFI_MAX_VIEWS; ++i) g.p[i] = (i < S) ? dst[i] : nullptr;
+    for (int i = 0; i < S; ++i)
+        if (!g.p[i]) return false;
+    return true;
+}
+
+// ---- stage 1: the views family ----
+struct ViewsCommon {            // what a forward and a backward call share
+    const float* ref;
+    EffiPtrList l;
+    int S;
+    const float *rt, *depth;
+    long dds, dps;
+    int C, h, w, D;
+};
+struct ViewsCall : ViewsCommon {
+    float *sim, *ent;
+    WarpBatch b;                // the sample strides of a *_batch entry
+    int n_smp = 1;              // > 1: the batched kernels (blockIdx.z = sample)
+};
+struct ViewsBwdCall : ViewsCommon {
+    const float* gsim;
+    float* gref;
+    EffiOutList g;
+};
+bool fill_views_common(ViewsCommon& a, const float* const* src, const float* const* table_dev) {
+    return fill_view_list(a.l, a.ref, src, table_dev, a.S) && a.rt && a.depth && a.h >= 2 && a.w >= 2 && a.D >= 1;
+}
+int fill_views(ViewsCall& c, const float* const* src, const float* const* table_dev) {
+    const WarpBatch& b = c.b;
+    if (c.n_smp < 1 || c.n_smp > 65535 || b.ref < 0 || b.src < 0 || b.rt < 0 || b.depth < 0 || b.sim < 0 || b.ent < 0) return EFFI_ERR_BADARG;
+    return fill_views_common(c, src, table_dev) && c.sim && c.ent ? EFFI_OK : EFFI_ERR_BADARG;
+}
+int fill_views_bwd(ViewsBwdCall& c, const float* const* src, float* const* grad_src) {
+    return fill_views_common(c, src, nullptr) && c.gsim && c.gref && fill_out_list(c.g, grad_src, c.S) ? EFFI_OK : EFFI_ERR_BADARG;
+}
+
+// x3: the split-precision entries (hi_only: plain bf16 operands, precision "bf16")
+int launch_views(const ViewsCall& c, bool x3, bool hi_only, effi_stream_t stream) {
+    hipStream_t s = effi_s(stream);
+    const EffiViewsForm f = effi_pick_views(x3, c.C, c.dps, c.D, c.h, c.w, effi_warp_opts());
+    const bool batch = c.n_smp > 1, tbl = c.l.tbl != nullptr;   // (no entry of the ABI passes a table together with a batch)
+    const unsigned S = (unsigned)c.S, n = (unsigned)c.n_smp;
+#define EFFI_VIEWS_HEAD c.ref, c.l, c.rt, c.depth, c.dds       // (the gather kernels take dps between the two)
+#define EFFI_VIEWS_TAIL c.h, c.w, c.D, c.sim, c.ent
+    switch (f.kernel) {
+        case EFFI_VIEWS_MM:
+            return effi_switch<0, 1>(hi_only, [&](auto HO) {
+                constexpr bool ho = HO() != 0;
+                const dim3 grid(mm_tiles(c.h, c.w), S, n);
+                if (batch) return effi_launch<warpcorr_views_mm_batch_kernel<ho>>(grid, 256, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL, c.b);
+                if (tbl) return effi_launch<warpcorr_views_mm_kernel<true, ho>>(grid, 256, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL);
+                return effi_launch<warpcorr_views_mm_kernel<false, ho>>(grid, 256, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL);
+            });
+        case EFFI_VIEWS_WINDOW: {
+            const dim3 grid(win_tiles(c.h, c.w), S, n);
+            if (batch) return effi_launch<warpcorr_views_win_batch_kernel<EFFI_WIN_MAXPX>>(grid, WIN_THREADS, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL, f.lds_px, c.b);
+            if (tbl) return effi_launch<warpcorr_views_win_kernel<EFFI_WIN_MAXPX, true>>(grid, WIN_THREADS, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL, f.lds_px);
+            return effi_launch<warpcorr_views_win_kernel<EFFI_WIN_MAXPX, false>>(grid, WIN_THREADS, s, EFFI_VIEWS_HEAD, EFFI_VIEWS_TAIL, f.lds_px);
+        }
+        default:
+            return switch_channels(c.C, [&](auto CC) {
+                constexpr int C = CC();
+                const dim3 grid(grid_blocks<C>(c.h, c.w), S, n);
+                if (batch) return effi_launch<warpcorr_views_batch_kernel<C>>(grid, 256, s, EFFI_VIEWS_HEAD, c.dps, EFFI_VIEWS_TAIL, c.b);
+                return effi_launch<warpcorr_views_kernel<C>>(grid, 256, s, EFFI_VIEWS_HEAD, c.dps, EFFI_VIEWS_TAIL);
+            });
+    }
+#undef EFFI_VIEWS_HEAD
+#undef EFFI_VIEWS_TAIL
+}
+
+// ---- stages 2 / 3: the dynamic stage ----
+struct DynCommon {              // what a forward and a backward call share
+    const float* ref;
+    EffiPtrList l;
+    int S;
+    const float *rt, *cur_depth, *interval, *view_w;
+    int vw_shift, C, h, w, D;
+};
+struct DynCall : DynCommon {
+    float *sim, *samples;
+};
+struct DynBwdCall : DynCommon {
+    const float *sim, *gsim;
+    float* gref;
+    EffiOutList g;
+    double* gvw;
+};
+bool fill_dyn_common(DynCommon& a, const float* const* src, const float* const* table_dev) {
+    if (!fill_view_list(a.l, a.ref, src, table_dev, a.S) || !a.rt || !a.cur_depth || !a.interval || !a.view_w) return false;
+    if (a.h < 2 || a.w < 2 || a.D < 2 || a.vw_shift < 0 || a.vw_shift > 4) return false;
+    return (a.h >> a.vw_shift) << a.vw_shift == a.h && (a.w >> a.vw_shift) << a.vw_shift == a.w;   // view weights: whole cells
+}
+int fill_dyn(DynCall& c, const float* const* src, const float* const* table_dev) {
+    return fill_dyn_common(c, src, table_dev) && c.sim && c.samples ? EFFI_OK : EFFI_ERR_BADARG;
+}
+int fill_dyn_bwd(DynBwdCall& c, const float* const* src, float* const* grad_src) {
+    return fill_dyn_common(c, src, nullptr) && c.sim && c.gsim && c.gref && c.gvw && fill_out_list(c.g, grad_src, c.S) ? EFFI_OK : EFFI_ERR_BADARG;
+}
+
+int launch_dyn(const DynCall& c, effi_stream_t stream) {
+    hipStream_t s = effi_s(stream);
+#define EFFI_DYN_ARGS c.ref, c.l, c.S, c.rt, c.cur_depth, c.interval, c.view_w, c.vw_shift, c.h, c.w, c.D, c.sim, c.samples
+#ifdef EFFI_DIAG_LANE_EXCHANGE
+    // diagnostic builds only: the forms that pass set-ups between lanes (option dyn_xchg: 1 = quad_perm DPP moves, 2 = ds_bpermute)
+    const long xchg = effi_option(EFFI_OPT_DYN_XCHG);
+    if (xchg == 1 || xchg == 2)
+        return switch_channels(c.C, [&](auto CC) {
+            constexpr int C = CC();
+            const dim3 grid(grid_blocks<C>(c.h, c.w));
+            if (xchg == 1) return effi_launch<warpcorr_dyn_kernel<C, false, false>>(grid, 256, s, EFFI_DYN_ARGS);
+            return effi_launch<warpcorr_dyn_kernel<C, true, true>>(grid, 256, s, EFFI_DYN_ARGS);
+        });
+#endif
+    const EffiDynForm f = effi_pick_dyn(c.C, c.S, c.D, c.h, c.w, effi_warp_opts());
+    return switch_channels(c.C, [&](auto CC) {
+        constexpr int C = CC();
+        const dim3 grid(grid_blocks<C>(c.h, c.w));
+        if (f.kernel == EFFI_DYN_EXACT) return effi_launch<warpcorr_dyn_kernel<C>>(grid, 256, s, EFFI_DYN_ARGS);
+        if constexpr (C != 32) {               // (the rule picks these two for C = 8 / 16 only, and only those are instantiated)
+            if (f.kernel == EFFI_DYN_WINDOW) return effi_launch<warpcorr_dyn_win_kernel<C, 32 / C>>(grid, 256, s, EFFI_DYN_ARGS, f.lds_px);
+            if (f.kernel == EFFI_DYN_HYP) return effi_launch<warpcorr_dyn_hyp_kernel<C>>(grid, 256, s, EFFI_DYN_ARGS);
+        }
+        return effi_launch<warpcorr_dyn_kernel<C, true, false, true>>(grid, 256, s, EFFI_DYN_ARGS);
+    });
+#undef EFFI_DYN_ARGS
+}
+
+// ---- the plain homography warp: forward (in = src_nhwc, out = the warped volume) and backward (in = grad_out, out = grad_src_nhwc)
+struct HomoCall {
+    const float *in, *rt, *depth;
+    long dds, dps;
+    int C, h, w, D;
+    float* out;
+};
+int fill_homo(const HomoCall& c) {
+    return c.in && c.rt && c.depth && c.out && c.h >= 2 && c.w >= 2 && c.D >= 1 ? EFFI_OK : EFFI_ERR_BADARG;
+}
 
 }  // namespace
 
 extern "C" int effi_homo_warp_f32(const float* src_nhwc, const float* rt, const float* depth, long dds, long dps,
                                   int C, int h, int w, int D, float* out, effi_stream_t stream) {
-    if (!src_nhwc || !rt || !depth || !out || h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
+    const HomoCall c{src_nhwc, rt, depth, dds, dps, C, h, w, D, out};
+    if (const int rc = fill_homo(c)) return rc;
     hipStream_t s = effi_s(stream);
-    switch (C) {
-        case 32: hipLaunchKernelGGL(homo_warp_kernel<32>, dim3(grid_blocks<32>(h, w)), dim3(256), 0, s, src_nhwc, rt, depth, dds, dps, h, w, D, out); break;
-        case 16: hipLaunchKernelGGL(homo_warp_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, src_nhwc, rt, depth, dds, dps, h, w, D, out); break;
-        case 8:  hipLaunchKernelGGL(homo_warp_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, src_nhwc, rt, depth, dds, dps, h, w, D, out); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return switch_channels(C, [&](auto CC) {
+        return effi_launch<homo_warp_kernel<CC()>>(dim3(grid_blocks<CC()>(h, w)), 256, s, c.in, c.rt, c.depth, c.dds, c.dps, c.h, c.w, c.D, c.out);
+    });
 }
 
 extern "C" int effi_homo_warp_bwd_f32(const float* rt, const float* depth, long dds, long dps, int C, int h, int w, int D,
                                       const float* grad_out, float* grad_src_nhwc, effi_stream_t stream) {
-    if (!rt || !depth || !grad_out || !grad_src_nhwc || h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
+    const HomoCall c{grad_out, rt, depth, dds, dps, C, h, w, D, grad_src_nhwc};
+    if (const int rc = fill_homo(c)) return rc;
     hipStream_t s = effi_s(stream);
-    switch (C) {
-        case 32: hipLaunchKernelGGL(homo_warp_bwd_kernel<32>, dim3(grid_blocks<32>(h, w)), dim3(256), 0, s, rt, depth, dds, dps, h, w, D, grad_out, grad_src_nhwc); break;
-        case 16: hipLaunchKernelGGL(homo_warp_bwd_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, rt, depth, dds, dps, h, w, D, grad_out, grad_src_nhwc); break;
-        case 8:  hipLaunchKernelGGL(homo_warp_bwd_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, rt, depth, dds, dps, h, w, D, grad_out, grad_src_nhwc); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
-// Window capacity of the stage-1 LDS kernel in pixels (128 B each): 72 KB leaves room for two 512-thread workgroups per CU.
-constexpr int WIN_MAXPX = 576;
-
-// Option warp_lds_kb (effi_set_option; tests and A/B runs only): unset = the windowed kernel with its full 72 KB window;
-// 0 = the windowed kernel with every chunk sampled from global memory (same arithmetic, the bitwise cross-check);
-// -1 = the direct-gather kernel (also what C != 32 and per-pixel hypotheses use).
-static int warp_lds_px() {
-    const long kb = effi_option(EFFI_OPT_WARP_LDS_KB);
-    if (kb == EFFI_OPT_UNSET) return WIN_MAXPX;
-    if (kb < 0) return -1;
-    return min(WIN_MAXPX, (int)(kb * 1024 / 128));
-}
-
-// A view table (device memory, EFFI_MAX_VIEWS + 2 pointers: reference, sources, nulls) as the kernels' view list
-static bool fill_table(const float* const* table_dev, int S, EffiPtrList& l) {
-    if (!table_dev || S < 1 || S > EFFI_MAX_VIEWS) return false;
-    for (int i = 0; i <= EFFI_MAX_VIEWS; ++i) l.p[i] = nullptr;
-    l.tbl = table_dev;
-    return true;
-}
-
-// bt != nullptr: n_smp samples in one launch (pointer form only), the kernel form chosen by the same rules
-static int launch_warpcorr_views(const float* ref_nhwc, const EffiPtrList& l, int S, const float* rt, const float* depth, long dds,
-                                 long dps, int C, int h, int w, int D, float* sim_views, float* entropy, effi_stream_t stream,
-                                 const WarpBatch* bt = nullptr, int n_smp = 1) {
-    if (!rt || !depth || !sim_views || !entropy) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
-    hipStream_t s = effi_s(stream);
-    const int lds_px = warp_lds_px();
-    if (bt) {
-        if (l.tbl) return EFFI_ERR_UNSUPPORTED;
-        if (C == 32 && dps == 0 && lds_px >= 0 && D <= 256) {
-            const int tiles = ((w + WIN_TW - 1) / WIN_TW) * ((h + WIN_TH - 1) / WIN_TH);
-            hipLaunchKernelGGL((warpcorr_views_win_batch_kernel<WIN_MAXPX>), dim3(tiles, S, n_smp), dim3(WIN_THREADS), 0, s, ref_nhwc, l, rt,
-                               depth, dds, h, w, D, sim_views, entropy, lds_px, *bt);
-            EFFI_LAUNCH_CHECK();
-            return EFFI_OK;
-        }
-        switch (C) {
-            case 32: hipLaunchKernelGGL(warpcorr_views_batch_kernel<32>, dim3(grid_blocks<32>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
-            case 16: hipLaunchKernelGGL(warpcorr_views_batch_kernel<16>, dim3(grid_blocks<16>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
-            case 8:  hipLaunchKernelGGL(warpcorr_views_batch_kernel<8>, dim3(grid_blocks<8>(h, w), S, n_smp), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy, *bt); break;
-            default: return EFFI_ERR_UNSUPPORTED;
-        }
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    if (C == 32 && dps == 0 && lds_px >= 0 && D <= 256) {
-        // hypotheses shared by all pixels (the cascade's stage 1): taps served from an LDS window
-        const int tiles = ((w + WIN_TW - 1) / WIN_TW) * ((h + WIN_TH - 1) / WIN_TH);
-        if (l.tbl)
-            hipLaunchKernelGGL((warpcorr_views_win_kernel<WIN_MAXPX, true>), dim3(tiles, S), dim3(WIN_THREADS), 0, s, ref_nhwc, l, rt, depth,
-                               dds, h, w, D, sim_views, entropy, lds_px);
-        else
-            hipLaunchKernelGGL((warpcorr_views_win_kernel<WIN_MAXPX, false>), dim3(tiles, S), dim3(WIN_THREADS), 0, s, ref_nhwc, l, rt, depth,
-                               dds, h, w, D, sim_views, entropy, lds_px);
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    switch (C) {
-        case 32: hipLaunchKernelGGL(warpcorr_views_kernel<32>, dim3(grid_blocks<32>(h, w), S), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy); break;
-        case 16: hipLaunchKernelGGL(warpcorr_views_kernel<16>, dim3(grid_blocks<16>(h, w), S), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy); break;
-        case 8:  hipLaunchKernelGGL(warpcorr_views_kernel<8>, dim3(grid_blocks<8>(h, w), S), dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, dps, h, w, D, sim_views, entropy); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return switch_channels(C, [&](auto CC) {
+        return effi_launch<homo_warp_bwd_kernel<CC()>>(dim3(grid_blocks<CC()>(h, w)), 256, s, c.rt, c.depth, c.dds, c.dps, c.h, c.w, c.D, c.in, c.out);
+    });
 }
 
 extern "C" int effi_warpcorr_views_f32(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                        const float* depth, long dds, long dps, int C, int h, int w, int D,
                                        float* sim_views, float* entropy, effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream);
+    ViewsCall c{{ref_nhwc, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy};
+    if (const int rc = fill_views(c, src_nhwc, nullptr)) return rc;
+    return launch_views(c, false, false, stream);
 }
 
-// Split-precision stage-1 form (warpcorr_views_mm_kernel): C = 32 and hypotheses shared by all pixels, else the exact kernels above.
-// hi_only: bf16 operands (precision "bf16").
-static int launch_warpcorr_views_x3(const float* ref_nhwc, const EffiPtrList& l, int S, const float* rt, const float* depth, long dds,
-                                    long dps, int C, int h, int w, int D, float* sim_views, float* entropy, int hi_only,
-                                    effi_stream_t stream, const WarpBatch* bt = nullptr, int n_smp = 1) {
-    if (!rt || !depth || !sim_views || !entropy) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
-    if (!(C == 32 && dps == 0 && D <= 256 && h < 32000 && w < 32000))
-        return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream, bt, n_smp);
-    hipStream_t s = effi_s(stream);
-    if (bt) {
-        if (l.tbl) return EFFI_ERR_UNSUPPORTED;
-        const dim3 bgrid(((w + 15) / 16) * ((h + 3) / 4), S, n_smp);
-        if (hi_only)
-            hipLaunchKernelGGL((warpcorr_views_mm_batch_kernel<true>), bgrid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views,
-                               entropy, *bt);
-        else
-            hipLaunchKernelGGL((warpcorr_views_mm_batch_kernel<false>), bgrid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views,
-                               entropy, *bt);
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    const dim3 grid(((w + 15) / 16) * ((h + 3) / 4), S);
-#define EFFI_MM(TBL, HO) hipLaunchKernelGGL((warpcorr_views_mm_kernel<TBL, HO>), grid, dim3(256), 0, s, ref_nhwc, l, rt, depth, dds, h, w, D, sim_views, entropy)
-    if (l.tbl) { if (hi_only) EFFI_MM(true, true); else EFFI_MM(true, false); }
-    else { if (hi_only) EFFI_MM(false, true); else EFFI_MM(false, false); }
-#undef EFFI_MM
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
+// Split-precision stage-1 form (warpcorr_views_mm_kernel): C = 32 and hypotheses shared by all pixels, else the exact kernels.
 extern "C" int effi_warpcorr_views_x3_f32(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                           const float* depth, long dds, long dps, int C, int h, int w, int D,
                                           float* sim_views, float* entropy, int hi_only, effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views_x3(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, hi_only, stream);
+    ViewsCall c{{ref_nhwc, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy};
+    if (const int rc = fill_views(c, src_nhwc, nullptr)) return rc;
+    return launch_views(c, true, hi_only != 0, stream);
 }
 
-static bool fill_warp_batch(WarpBatch& b, int n_smp, long ref_ss, long src_ss, long rt_ss, long depth_ss, long sim_ss, long ent_ss) {
-    if (n_smp < 1 || n_smp > 65535 || ref_ss < 0 || src_ss < 0 || rt_ss < 0 || depth_ss < 0 || sim_ss < 0 || ent_ss < 0) return false;
-    b = WarpBatch{ref_ss, src_ss, rt_ss, depth_ss, sim_ss, ent_ss};
-    return true;
-}
-
+// n_smp samples in one launch (pointer form only), the kernel form chosen by the same rules; one sample: the unbatched kernels
 extern "C" int effi_warpcorr_views_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                              const float* depth, long dds, long dps, int C, int h, int w, int D, float* sim_views,
                                              float* entropy, int n_smp, long ref_sstride, long src_sstride, long rt_sstride,
                                              long depth_sstride, long sim_sstride, long entropy_sstride, effi_stream_t stream) {
-    EffiPtrList l;
-    WarpBatch b;
-    if (!fill_warp_batch(b, n_smp, ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride)) return EFFI_ERR_BADARG;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream, n_smp > 1 ? &b : nullptr, n_smp);
+    ViewsCall c{{ref_nhwc, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy,
+                {ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride}, n_smp};
+    if (const int rc = fill_views(c, src_nhwc, nullptr)) return rc;
+    return launch_views(c, false, false, stream);
 }
 
 extern "C" int effi_warpcorr_views_x3_f32_batch(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
@@ -1913,149 +1955,59 @@ extern "C" int effi_warpcorr_views_x3_f32_batch(const float* ref_nhwc, const flo
                                                 float* entropy, int hi_only, int n_smp, long ref_sstride, long src_sstride,
                                                 long rt_sstride, long depth_sstride, long sim_sstride, long entropy_sstride,
                                                 effi_stream_t stream) {
-    EffiPtrList l;
-    WarpBatch b;
-    if (!fill_warp_batch(b, n_smp, ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride)) return EFFI_ERR_BADARG;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views_x3(ref_nhwc, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, hi_only, stream,
-                                    n_smp > 1 ? &b : nullptr, n_smp);
+    ViewsCall c{{ref_nhwc, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy,
+                {ref_sstride, src_sstride, rt_sstride, depth_sstride, sim_sstride, entropy_sstride}, n_smp};
+    if (const int rc = fill_views(c, src_nhwc, nullptr)) return rc;
+    return launch_views(c, true, hi_only != 0, stream);
 }
 
 extern "C" int effi_warpcorr_views_x3_tbl_f32(const float* const* view_table_dev, int S, const float* rt, const float* depth, long dds,
                                               long dps, int C, int h, int w, int D, float* sim_views, float* entropy, int hi_only,
                                               effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_table(view_table_dev, S, l)) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views_x3(nullptr, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, hi_only, stream);
+    ViewsCall c{{nullptr, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy};
+    if (const int rc = fill_views(c, nullptr, view_table_dev)) return rc;
+    return launch_views(c, true, hi_only != 0, stream);
 }
 
 extern "C" int effi_warpcorr_views_tbl_f32(const float* const* view_table_dev, int S, const float* rt, const float* depth, long dds,
                                            long dps, int C, int h, int w, int D, float* sim_views, float* entropy,
                                            effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_table(view_table_dev, S, l)) return EFFI_ERR_BADARG;
-    return launch_warpcorr_views(nullptr, l, S, rt, depth, dds, dps, C, h, w, D, sim_views, entropy, stream);
+    ViewsCall c{{nullptr, {}, S, rt, depth, dds, dps, C, h, w, D}, sim_views, entropy};
+    if (const int rc = fill_views(c, nullptr, view_table_dev)) return rc;
+    return launch_views(c, false, false, stream);
 }
 
 extern "C" int effi_warpcorr_views_bwd_f32(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                            const float* depth, long dds, long dps, int C, int h, int w, int D,
                                            const float* grad_sim, float* grad_ref_nhwc, float* const* grad_src_nhwc,
                                            effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc || !rt || !depth || !grad_sim || !grad_ref_nhwc || !grad_src_nhwc) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || D < 1) return EFFI_ERR_BADARG;
-    EffiOutList g;
-    for (int i = 0; i <= EFFI_MAX_VIEWS; ++i) g.p[i] = (i < S) ? grad_src_nhwc[i] : nullptr;
-    for (int i = 0; i < S; ++i)
-        if (!g.p[i]) return EFFI_ERR_BADARG;
+    ViewsBwdCall c{{ref_nhwc, {}, S, rt, depth, dds, dps, C, h, w, D}, grad_sim, grad_ref_nhwc, {}};
+    if (const int rc = fill_views_bwd(c, src_nhwc, grad_src_nhwc)) return rc;
     hipStream_t s = effi_s(stream);
-    const int lds_px = warp_lds_px();
-    if (C == 32 && dps == 0 && lds_px >= 0 && D <= 256) {
-        // hypotheses shared by all pixels: scatter privatised in an LDS window; grad_ref is ACCUMULATED per view (zero on entry)
-        const int tiles = ((w + WIN_TW - 1) / WIN_TW) * ((h + WIN_TH - 1) / WIN_TH);
-        hipLaunchKernelGGL(warpcorr_views_bwd_win_kernel<WIN_MAXPX>, dim3(tiles, S), dim3(WIN_THREADS), 0, s, ref_nhwc, l, rt, depth, dds, h,
-                           w, D, grad_sim, grad_ref_nhwc, g, lds_px);
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    switch (C) {
-        case 32: hipLaunchKernelGGL(warpcorr_views_bwd_kernel<32>, dim3(grid_blocks<32>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, depth, dds, dps, h, w, D, grad_sim, grad_ref_nhwc, g); break;
-        case 16: hipLaunchKernelGGL(warpcorr_views_bwd_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, depth, dds, dps, h, w, D, grad_sim, grad_ref_nhwc, g); break;
-        case 8:  hipLaunchKernelGGL(warpcorr_views_bwd_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, depth, dds, dps, h, w, D, grad_sim, grad_ref_nhwc, g); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
-}
-
-static int launch_warpcorr_dyn(const float* ref_nhwc, const EffiPtrList& l, int S, const float* rt, const float* cur_depth,
-                               const float* interval, const float* view_w, int vw_shift, int C, int h, int w, int D, float* sim,
-                               float* samples, effi_stream_t stream) {
-    if (!rt || !cur_depth || !interval || !view_w || !sim || !samples) return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || D < 2 || vw_shift < 0 || vw_shift > 4) return EFFI_ERR_BADARG;
-    if ((h >> vw_shift) << vw_shift != h || (w >> vw_shift) << vw_shift != w) return EFFI_ERR_BADARG;
-    hipStream_t s = effi_s(stream);
-    // (An 8-channels-per-lane form of this kernel -- one lane per pixel at C = 8, no exchange, no reduction, cheaper projection --
-    // was built and measured at 592x800: 121 us against 109 us; at 296x400, C = 16: 63 against 58.  These kernels are bound by the
-    // number of distinct cache lines a wave-instruction touches in the L1 / texture path, not by instruction issue.)
-#define EFFI_DYN(CC, ...) hipLaunchKernelGGL((warpcorr_dyn_kernel<CC, __VA_ARGS__>), dim3(grid_blocks<CC>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples)
-#ifdef EFFI_DIAG_LANE_EXCHANGE
-    // diagnostic builds only: the forms that pass set-ups between lanes (option dyn_xchg: 1 = quad_perm DPP moves, 2 = ds_bpermute)
-    const long xchg = effi_option(EFFI_OPT_DYN_XCHG);
-    if (xchg == 1 || xchg == 2) {
-        const bool dpp = xchg == 1;
-        switch (C) {
-            case 32: if (dpp) EFFI_DYN(32, false, false); else EFFI_DYN(32, true, true); break;
-            case 16: if (dpp) EFFI_DYN(16, false, false); else EFFI_DYN(16, true, true); break;
-            case 8:  if (dpp) EFFI_DYN(8, false, false); else EFFI_DYN(8, true, true); break;
-            default: return EFFI_ERR_UNSUPPORTED;
-        }
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-#endif
-    // Default for C = 8 / 16 (stages 2 / 3): the hypothesis-per-lane form (91 vs 107 us at 592x800, 60 vs 75 us at 296x400);
-    // option dyn_form = 1 selects the channel-split form below, dyn_setup_exact = 1 the reference's IEEE divisions (A/B runs, tests)
-    const bool lanes = effi_option(EFFI_OPT_DYN_FORM) == 1;
-    const bool exact = effi_option(EFFI_OPT_DYN_SETUP_EXACT) == 1;
-    if (!exact && !lanes && (C == 8 || C == 16) && (long)h * w * C * 4 < (1L << 31)) {
-        // LDS-window form (warpcorr_dyn_win_kernel): D <= 8 (a lane holds the set-ups of its 4 / 2 hypotheses for two views);
-        // option dyn_win: -1 = the gather kernel below, 0 = the window kernel with every view sampled from global memory
-        const long dw = effi_option(EFFI_OPT_DYN_WIN);
-        if (dw != -1 && D <= 8 && S <= EFFI_MAX_VIEWS && h < 32000 && w < 32000) {
-            // option value n > 0: windows of at most n pixels (tests: most boxes then overflow and mix with LDS-served views)
-            const int lds_px = dw == EFFI_OPT_UNSET ? (1 << 20) : (int)max(dw, 0L);
-            if (C == 8)
-                hipLaunchKernelGGL((warpcorr_dyn_win_kernel<8, 4>), dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth,
-                                   interval, view_w, vw_shift, h, w, D, sim, samples, lds_px);
-            else
-                hipLaunchKernelGGL((warpcorr_dyn_win_kernel<16, 2>), dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt,
-                                   cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples, lds_px);
-            EFFI_LAUNCH_CHECK();
-            return EFFI_OK;
-        }
-        if (C == 8) hipLaunchKernelGGL(warpcorr_dyn_hyp_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples);
-        else hipLaunchKernelGGL(warpcorr_dyn_hyp_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples);
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    // set-up arithmetic of the default (exchange-free) form: "fast" (see the kernel) unless EFFI_DYN_SETUP=exact asks for the
-    // reference's IEEE divisions op for op, or the map is too large for 32-bit byte offsets
-    if (!exact && (long)h * w * C * 4 < (1L << 31)) {
-        switch (C) {
-            case 32: EFFI_DYN(32, true, false, true); break;
-            case 16: EFFI_DYN(16, true, false, true); break;
-            case 8:  EFFI_DYN(8, true, false, true); break;
-            default: return EFFI_ERR_UNSUPPORTED;
-        }
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-#undef EFFI_DYN
-    switch (C) {
-        case 32: hipLaunchKernelGGL(warpcorr_dyn_kernel<32>, dim3(grid_blocks<32>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples); break;
-        case 16: hipLaunchKernelGGL(warpcorr_dyn_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples); break;
-        case 8:  hipLaunchKernelGGL(warpcorr_dyn_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, samples); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    const EffiViewsForm f = effi_pick_views(false, C, dps, D, h, w, effi_warp_opts());
+    if (f.kernel == EFFI_VIEWS_WINDOW)         // scatter privatised in an LDS window; grad_ref is ACCUMULATED per view (zero on entry)
+        return effi_launch<warpcorr_views_bwd_win_kernel<EFFI_WIN_MAXPX>>(dim3(win_tiles(h, w), S), WIN_THREADS, s, c.ref, c.l, c.rt, c.depth, c.dds,
+                                                                         c.h, c.w, c.D, c.gsim, c.gref, c.g, f.lds_px);
+    return switch_channels(C, [&](auto CC) {
+        return effi_launch<warpcorr_views_bwd_kernel<CC()>>(dim3(grid_blocks<CC()>(h, w)), 256, s, c.ref, c.l, c.S, c.rt, c.depth, c.dds, c.dps, c.h,
+                                                          c.w, c.D, c.gsim, c.gref, c.g);
+    });
 }
 
 extern "C" int effi_warpcorr_dyn_f32(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                      const float* cur_depth, const float* interval, const float* view_w, int vw_shift,
                                      int C, int h, int w, int D, float* sim, float* samples, effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc) return EFFI_ERR_BADARG;
-    return launch_warpcorr_dyn(ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, C, h, w, D, sim, samples, stream);
+    DynCall c{{ref_nhwc, {}, S, rt, cur_depth, interval, view_w, vw_shift, C, h, w, D}, sim, samples};
+    if (const int rc = fill_dyn(c, src_nhwc, nullptr)) return rc;
+    return launch_dyn(c, stream);
 }
 
 extern "C" int effi_warpcorr_dyn_tbl_f32(const float* const* view_table_dev, int S, const float* rt, const float* cur_depth,
                                          const float* interval, const float* view_w, int vw_shift, int C, int h, int w, int D,
                                          float* sim, float* samples, effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_table(view_table_dev, S, l)) return EFFI_ERR_BADARG;
-    return launch_warpcorr_dyn(nullptr, l, S, rt, cur_depth, interval, view_w, vw_shift, C, h, w, D, sim, samples, stream);
+    DynCall c{{nullptr, {}, S, rt, cur_depth, interval, view_w, vw_shift, C, h, w, D}, sim, samples};
+    if (const int rc = fill_dyn(c, nullptr, view_table_dev)) return rc;
+    return launch_dyn(c, stream);
 }
 
 // effi_view_table_set: n pointers, by value, into a device table (stream-ordered: the replay that follows on the same stream reads them)
@@ -2074,33 +2026,18 @@ extern "C" int effi_view_table_set(const void** table_dev, const void* const* pt
     if (!table_dev || !ptrs || n < 1 || n > EFFI_VIEW_TABLE_MAX) return EFFI_ERR_BADARG;
     EffiTableArgs a;
     for (int i = 0; i < EFFI_VIEW_TABLE_MAX; ++i) a.p[i] = (i < n) ? ptrs[i] : nullptr;
-    hipStream_t s = effi_s(stream);
-    hipLaunchKernelGGL(view_table_set_kernel, dim3(1), dim3(64), 0, s, table_dev, a, n);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<view_table_set_kernel>(dim3(1), 64, effi_s(stream), table_dev, a, n);
 }
 
 extern "C" int effi_warpcorr_dyn_bwd_f32(const float* ref_nhwc, const float* const* src_nhwc, int S, const float* rt,
                                          const float* cur_depth, const float* interval, const float* view_w, int vw_shift, int C, int h,
                                          int w, int D, const float* sim, const float* grad_sim, float* grad_ref_nhwc,
                                          float* const* grad_src_nhwc, double* grad_view_w, effi_stream_t stream) {
-    EffiPtrList l;
-    if (!fill_views(src_nhwc, S, l) || !ref_nhwc || !rt || !cur_depth || !interval || !view_w || !sim || !grad_sim || !grad_ref_nhwc ||
-        !grad_src_nhwc || !grad_view_w)
-        return EFFI_ERR_BADARG;
-    if (h < 2 || w < 2 || D < 2 || vw_shift < 0 || vw_shift > 4) return EFFI_ERR_BADARG;
-    if ((h >> vw_shift) << vw_shift != h || (w >> vw_shift) << vw_shift != w) return EFFI_ERR_BADARG;
-    EffiOutList g;
-    for (int i = 0; i <= EFFI_MAX_VIEWS; ++i) g.p[i] = (i < S) ? grad_src_nhwc[i] : nullptr;
-    for (int i = 0; i < S; ++i)
-        if (!g.p[i]) return EFFI_ERR_BADARG;
+    DynBwdCall c{{ref_nhwc, {}, S, rt, cur_depth, interval, view_w, vw_shift, C, h, w, D}, sim, grad_sim, grad_ref_nhwc, {}, grad_view_w};
+    if (const int rc = fill_dyn_bwd(c, src_nhwc, grad_src_nhwc)) return rc;
     hipStream_t s = effi_s(stream);
-    switch (C) {
-        case 32: hipLaunchKernelGGL(warpcorr_dyn_bwd_kernel<32>, dim3(grid_blocks<32>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, grad_sim, grad_ref_nhwc, g, grad_view_w); break;
-        case 16: hipLaunchKernelGGL(warpcorr_dyn_bwd_kernel<16>, dim3(grid_blocks<16>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, grad_sim, grad_ref_nhwc, g, grad_view_w); break;
-        case 8:  hipLaunchKernelGGL(warpcorr_dyn_bwd_kernel<8>, dim3(grid_blocks<8>(h, w)), dim3(256), 0, s, ref_nhwc, l, S, rt, cur_depth, interval, view_w, vw_shift, h, w, D, sim, grad_sim, grad_ref_nhwc, g, grad_view_w); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return switch_channels(C, [&](auto CC) {
+        return effi_launch<warpcorr_dyn_bwd_kernel<CC()>>(dim3(grid_blocks<CC()>(h, w)), 256, s, c.ref, c.l, c.S, c.rt, c.cur_depth, c.interval, c.view_w,
+                                                        c.vw_shift, c.h, c.w, c.D, c.sim, c.gsim, c.gref, c.g, c.gvw);
+    });
 }

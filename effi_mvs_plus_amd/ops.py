@@ -639,15 +639,21 @@ def warpcorr_views(ref_nhwc, srcs_nhwc, rt, depth, D, x3=False):
                 for b in range(n)]
         return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
     depth, dds, dps, dss = _depth_strides(depth, n, D, h, w)
+    return _warpcorr_views((_p(ref_nhwc), _ptr_array(srcs_nhwc)), False, S, Cc, h, w, rt, depth, dds, dps, D, x3, n,
+                           lambda sim, ent: (rs, sstr.pop(), rts, dss, sim.stride(0), ent.stride(0)))
+
+
+def _warpcorr_views(views, tbl, S, Cc, h, w, rt, depth, dds, dps, D, x3, n=None, tail=None):
+    """The outputs, the profile record and the one C call of ``warpcorr_views`` (``views``: reference and source pointers) and of
+    ``warpcorr_views_tbl`` (``views``: the row of a ViewTable; ``tbl``).  ``n`` / ``tail(sim, ent)``: sample count and strides."""
     lead, reps = (() if n is None else (n,)), n or 1
-    sim = torch.empty(lead + (S, D, h, w), device=ref_nhwc.device, dtype=torch.float32)
-    ent = torch.empty(lead + (S, h, w), device=ref_nhwc.device, dtype=torch.float32)
+    sim = torch.empty(lead + (S, D, h, w), device=rt.device, dtype=torch.float32)
+    ent = torch.empty(lead + (S, h, w), device=rt.device, dtype=torch.float32)
     work = lambda: {"flops": reps * S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * reps * h * w * (S * Cc + Cc + S * D + S)}
     x3 = bool(x3) and uses_split()
-    _launch("effi_warpcorr_views_x3_f32" if x3 else "effi_warpcorr_views_f32",
-            (_p(ref_nhwc), _ptr_array(srcs_nhwc), S, _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent))
-            + ((int(_PRECISION == "bf16"),) if x3 else ()),
-            n, lambda: (rs, sstr.pop(), rts, dss, sim.stride(0), ent.stride(0)), key=f"warpcorr_views_c{Cc}", work=work)
+    _launch("effi_warpcorr_views" + ("_x3" if x3 else "") + ("_tbl" if tbl else "") + "_f32",
+            views + (S, _p(rt), _p(depth), dds, dps, Cc, h, w, D, _p(sim), _p(ent)) + ((int(_PRECISION == "bf16"),) if x3 else ()),
+            n, lambda: tail(sim, ent), key=f"warpcorr_views_c{Cc}", work=work)
     return sim, ent
 
 
@@ -720,37 +726,38 @@ def warpcorr_views_tbl(table, stage, rt, depth, D, x3=False):
     if rt.shape[0] != S:
         raise ValueError("Different number of images and projection matrices")
     depth, dds, dps, _ = _depth_strides(depth, None, D, h, w)
-    sim = torch.empty(S, D, h, w, device=rt.device, dtype=torch.float32)
-    ent = torch.empty(S, h, w, device=rt.device, dtype=torch.float32)
-    work = lambda: {"flops": S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * h * w * (S * Cc + Cc + S * D + S)}
-    if x3 and uses_split():
-        check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_x3_tbl_f32, table.row(stage), S, _p(rt), _p(depth), dds,
-                    dps, Cc, h, w, D, _p(sim), _p(ent), int(_PRECISION == "bf16"), _stream()), "effi_warpcorr_views_x3_tbl_f32")
-        return sim, ent
-    check(_call(f"warpcorr_views_c{Cc}", work, _lib.lib().effi_warpcorr_views_tbl_f32, table.row(stage), S, _p(rt), _p(depth), dds, dps,
-                Cc, h, w, D, _p(sim), _p(ent), _stream()), "effi_warpcorr_views_tbl_f32")
-    return sim, ent
+    return _warpcorr_views((table.row(stage),), True, S, Cc, h, w, rt, depth, dds, dps, D, x3)
 
 
-def warpcorr_dyn_tbl(table, stage, rt, cur_depth, interval, view_w, D):
-    """``warpcorr_dyn`` reading its reference / source maps through row ``stage`` of a ViewTable."""
-    Cc, h, w = table.shapes[stage]
-    S = table.n_views - 1
-    _t(rt, "rt"), _t(cur_depth, "cur_depth"), _t(interval, "interval"), _t(view_w, "view_w")
-    if view_w.shape[0] != S or rt.shape[0] != S:
-        raise ValueError("view weights / projections / sources disagree on the number of views")
+def _vw_shift(view_w, h, w):
+    """k of view weights [S, h >> k, w >> k] on an h x w map; anything else is refused (the library answers EFFI_ERR_BADARG)."""
     vh, vw = view_w.shape[1], view_w.shape[2]
     shift = 0
     while (vh << shift) < h:
         shift += 1
     if (vh << shift) != h or (vw << shift) != w:
         raise ValueError(f"view weights {vh}x{vw} are not a power-of-two downsampling of {h}x{w}")
+    return shift
+
+
+def _warpcorr_dyn(entry, views, S, Cc, h, w, rt, cur_depth, interval, view_w, D):
+    """The body of ``warpcorr_dyn`` (``views``: reference and source pointers) and ``warpcorr_dyn_tbl`` (the row of a ViewTable)."""
+    _t(rt, "rt"), _t(cur_depth, "cur_depth"), _t(interval, "interval"), _t(view_w, "view_w")
+    if view_w.shape[0] != S or rt.shape[0] != S:
+        raise ValueError("view weights / projections / sources disagree on the number of views")
+    shift = _vw_shift(view_w, h, w)
     sim = torch.empty(D, h, w, device=rt.device, dtype=torch.float32)
     samples = torch.empty(D, h, w, device=rt.device, dtype=torch.float32)
     work = lambda: {"flops": S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * h * w * (S * Cc + Cc + 2 * D + 1 + S / 4.0 ** shift)}
-    check(_call(f"warpcorr_dyn_c{Cc}", work, _lib.lib().effi_warpcorr_dyn_tbl_f32, table.row(stage), S, _p(rt), _p(cur_depth),
-                _p(interval), _p(view_w), shift, Cc, h, w, D, _p(sim), _p(samples), _stream()), "effi_warpcorr_dyn_tbl_f32")
+    check(_call(f"warpcorr_dyn_c{Cc}", work, getattr(_lib.lib(), entry), *views, S, _p(rt), _p(cur_depth), _p(interval), _p(view_w), shift,
+                Cc, h, w, D, _p(sim), _p(samples), _stream()), entry)
     return sim, samples
+
+
+def warpcorr_dyn_tbl(table, stage, rt, cur_depth, interval, view_w, D):
+    """``warpcorr_dyn`` reading its reference / source maps through row ``stage`` of a ViewTable."""
+    Cc, h, w = table.shapes[stage]
+    return _warpcorr_dyn("effi_warpcorr_dyn_tbl_f32", (table.row(stage),), table.n_views - 1, Cc, h, w, rt, cur_depth, interval, view_w, D)
 
 
 def pixelwise_net(entropy, params):
@@ -785,25 +792,11 @@ def view_aggregate(sim_views, weights):
 def warpcorr_dyn(ref_nhwc, srcs_nhwc, rt, cur_depth, interval, view_w, D):
     """cur_depth [h,w]; interval: 1-element tensor; view_w [S,h>>k,w>>k] -> (sim [D,h,w], samples [D,h,w])."""
     h, w, Cc = ref_nhwc.shape
-    S = len(srcs_nhwc)
-    _t(ref_nhwc, "ref_nhwc"), _t(rt, "rt"), _t(cur_depth, "cur_depth"), _t(interval, "interval"), _t(view_w, "view_w")
+    _t(ref_nhwc, "ref_nhwc")
     for s in srcs_nhwc:
         _t(s, "src_nhwc")
-    if view_w.shape[0] != S or rt.shape[0] != S:
-        raise ValueError("view weights / projections / sources disagree on the number of views")
-    vh, vw = view_w.shape[1], view_w.shape[2]
-    shift = 0
-    while (vh << shift) < h:
-        shift += 1
-    if (vh << shift) != h or (vw << shift) != w:
-        raise ValueError(f"view weights {vh}x{vw} are not a power-of-two downsampling of {h}x{w}")
-    sim = torch.empty(D, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    samples = torch.empty(D, h, w, device=ref_nhwc.device, dtype=torch.float32)
-    work = lambda: {"flops": S * D * h * w * (10.0 * Cc + 20), "bytes": 4.0 * h * w * (S * Cc + Cc + 2 * D + 1 + S / 4.0 ** shift)}
-    check(_call(f"warpcorr_dyn_c{Cc}", work, _lib.lib().effi_warpcorr_dyn_f32, _p(ref_nhwc), _ptr_array(srcs_nhwc), S, _p(rt),
-                _p(cur_depth), _p(interval), _p(view_w), shift, Cc, h, w, D, _p(sim), _p(samples), _stream()),
-          "effi_warpcorr_dyn_f32")
-    return sim, samples
+    return _warpcorr_dyn("effi_warpcorr_dyn_f32", (_p(ref_nhwc), _ptr_array(srcs_nhwc)), len(srcs_nhwc), Cc, h, w, rt, cur_depth, interval,
+                         view_w, D)
 
 
 def _conv_out(size, stride):
@@ -2897,10 +2890,7 @@ def warpcorr_dyn_bwd(ref_nhwc, srcs_nhwc, rt, cur_depth, interval, view_w, D, si
     S = len(srcs_nhwc)
     for t_ in (ref_nhwc, rt, cur_depth, interval, view_w, sim, grad_sim):
         _t(t_, "warpcorr_dyn_bwd operand")
-    vh = view_w.shape[1]
-    shift = 0
-    while (vh << shift) < h:
-        shift += 1
+    shift = _vw_shift(view_w, h, w)
     g_ref = torch.empty_like(ref_nhwc)
     g_src = [torch.zeros_like(s_) for s_ in srcs_nhwc]
     g_vw = torch.zeros(view_w.shape, device=view_w.device, dtype=torch.float64)      # 64-bit atomics: the sum cancels (see the kernel)
