@@ -107,6 +107,7 @@ extern "C" int effi_launch_form(int launcher, int nt, int h, int w, int planes, 
         case EFFI_LF_DECONV_X3: f = effi_pick_deconv_x3(cout, h, w, planes, count, o); break;
         case EFFI_LF_C3_PLANES: f = effi_pick_c3_planes(h, w, planes, count); break;
         case EFFI_LF_DECONV_K3: f = effi_pick_deconv_k3(cout, h, w, planes, count); break;
+        case EFFI_LF_C3_ZPT: f = EffiForm{1, EFFI_C3_TX, 4, effi_pick_c3_zpt(s2 ? 2 : 1, s2 ? 2 : 1, h, w, planes, nt, count), 0}; break;
         default: return EFFI_ERR_BADARG;
     }
     form[0] = f.rows, form[1] = f.cols, form[2] = f.waves, form[3] = f.planes, form[4] = f.variant;

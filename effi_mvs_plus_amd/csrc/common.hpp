@@ -239,6 +239,10 @@ __device__ __forceinline__ float lookup1d_fetch(const float* __restrict__ vol, l
 __host__ __device__ inline bool effi_vol_fits32(long npix, long ps, int D, long ds) {
     return ps >= 0 && ds >= 0 && npix >= 1 && D >= 1 && ((npix - 1) * ps + (long)(D - 1) * ds + 1) * 4 < (1L << 31);
 }
+// off32 of a look-up: both of its volumes fit (cur_vol: pixel stride cps, Dcur planes of stride cds; reg_vol: rps, Dreg, rds)
+__host__ __device__ inline bool effi_lookup_fits32(long npix, long cps, int Dcur, long cds, long rps, int Dreg, long rds) {
+    return effi_vol_fits32(npix, cps, Dcur, cds) && effi_vol_fits32(npix, rps, Dreg, rds);
+}
 template <int NQ>
 __device__ __forceinline__ void effi_getcost_pixel(float inv_or_depth, int input_is_depth, const float* __restrict__ disp_range, int n_range,
                                                    float itv, const float* __restrict__ cur_vol, long cpo, long cds, int Dcur,

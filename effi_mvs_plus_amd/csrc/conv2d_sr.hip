@@ -117,7 +117,7 @@ extern "C" int EFFI_FN(effi_encoder_pair_gen_bf16x3_sr)(const float* inv_depth, 
     a1.out_sr = reinterpret_cast<unsigned short*>(out_sr_d2);
     const EncGenArgs g{inv_depth, disp_range, n_range, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg, dmin, dmax, range_ps,
                        weight_c1, bias_c1, weight_d1, bias_d1, hd,
-                       effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds)};
+                       effi_lookup_fits32((long)h * w, cps, Dcur, cds, rps, Dreg, rds)};
     hipStream_t st = effi_s(stream);
     return effi_switch_nt<1, 2, 3>(cout / 16, [&](auto NT) { return launch_bf16x3_encgen_pair<NT()>(a0, a1, g, st); });
 }

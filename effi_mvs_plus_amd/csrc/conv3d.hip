@@ -358,33 +358,32 @@ static bool c3_lean(int bit) {
     return v == EFFI_OPT_UNSET || ((v >> bit) & 1);
 }
 
-// launch rule of the cin = 1 kernel: 8 planes per thread when the grid still covers the chip twice.  grid.y = the two calls of a pair
-// (b != nullptr) or the n_smp samples of a batch (sample strides in_ss / out_ss; a pixel's FMA order does not depend on the planes
-// per thread, so the rule may count the workgroups of all samples)
-int launch_c1to8(const C1Call& a, const C1Call* b, int D, int h, int w, int sxy, int relu, hipStream_t st, int n_smp = 1, long in_ss = 0,
-                 long out_ss = 0) {
-    if ((long)D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input volume
-    const int ho = (h - 1) / sxy + 1, wo = (w - 1) / sxy + 1;
-    const long tiles = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY), ncall = b ? 2 : n_smp;
-    const bool z8 = effi_pick_c3_planes(ho, wo, D, ncall).planes == 8;
-    const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
-    const C1Call& bb = b ? *b : a;
-#define EFFI_C1(SXYV, ZV)                                                                                                             \
-    do {                                                                                                                              \
-        if (n_smp > 1)                                                                                                                \
-            hipLaunchKernelGGL((conv3d_c1to8_batch_kernel<SXYV, ZV>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, ho, wo, relu); \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((conv3d_c1to8_kernel<SXYV, ZV>), grid, dim3(256), 0, st, a, bb, D, h, w, ho, wo, relu);                  \
-    } while (0)
-    if (sxy == 1) {
-        if (z8) EFFI_C1(1, 8);
-        else EFFI_C1(1, 4);
-    } else {
-        if (z8) EFFI_C1(2, 8);
-        else EFFI_C1(2, 4);
-    }
-#undef EFFI_C1
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+// the layers the two dedicated kernels take: decided here for the single, batched and pair entries of both directions
+static bool route_c1to8(int cin, int cout, int sz, int sxy, const float* skip) {
+    return cin == 1 && cout == 8 && sz == 1 && (sxy == 1 || sxy == 2) && !skip && c3_lean(0);
+}
+static bool route_c8to1(int cin, int cout, int sz, const float* skip) { return cin == 8 && cout == 1 && sz == 1 && !skip && c3_lean(1); }
+
+// The sample batch of a launch, host side: the count and the strides the batched kernels take (the 1 -> 8, 8 -> 1 and transposed
+// kernels have one input: its stride is ss.src[0]).  A launcher gets it as ``const C3Samples* bt``, nullptr for a single sample.
+struct C3Samples {
+    int n;
+    C3Batch ss;
+};
+
+// launch rule of the cin = 1 kernel: effi_pick_c3_planes on the OUTPUT map.  grid.y = the two calls of a pair (b != nullptr) or the
+// samples of a batch (a pixel's FMA order does not depend on the planes per thread, so the rule counts the workgroups of all samples)
+int launch_c1to8(const C1Call& a, const C1Call* b, int D, int h, int w, int sxy, int relu, hipStream_t st, const C3Samples* bt = nullptr) {
+    if (!effi_c1to8_fits32(D, h, w)) return EFFI_ERR_UNSUPPORTED;
+    const int ho = (h - 1) / sxy + 1, wo = (w - 1) / sxy + 1, ncall = b ? 2 : bt ? bt->n : 1;
+    const int planes = effi_pick_c3_planes(ho, wo, D, ncall).planes;
+    const dim3 grid(effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(D, planes), ncall);
+    return effi_switch<1, 2>(sxy, [&](auto SXY) {
+        return effi_switch<4, 8>(planes, [&](auto ZPT) {
+            if (bt) return effi_launch<conv3d_c1to8_batch_kernel<SXY(), ZPT()>>(grid, 256, st, a, bt->ss.src[0], bt->ss.out, D, h, w, ho, wo, relu);
+            return effi_launch<conv3d_c1to8_kernel<SXY(), ZPT()>>(grid, 256, st, a, b ? *b : a, D, h, w, ho, wo, relu);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -586,22 +585,16 @@ __global__ __launch_bounds__(256) void conv3d_c8to1_batch_kernel(C8Call c, long 
     conv3d_c8to1_body<DECONV, ZPT>(c.in + smp * in_ss, c.wgt, c.bias, c.out + smp * out_ss, D, h, w, relu);
 }
 
-// (grid.y: the two calls of a pair, or the n_smp samples of a batch -- as launch_c1to8)
+// (grid.y: the two calls of a pair, or the samples of a batch -- as launch_c1to8)
 template <bool DECONV>
-int launch_c8to1(const C8Call& a, const C8Call* b, int D, int h, int w, int relu, hipStream_t st, int n_smp = 1, long in_ss = 0,
-                 long out_ss = 0) {
-    if (8L * D * h * w >= (1L << 29)) return EFFI_ERR_UNSUPPORTED;              // 32-bit byte offsets inside the input tensor
-    const long tiles = (long)effi_cdiv(w, TX) * effi_cdiv(h, TY), ncall = b ? 2 : n_smp;
-    const bool z8 = effi_pick_c3_planes(h, w, D, ncall).planes == 8;
-    const dim3 grid((unsigned)(tiles * effi_cdiv(D, z8 ? 8 : 4)), (unsigned)ncall);
-    if (n_smp > 1) {
-        if (z8) hipLaunchKernelGGL((conv3d_c8to1_batch_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, relu);
-        else hipLaunchKernelGGL((conv3d_c8to1_batch_kernel<DECONV, 4>), grid, dim3(256), 0, st, a, in_ss, out_ss, D, h, w, relu);
-    } else {
-        if (z8) hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 8>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
-        else hipLaunchKernelGGL((conv3d_c8to1_kernel<DECONV, 4>), grid, dim3(256), 0, st, a, b ? *b : a, D, h, w, relu);
-    }
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+int launch_c8to1(const C8Call& a, const C8Call* b, int D, int h, int w, int relu, hipStream_t st, const C3Samples* bt = nullptr) {
+    if (!effi_c8to1_fits32(D, h, w)) return EFFI_ERR_UNSUPPORTED;
+    const int ncall = b ? 2 : bt ? bt->n : 1, planes = effi_pick_c3_planes(h, w, D, ncall).planes;
+    const dim3 grid(effi_cdiv(w, TX) * effi_cdiv(h, TY) * effi_cdiv(D, planes), ncall);
+    return effi_switch<4, 8>(planes, [&](auto ZPT) {
+        if (bt) return effi_launch<conv3d_c8to1_batch_kernel<DECONV, ZPT()>>(grid, 256, st, a, bt->ss.src[0], bt->ss.out, D, h, w, relu);
+        return effi_launch<conv3d_c8to1_kernel<DECONV, ZPT()>>(grid, 256, st, a, b ? *b : a, D, h, w, relu);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -799,82 +792,139 @@ __global__ __launch_bounds__(256) void deconv3d_k3_pair_kernel(Deconv3dCall a, D
                                  second ? b.skip : a.skip, second ? b.out : a.out);
 }
 
-template <int COUT_T, int SZ, int SXY, int ZPT>
-int launch_conv_z(const SrcSet& s, int cin, const float* wgt, const float* bias, int cout, int D, int h, int w,
-                  int relu, const float* skip, float* out, hipStream_t st, const C3Batch* bt = nullptr, int n_smp = 1) {
-    const int Do = (D - 1) / SZ + 1, ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
-    dim3 grid(effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, ZPT) * effi_cdiv(cout, COUT_T));
-    if (bt) {
-        grid.y = (unsigned)n_smp;
-        if (cout == COUT_T)
-            hipLaunchKernelGGL((conv3d_k3_batch_kernel<COUT_T, SZ, SXY, ZPT, true>), grid, dim3(256), 0, st, s, *bt, cin, wgt, bias, cout, D,
-                               h, w, Do, ho, wo, relu, skip, out);
-        else
-            hipLaunchKernelGGL((conv3d_k3_batch_kernel<COUT_T, SZ, SXY, ZPT, false>), grid, dim3(256), 0, st, s, *bt, cin, wgt, bias, cout, D,
-                               h, w, Do, ho, wo, relu, skip, out);
-        return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-    }
-    if (cout == COUT_T)
-        hipLaunchKernelGGL((conv3d_k3_kernel<COUT_T, SZ, SXY, ZPT, true>), grid, dim3(256), 0, st, s, cin, wgt, bias, cout, D, h, w,
-                           Do, ho, wo, relu, skip, out);
-    else
-        hipLaunchKernelGGL((conv3d_k3_kernel<COUT_T, SZ, SXY, ZPT, false>), grid, dim3(256), 0, st, s, cin, wgt, bias, cout, D, h, w,
-                           Do, ho, wo, relu, skip, out);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+// The general kernel, one launcher: a single call, the two calls of a pair (b != nullptr: 8 output channels, stride 1 in z) or the
+// samples of a batch (bt).  Strides (1,1,1), (2,2,2) and (1,2,2); a workgroup owns 8 output channels (cout % 8 == 0) or, at stride 1,
+// the one of cout == 1; DENSE: cout is that tile (see conv3d_k3_body).  Planes per thread: effi_pick_c3_zpt.
+int launch_conv(const Conv3dCall& a, const Conv3dCall* b, int cin, int cout, int D, int h, int w, int sz, int sxy, int relu, hipStream_t st,
+                const C3Samples* bt = nullptr) {
+    const int ct = cout % 8 == 0 ? 8 : 1, ncall = b ? 2 : bt ? bt->n : 1;
+    if ((ct == 1 && cout != 1) || (sxy != 1 && sxy != 2)) return EFFI_ERR_UNSUPPORTED;
+    return effi_switch_nt<11, 22, 12>(10L * sz + sxy, [&](auto STRIDES) {   // (10 sz + sxy, sxy one digit)
+        constexpr int SZ = STRIDES() / 10, SXY = STRIDES() % 10;
+        const int Do = (D - 1) / SZ + 1, ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
+        const int zpt = effi_pick_c3_zpt(SZ, SXY, ho, wo, Do, effi_cdiv(cout, ct), ncall);
+        const dim3 grid(effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, zpt) * effi_cdiv(cout, ct), ncall);
+        return effi_switch_nt<8, 1>(ct, [&](auto COUT_T) {
+            return effi_switch<1, effi_c3_zbig(SZ, SXY)>(zpt, [&](auto ZPT) {
+                constexpr int CT = COUT_T(), Z = ZPT();
+                if constexpr (CT == 1 && SXY != 1) {
+                    return EFFI_ERR_UNSUPPORTED;                                  // one output channel: stride 1 only
+                } else {
+                    if (b) {
+                        if constexpr (CT == 8 && SZ == 1)
+                            return effi_launch<conv3d_k3_pair_kernel<8, 1, SXY, Z>>(grid, 256, st, a, *b, cin, cout, D, h, w, Do, ho, wo, relu);
+                        else return EFFI_ERR_UNSUPPORTED;
+                    }
+                    return effi_switch<0, 1>(cout == CT, [&](auto DENSE) {
+                        constexpr bool dense = DENSE() != 0;
+                        if (bt)
+                            return effi_launch<conv3d_k3_batch_kernel<CT, SZ, SXY, Z, dense>>(grid, 256, st, a.src, bt->ss, cin, a.wgt, a.bias, cout,
+                                                                                              D, h, w, Do, ho, wo, relu, a.skip, a.out);
+                        return effi_launch<conv3d_k3_kernel<CT, SZ, SXY, Z, dense>>(grid, 256, st, a.src, cin, a.wgt, a.bias, cout, D, h, w, Do, ho,
+                                                                                    wo, relu, a.skip, a.out);
+                    });
+                }
+            });
+        });
+    });
 }
 
-// Output z-slices per thread: 4 (2 for stride 2) amortises the z halo of the LDS tile; low-resolution layers
-// fall back to 1 so that the grid still has >= 2 workgroups per CU.
-// (batched, bt != nullptr: the rule on the workgroups of all n_smp samples; an output's FMA order does not depend on ZPT)
-template <int COUT_T, int SZ, int SXY>
-int launch_conv(const SrcSet& s, int cin, const float* wgt, const float* bias, int cout, int D, int h, int w,
-                int relu, const float* skip, float* out, hipStream_t st, const C3Batch* bt = nullptr, int n_smp = 1) {
-    constexpr int ZBIG = (SXY == 1) ? 4 : ((SZ == 1) ? 4 : 2);
-    const int Do = (D - 1) / SZ + 1, ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
-    const long blocks = (long)effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(Do, ZBIG) * effi_cdiv(cout, COUT_T) * n_smp;
-    if (blocks >= 384) return launch_conv_z<COUT_T, SZ, SXY, ZBIG>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
-    return launch_conv_z<COUT_T, SZ, SXY, 1>(s, cin, wgt, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
+// The transposed kernel, one launcher: stride 2 with cout % 8 == 0 (output channels per thread: effi_pick_deconv_k3; 4 on the
+// low-resolution level, so that the grid covers the chip) or stride 1 to one channel, which alone has a pair form
+int launch_deconv(const Deconv3dCall& a, const Deconv3dCall* b, int cin, int cout, int D, int h, int w, int sz, int relu, hipStream_t st,
+                  const C3Samples* bt = nullptr) {
+    const int tiles = effi_cdiv(w, TX) * effi_cdiv(h, TY), ncall = b ? 2 : bt ? bt->n : 1;
+    int ct, gx;
+    if (sz == 2 && cout % 8 == 0 && !b) {
+        ct = effi_pick_deconv_k3(cout, h, w, D, ncall).planes;
+        gx = tiles * D * (cout / ct);
+    } else if (sz == 1 && cout == 1) {
+        ct = 1, gx = tiles * effi_cdiv(D, 4);
+    } else {
+        return EFFI_ERR_UNSUPPORTED;
+    }
+    const dim3 grid(gx, ncall);
+    return effi_switch<8, 4, 1>(ct, [&](auto COUT_T) {
+        constexpr int CT = COUT_T(), SZ = CT == 1 ? 1 : 2;
+        if constexpr (CT == 1)
+            if (b) return effi_launch<deconv3d_k3_pair_kernel<1, 1>>(grid, 256, st, a, *b, cin, cout, D, h, w, relu);
+        if (bt)
+            return effi_launch<deconv3d_k3_batch_kernel<CT, SZ>>(grid, 256, st, a.in, bt->ss.src[0], cin, a.wgt, a.bias, cout, D, h, w, relu, a.skip,
+                                                                 bt->ss.skip, a.out, bt->ss.out);
+        return effi_launch<deconv3d_k3_kernel<CT, SZ>>(grid, 256, st, a.in, cin, a.wgt, a.bias, cout, D, h, w, relu, a.skip, a.out);
+    });
 }
 
 }  // namespace
 
-static int conv3d_k3_impl(const float* const* srcs, const int* src_channels, int n_src, const float* weight, const float* bias, int cout,
-                          int D, int h, int w, int sz, int sxy, int relu, const float* skip, float* out, const C3Batch* bt, int n_smp,
-                          effi_stream_t stream) {
-    if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !weight || !out) return EFFI_ERR_BADARG;
-    if (D < 1 || h < 1 || w < 1 || cout < 1) return EFFI_ERR_BADARG;
-    SrcSet s;
-    int cin = 0;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        s.p[i] = (i < n_src) ? srcs[i] : nullptr;
-        s.ch[i] = (i < n_src) ? src_channels[i] : 0;
-        if (i < n_src && (!srcs[i] || src_channels[i] < 1)) return EFFI_ERR_BADARG;
-        cin += s.ch[i];
+// ---- entries: the family's call struct from its filler (which validates), the route to a dedicated kernel, the launcher -------------
+// cat(srcs) with its weights, skip tensor and output -> c (unused source slots null / 0), the channel sum -> cin
+static int fill_conv(Conv3dCall& c, int& cin, const float* const* srcs, const int* src_channels, int n_src, const float* weight,
+                     const float* bias, const float* skip, float* out, int D, int h, int w) {
+    if (!srcs || !src_channels || n_src < 1 || n_src > EFFI_MAX_SRC || !weight || !out || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    c = Conv3dCall{SrcSet{}, weight, bias, skip, out};
+    cin = 0;
+    for (int i = 0; i < n_src; ++i) {
+        if (!srcs[i] || src_channels[i] < 1) return EFFI_ERR_BADARG;
+        c.src.p[i] = srcs[i], c.src.ch[i] = src_channels[i];
+        cin += src_channels[i];
     }
+    return EFFI_OK;
+}
+static int fill_deconv(Deconv3dCall& c, const float* in, const float* weight, const float* bias, const float* skip, float* out, int cin,
+                       int D, int h, int w) {
+    if (!in || !weight || !out || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    c = Deconv3dCall{in, weight, bias, skip, out};
+    return EFFI_OK;
+}
+// the sample batch of a *_batch entry: the strides of its n_src sources (the other slots 0), of the skip tensor and of the output
+static int fill_samples(C3Samples& b, int n_smp, const long* src_ss, int n_src, long skip_ss, long out_ss) {
+    if (n_smp < 1 || n_smp > 65535 || !src_ss || skip_ss < 0 || out_ss < 0 || n_src < 1 || n_src > EFFI_MAX_SRC) return EFFI_ERR_BADARG;
+    b = C3Samples{n_smp, C3Batch{{}, skip_ss, out_ss}};
+    for (int i = 0; i < n_src; ++i) {
+        if (src_ss[i] < 0) return EFFI_ERR_BADARG;
+        b.ss.src[i] = src_ss[i];
+    }
+    return EFFI_OK;
+}
+
+// one call (b == nullptr), the two of a pair or a sample batch (bt), forward: the dedicated kernel of the layer, else the general one
+static int conv3d_k3_run(const Conv3dCall& a, const Conv3dCall* b, int cin, int cout, int D, int h, int w, int sz, int sxy, int relu,
+                         const C3Samples* bt, effi_stream_t stream) {
     hipStream_t st = effi_s(stream);
-    if (cin == 1 && cout == 8 && sz == 1 && (sxy == 1 || sxy == 2) && !skip && c3_lean(0)) {
-        const C1Call c{srcs[0], weight, bias, out};
-        return launch_c1to8(c, nullptr, D, h, w, sxy, relu, st, n_smp, bt ? bt->src[0] : 0, bt ? bt->out : 0);
+    if (route_c1to8(cin, cout, sz, sxy, a.skip)) {
+        const C1Call ca{a.src.p[0], a.wgt, a.bias, a.out}, cb = b ? C1Call{b->src.p[0], b->wgt, b->bias, b->out} : ca;
+        return launch_c1to8(ca, b ? &cb : nullptr, D, h, w, sxy, relu, st, bt);
     }
-    if (cin == 8 && n_src == 1 && cout == 1 && sz == 1 && sxy == 1 && !skip && c3_lean(1)) {
-        const C8Call c{srcs[0], weight, bias, out};
-        return launch_c8to1<false>(c, nullptr, D, h, w, relu, st, n_smp, bt ? bt->src[0] : 0, bt ? bt->out : 0);
+    if (a.src.ch[0] == 8 && sxy == 1 && route_c8to1(cin, cout, sz, a.skip))       // (ONE source of 8 channels)
+        return launch_c8to1<false>(C8Call{a.src.p[0], a.wgt, a.bias, a.out}, nullptr, D, h, w, relu, st, bt);
+    return launch_conv(a, b, cin, cout, D, h, w, sz, sxy, relu, st, bt);
+}
+// the same, transposed
+static int deconv3d_k3_run(const Deconv3dCall& a, const Deconv3dCall* b, int cin, int cout, int D, int h, int w, int sz, int relu,
+                           const C3Samples* bt, effi_stream_t stream) {
+    hipStream_t st = effi_s(stream);
+    if (route_c8to1(cin, cout, sz, a.skip)) {
+        const C8Call ca{a.in, a.wgt, a.bias, a.out}, cb = b ? C8Call{b->in, b->wgt, b->bias, b->out} : ca;
+        return launch_c8to1<true>(ca, b ? &cb : nullptr, D, h, w, relu, st, bt);
     }
-    const bool c8 = (cout % 8 == 0);
-    if (!c8 && cout != 1) return EFFI_ERR_UNSUPPORTED;
-    if (sz == 1 && sxy == 1)
-        return c8 ? launch_conv<8, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp)
-                  : launch_conv<1, 1, 1>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
-    if (!c8) return EFFI_ERR_UNSUPPORTED;
-    if (sz == 2 && sxy == 2) return launch_conv<8, 2, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
-    if (sz == 1 && sxy == 2) return launch_conv<8, 1, 2>(s, cin, weight, bias, cout, D, h, w, relu, skip, out, st, bt, n_smp);
-    return EFFI_ERR_UNSUPPORTED;
+    return launch_deconv(a, b, cin, cout, D, h, w, sz, relu, st, bt);
+}
+
+static int conv3d_k3_impl(const float* const* srcs, const int* src_channels, int n_src, const float* weight, const float* bias, int cout,
+                          int D, int h, int w, int sz, int sxy, int relu, const float* skip, float* out, const C3Samples* bt,
+                          effi_stream_t stream) {
+    Conv3dCall c;
+    int cin;
+    if (cout < 1) return EFFI_ERR_BADARG;
+    if (const int rc = fill_conv(c, cin, srcs, src_channels, n_src, weight, bias, skip, out, D, h, w)) return rc;
+    return conv3d_k3_run(c, nullptr, cin, cout, D, h, w, sz, sxy, relu, bt, stream);
 }
 
 extern "C" int effi_conv3d_k3_f32(const float* const* srcs, const int* src_channels, int n_src, const float* weight,
                                   const float* bias, int cout, int D, int h, int w, int sz, int sxy, int relu,
                                   const float* skip, float* out, effi_stream_t stream) {
-    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, nullptr, 1, stream);
+    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, nullptr, stream);
 }
 
 // n_smp == 1: the single-sample launch itself
@@ -882,113 +932,54 @@ extern "C" int effi_conv3d_k3_f32_batch(const float* const* srcs, const int* src
                                         const float* bias, int cout, int D, int h, int w, int sz, int sxy, int relu,
                                         const float* skip, float* out, int n_smp, const long* src_sstride, long skip_sstride,
                                         long out_sstride, effi_stream_t stream) {
-    if (n_smp < 1 || n_smp > 65535 || !src_sstride || skip_sstride < 0 || out_sstride < 0 || n_src < 1 || n_src > EFFI_MAX_SRC)
-        return EFFI_ERR_BADARG;
-    C3Batch bt;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        bt.src[i] = (i < n_src) ? src_sstride[i] : 0;
-        if (bt.src[i] < 0) return EFFI_ERR_BADARG;
-    }
-    bt.skip = skip_sstride;
-    bt.out = out_sstride;
-    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, n_smp > 1 ? &bt : nullptr, n_smp,
-                          stream);
+    C3Samples b;
+    if (const int rc = fill_samples(b, n_smp, src_sstride, n_src, skip_sstride, out_sstride)) return rc;
+    return conv3d_k3_impl(srcs, src_channels, n_src, weight, bias, cout, D, h, w, sz, sxy, relu, skip, out, n_smp > 1 ? &b : nullptr, stream);
 }
 
-// n_smp > 1: grid.y = sample.  The channel split of the stride-2 form follows the workgroups of all samples (an output's FMA order does
-// not depend on it).
+// (sample batch: the channel split of the stride-2 form follows the workgroups of all samples; an output's FMA order does not depend on it)
 static int deconv3d_k3_impl(const float* in, int cin, const float* weight, const float* bias, int cout, int D, int h, int w, int sz,
-                            int relu, const float* skip, float* out, int n_smp, long in_ss, long skip_ss, long out_ss,
-                            effi_stream_t stream) {
-    if (!in || !weight || !out || cin < 1 || cout < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    hipStream_t st = effi_s(stream);
-    const int tiles = effi_cdiv(w, TX) * effi_cdiv(h, TY);
-#define EFFI_DK(CT, SZV, GX)                                                                                                          \
-    do {                                                                                                                              \
-        if (n_smp > 1)                                                                                                                \
-            hipLaunchKernelGGL((deconv3d_k3_batch_kernel<CT, SZV>), dim3(GX, n_smp), dim3(256), 0, st, in, in_ss, cin, weight, bias,   \
-                               cout, D, h, w, relu, skip, skip_ss, out, out_ss);                                                      \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((deconv3d_k3_kernel<CT, SZV>), dim3(GX), dim3(256), 0, st, in, cin, weight, bias, cout, D, h, w, relu,  \
-                               skip, out);                                                                                            \
-    } while (0)
-    if (sz == 2 && cout % 8 == 0) {
-        if (effi_pick_deconv_k3(cout, h, w, D, n_smp).planes == 8) EFFI_DK(8, 2, tiles * D * (cout / 8));
-        else EFFI_DK(4, 2, tiles * D * (cout / 4));   // low-resolution level: split the output channels finer so the grid covers the chip
-    } else if (sz == 1 && cout == 1 && cin == 8 && !skip && c3_lean(1)) {
-        const C8Call c{in, weight, bias, out};
-        return launch_c8to1<true>(c, nullptr, D, h, w, relu, st, n_smp, in_ss, out_ss);
-    } else if (sz == 1 && cout == 1) {
-        EFFI_DK(1, 1, tiles * effi_cdiv(D, 4));
-    } else {
-        return EFFI_ERR_UNSUPPORTED;
-    }
-#undef EFFI_DK
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+                            int relu, const float* skip, float* out, const C3Samples* bt, effi_stream_t stream) {
+    Deconv3dCall c;
+    if (cout < 1) return EFFI_ERR_BADARG;
+    if (const int rc = fill_deconv(c, in, weight, bias, skip, out, cin, D, h, w)) return rc;
+    return deconv3d_k3_run(c, nullptr, cin, cout, D, h, w, sz, relu, bt, stream);
 }
 
 extern "C" int effi_deconv3d_k3_f32(const float* in, int cin, const float* weight, const float* bias, int cout, int D,
                                     int h, int w, int sz, int relu, const float* skip, float* out,
                                     effi_stream_t stream) {
-    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, 1, 0, 0, 0, stream);
+    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, nullptr, stream);
 }
 
 // n_smp == 1: the single-sample launch itself
 extern "C" int effi_deconv3d_k3_f32_batch(const float* in, int cin, const float* weight, const float* bias, int cout, int D, int h,
                                           int w, int sz, int relu, const float* skip, float* out, int n_smp, long in_sstride,
                                           long skip_sstride, long out_sstride, effi_stream_t stream) {
-    if (n_smp < 1 || n_smp > 65535 || in_sstride < 0 || skip_sstride < 0 || out_sstride < 0) return EFFI_ERR_BADARG;
-    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, n_smp, in_sstride, skip_sstride, out_sstride, stream);
+    C3Samples b;
+    if (const int rc = fill_samples(b, n_smp, &in_sstride, 1, skip_sstride, out_sstride)) return rc;
+    return deconv3d_k3_impl(in, cin, weight, bias, cout, D, h, w, sz, relu, skip, out, n_smp > 1 ? &b : nullptr, stream);
 }
 
-// ---- pair launches (see conv3d_k3_pair_kernel) ------------------------------------------------------------------------
-namespace {
-template <int SXY, int ZPT>
-int launch_conv_pair(const Conv3dCall& a, const Conv3dCall& b, int cin, int D, int h, int w, int relu, hipStream_t st) {
-    const int ho = (h - 1) / SXY + 1, wo = (w - 1) / SXY + 1;
-    const dim3 grid(effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(D, ZPT), 2);
-    hipLaunchKernelGGL((conv3d_k3_pair_kernel<8, 1, SXY, ZPT>), grid, dim3(256), 0, st, a, b, cin, 8, D, h, w, D, ho, wo, relu);
-    return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
-}
-}  // namespace
-
+// ---- pair launches (see conv3d_k3_pair_kernel): two calls of one shape, no skip tensor ----------------------------------
 extern "C" int effi_conv3d_k3_pair_f32(const float* in_a, const float* weight_a, const float* bias_a, float* out_a,
                                        const float* in_b, const float* weight_b, const float* bias_b, float* out_b, int cin,
                                        int cout, int D, int h, int w, int sxy, int relu, effi_stream_t stream) {
-    if (!in_a || !weight_a || !out_a || !in_b || !weight_b || !out_b || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    if (cout != 8 || (sxy != 1 && sxy != 2)) return EFFI_ERR_UNSUPPORTED;
     Conv3dCall a, b;
-    for (int i = 0; i < EFFI_MAX_SRC; ++i) {
-        a.src.p[i] = (i == 0) ? in_a : nullptr;
-        b.src.p[i] = (i == 0) ? in_b : nullptr;
-        a.src.ch[i] = b.src.ch[i] = (i == 0) ? cin : 0;
-    }
-    a.wgt = weight_a; a.bias = bias_a; a.skip = nullptr; a.out = out_a;
-    b.wgt = weight_b; b.bias = bias_b; b.skip = nullptr; b.out = out_b;
-    hipStream_t st = effi_s(stream);
-    if (cin == 1 && c3_lean(0)) {
-        const C1Call ca{in_a, weight_a, bias_a, out_a}, cb{in_b, weight_b, bias_b, out_b};
-        return launch_c1to8(ca, &cb, D, h, w, sxy, relu, st);
-    }
-    const int ho = (h - 1) / sxy + 1, wo = (w - 1) / sxy + 1;
-    const bool big = 2L * effi_cdiv(wo, TX) * effi_cdiv(ho, TY) * effi_cdiv(D, 4) >= 384;     // as launch_conv, for both grids
-    if (sxy == 1) return big ? launch_conv_pair<1, 4>(a, b, cin, D, h, w, relu, st) : launch_conv_pair<1, 1>(a, b, cin, D, h, w, relu, st);
-    return big ? launch_conv_pair<2, 4>(a, b, cin, D, h, w, relu, st) : launch_conv_pair<2, 1>(a, b, cin, D, h, w, relu, st);
+    int cin_a, cin_b;
+    if (fill_conv(a, cin_a, &in_a, &cin, 1, weight_a, bias_a, nullptr, out_a, D, h, w) ||
+        fill_conv(b, cin_b, &in_b, &cin, 1, weight_b, bias_b, nullptr, out_b, D, h, w))
+        return EFFI_ERR_BADARG;
+    if (cout != 8 || (sxy != 1 && sxy != 2)) return EFFI_ERR_UNSUPPORTED;
+    return conv3d_k3_run(a, &b, cin, cout, D, h, w, 1, sxy, relu, nullptr, stream);
 }
 
 extern "C" int effi_deconv3d_k3_pair_f32(const float* in_a, const float* weight_a, const float* bias_a, float* out_a,
                                          const float* in_b, const float* weight_b, const float* bias_b, float* out_b, int cin,
                                          int cout, int D, int h, int w, int sz, int relu, effi_stream_t stream) {
-    if (!in_a || !weight_a || !out_a || !in_b || !weight_b || !out_b || cin < 1 || D < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
+    Deconv3dCall a, b;
+    if (fill_deconv(a, in_a, weight_a, bias_a, nullptr, out_a, cin, D, h, w) || fill_deconv(b, in_b, weight_b, bias_b, nullptr, out_b, cin, D, h, w))
+        return EFFI_ERR_BADARG;
     if (sz != 1 || cout != 1) return EFFI_ERR_UNSUPPORTED;
-    if (cin == 8 && c3_lean(1)) {
-        const C8Call ca{in_a, weight_a, bias_a, out_a}, cb{in_b, weight_b, bias_b, out_b};
-        return launch_c8to1<true>(ca, &cb, D, h, w, relu, effi_s(stream));
-    }
-    const Deconv3dCall a{in_a, weight_a, bias_a, nullptr, out_a}, b{in_b, weight_b, bias_b, nullptr, out_b};
-    const dim3 grid(effi_cdiv(w, TX) * effi_cdiv(h, TY) * effi_cdiv(D, 4), 2);
-    hipLaunchKernelGGL((deconv3d_k3_pair_kernel<1, 1>), grid, dim3(256), 0, effi_s(stream), a, b, cin, cout, D, h, w, relu);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return deconv3d_k3_run(a, &b, cin, cout, D, h, w, sz, relu, nullptr, stream);
 }

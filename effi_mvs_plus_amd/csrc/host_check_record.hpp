@@ -1,4 +1,4 @@
-// The launch recorder of the stand-alone host checks (conv_host_check.cpp, warp_host_check.cpp).  Include it BEFORE the .hip files
+// The launch recorder of the stand-alone host checks (conv_host_check.cpp, warp_host_check.cpp, vol_host_check.cpp).  Include it BEFORE the .hip files
 // under test: from here on hipLaunchKernelGGL appends a record to g_rec instead of launching -- kernel instantiation, grid, block and
 // each by-value argument, field by field -- and the error queries answer hipSuccess.  The stand-ins for what api.hip gives the library
 // (zero page, option table) are here too.  A program adds a show_one overload per argument struct of its kernels, in the namespace of
@@ -79,7 +79,8 @@ static void ptr(const char* n, const void* p) {
 #define FI(s, f) ((s).f != 0 ? put(" " #f "=%ld", (long)(s).f) : (void)0)
 #define FP(s, f) ptr(#f, (s).f)
 template <class T> static void show(const T& v) {
-    if constexpr (std::is_pointer_v<T>) v ? ptr("ptr", v) : put(" null");
+    if constexpr (std::is_null_pointer_v<T>) put(" null");      // (a literal nullptr among the arguments)
+    else if constexpr (std::is_pointer_v<T>) v ? ptr("ptr", v) : put(" null");
     else if constexpr (std::is_integral_v<T>) put(" %ld", (long)v);
     else show_one(v);
 }

@@ -2,10 +2,13 @@
 // of the tuning options go in, the tile form comes out.  Every launcher calls the pick function of its rule and launches what it
 // returns; effi_launch_form (api.hip) calls the same functions without launching anything, so that a test can assert the form a case
 // is written for (tests/conv_cases.py: FORMS) and sweep the forms the workloads take.  There is no second copy of a rule.
+// The rules of the vector-ALU 3-D kernels (conv3d.hip) are among them: planes per thread of the 1 -> 8 / 8 -> 1 kernels and of the
+// general kernel (effi_pick_c3_planes, effi_pick_c3_zpt), output channels per thread of the transposed one, the element limits of
+// the two dedicated kernels; csrc/vol_host_check.cpp pins them through the entries.
 // The rules of the warp and correlation kernels (warpcorr.hip) are at the end: which kernel a stage-1 ("views") call and a call of
 // the dynamic stage take, with the size of their LDS window; csrc/warp_host_check.cpp pins them through the entries.
-// In front of the rules, the two helpers every launcher dispatches with: effi_switch (a run-time value as a template argument) and
-// effi_launch.
+// In front of the rules, the helpers every launcher dispatches with: effi_switch (a run-time value as a template argument) and
+// effi_launch (effi_launch_lds: with dynamic LDS).
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -25,9 +28,13 @@ template <int... Vs, class F>
 static int effi_switch_nt(long v, F&& f) { return effi_switch_or<Vs...>(EFFI_ERR_UNSUPPORTED, v, f); }
 
 template <auto KERNEL, class... Args>
-static int effi_launch(dim3 grid, int threads, hipStream_t st, const Args&... args) {
-    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, st, args...);
+static int effi_launch_lds(dim3 grid, int threads, size_t dynamic_lds, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), dynamic_lds, st, args...);
     return hipPeekAtLastError() == hipSuccess ? EFFI_OK : EFFI_ERR_LAUNCH;
+}
+template <auto KERNEL, class... Args>
+static int effi_launch(dim3 grid, int threads, hipStream_t st, const Args&... args) {
+    return effi_launch_lds<KERNEL>(grid, threads, 0, st, args...);
 }
 
 #ifndef EFFI_C3_TX
@@ -201,6 +208,24 @@ static inline EffiForm effi_pick_c3_planes(int h, int w, int D, long ncall) {
     const long tiles = (long)effi_cdiv(w, EFFI_C3_TX) * effi_cdiv(h, EFFI_C3_TY);
     return EffiForm{1, EFFI_C3_TX, 4, tiles * effi_cdiv(D, 8) * ncall >= 512 ? 8 : 4, 0};
 }
+
+// Both kernels address their input with 32-bit byte offsets: fewer than 2^29 elements in the input tensor (D x h x w: the INPUT volume)
+static inline bool effi_c1to8_fits32(int D, int h, int w) { return (long)D * h * w < (1L << 29); }
+static inline bool effi_c8to1_fits32(int D, int h, int w) { return 8L * D * h * w < (1L << 29); }
+
+// General kernel, stride (sz, sxy, sxy): output planes per thread.  4 (2 with stride 2 in z and xy) amortise the z halo of the LDS
+// tile; low-resolution layers fall back to 1 so that the grid still has >= 2 workgroups per CU (384 workgroups of the larger form).
+// ho, wo, Do: the OUTPUT volume; cout_tiles: groups of output channels a workgroup owns; ncall: the two calls of a pair or the
+// samples of a batch (an output's FMA order does not depend on the planes per thread, so the rule counts all their workgroups).
+constexpr int effi_c3_zbig(int sz, int sxy) { return (sxy == 1 || sz == 1) ? 4 : 2; }
+static inline int effi_pick_c3_zpt(int sz, int sxy, int ho, int wo, int Do, int cout_tiles, long ncall) {
+    const int zbig = effi_c3_zbig(sz, sxy);
+    const long blocks = (long)effi_cdiv(wo, EFFI_C3_TX) * effi_cdiv(ho, EFFI_C3_TY) * effi_cdiv(Do, zbig) * cout_tiles * ncall;
+    return blocks >= 384 ? zbig : 1;
+}
+// its id in effi_launch_form (beside EFFI_LF_* of include/effi_mvs_hip.h, which stays as it is): nt = cout_tiles, h, w, planes = the
+// output volume, count = ncall, EFFI_LF_FLAG_S2 = stride (2, 2, 2); form.planes = the planes per thread
+constexpr int EFFI_LF_C3_ZPT = 12;
 
 // transposed convolution, stride 2, cout % 8 == 0: 8 output channels per thread, 4 on the low-resolution level (the output channels
 // split finer so that the grid covers the chip)

@@ -5,6 +5,7 @@
 // reference's separate torch ops; fused multiply-adds are written explicitly where wanted.
 #include <cstdint>
 #include "common.hpp"
+#include "launch_form.hpp"          // (effi_switch*, effi_launch: the dispatch of the host section)
 
 namespace {
 
@@ -560,32 +561,33 @@ __global__ void convex_upsample2x_kernel(const float* __restrict__ inv, const fl
 extern "C" int effi_planar_to_nhwc_f32(const float* const* srcs, float* const* dsts, int n, int C, int HW,
                                        effi_stream_t stream) {
     if (!srcs || !dsts || n < 1 || n > EFFI_MAX_VIEWS + 1 || C < 1 || C > 128 || HW < 1) return EFFI_ERR_BADARG;
-    EffiPtrList s;
-    EffiOutList d;
+    EffiPtrList s{};                         // (the slots past n and the view table stay null)
+    EffiOutList d{};
     for (int i = 0; i < n; ++i) {
         if (!srcs[i] || !dsts[i]) return EFFI_ERR_BADARG;
         s.p[i] = srcs[i];
         d.p[i] = dsts[i];
     }
-    hipLaunchKernelGGL(planar_to_nhwc_kernel, dim3(effi_cdiv(HW, 64), n), dim3(TPB), (size_t)C * 65 * sizeof(float),
-                       effi_s(stream), s, d, C, HW);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch_lds<planar_to_nhwc_kernel>(dim3(effi_cdiv(HW, 64), n), TPB, (size_t)C * 65 * sizeof(float), effi_s(stream), s, d, C, HW);
 }
+
+// every pointer on a 16-byte boundary (float4 / split-resident accesses)
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+// a split-resident map of an h x w image: a zero row / column on each side at least (effi_sr_geometry), and the 16-byte units of
+// ``planes`` planes that no producer writes (sr_clear_border_unit)
+static bool sr_geometry_ok(int h, int w, int hp, int wp) { return hp >= h + 2 && wp >= w + 2; }
+static long sr_border_units(long planes, int h, int w, int hp, int wp) { return planes * ((long)(hp - h) * wp + (long)h * (wp - w)); }
 
 extern "C" int effi_split_tanh_relu_f32(const float* ctx, int hd, int cd, int hw, float* hidden, float* inp,
                                         effi_stream_t stream) {
     if (!ctx || !hidden || !inp || hd < 1 || cd < 1 || hw < 1) return EFFI_ERR_BADARG;
     const long n = (long)(hd + cd) * hw;
-    if ((hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(ctx) | reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(inp)) & 15) == 0)
-        hipLaunchKernelGGL(split_tanh_relu4_kernel, dim3(effi_cdiv(n / 4, TPB)), dim3(TPB), 0, effi_s(stream),
-                           reinterpret_cast<const float4*>(ctx), (long)hd * hw / 4, n / 4, reinterpret_cast<float4*>(hidden),
-                           reinterpret_cast<float4*>(inp));
-    else
-        hipLaunchKernelGGL(split_tanh_relu_kernel, dim3(min(effi_cdiv(n, TPB), 4096)), dim3(TPB), 0, effi_s(stream),
-                           ctx, hd, cd, hw, hidden, inp);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    if ((hw & 3) == 0 && aligned16(ctx, hidden, inp))
+        return effi_launch<split_tanh_relu4_kernel>(dim3(effi_cdiv(n / 4, TPB)), TPB, effi_s(stream), reinterpret_cast<const float4*>(ctx),
+                                                    (long)hd * hw / 4, n / 4, reinterpret_cast<float4*>(hidden), reinterpret_cast<float4*>(inp));
+    return effi_launch<split_tanh_relu_kernel>(dim3(min(effi_cdiv(n, TPB), 4096)), TPB, effi_s(stream), ctx, hd, cd, hw, hidden, inp);
 }
 
 extern "C" int effi_split_tanh_relu_stages_f32(const float* const* ctx, const int* hd, const int* cd, const int* hw,
@@ -606,40 +608,27 @@ extern "C" int effi_split_tanh_relu_stages_f32(const float* const* ctx, const in
     a.first[4] = blocks;
     a.vec4 = 1;
     for (int k = 0; k < n_stages; ++k)
-        if ((a.nh[k] & 3) || (a.n[k] & 3) ||
-            ((reinterpret_cast<uintptr_t>(ctx[k]) | reinterpret_cast<uintptr_t>(hidden[k]) | reinterpret_cast<uintptr_t>(inp[k])) & 15))
-            a.vec4 = 0;
-    hipLaunchKernelGGL(split_tanh_relu_stages_kernel, dim3(blocks), dim3(TPB), 0, effi_s(stream), a);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+        if ((a.nh[k] & 3) || (a.n[k] & 3) || !aligned16(ctx[k], hidden[k], inp[k])) a.vec4 = 0;
+    return effi_launch<split_tanh_relu_stages_kernel>(dim3(blocks), TPB, effi_s(stream), a);
 }
 
 extern "C" int effi_depth_to_inv_f32(const float* depth, const float* disp_range, int n_range, int n, float* inv,
                                      effi_stream_t stream) {
     if (!depth || !disp_range || !inv || n_range < 2 || n < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(depth_to_inv_kernel, dim3(min(effi_cdiv(n, TPB), 4096)), dim3(TPB), 0, effi_s(stream),
-                       depth, disp_range, n_range, n, inv);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<depth_to_inv_kernel>(dim3(min(effi_cdiv(n, TPB), 4096)), TPB, effi_s(stream), depth, disp_range, n_range, n, inv);
 }
 
 extern "C" int effi_stage1_hypotheses_f32(const float* disp_range, int n_range, int D, float* depths,
                                           float* intervals, effi_stream_t stream) {
     if (!disp_range || !depths || !intervals || n_range < 2 || D < 2) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(stage1_hypotheses_kernel, dim3(1), dim3(128), 0, effi_s(stream), disp_range, n_range, D,
-                       depths, intervals);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<stage1_hypotheses_kernel>(dim3(1), 128, effi_s(stream), disp_range, n_range, D, depths, intervals);
 }
 
 extern "C" int effi_upsample_nearest_f32(const float* in, int C, int h, int w, int f, float* out,
                                          effi_stream_t stream) {
     if (!in || !out || C < 1 || h < 1 || w < 1 || f < 1) return EFFI_ERR_BADARG;
     const long n = (long)C * h * f * w * f;
-    hipLaunchKernelGGL(upsample_nearest_kernel, dim3(min(effi_cdiv(n, TPB), 8192)), dim3(TPB), 0, effi_s(stream),
-                       in, C, h, w, f, out);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<upsample_nearest_kernel>(dim3(min(effi_cdiv(n, TPB), 8192)), TPB, effi_s(stream), in, C, h, w, f, out);
 }
 
 extern "C" int effi_head_update_f32(const float* partial9, const float* bias2, const float* inv_depth, const float* disp_range,
@@ -648,33 +637,32 @@ extern "C" int effi_head_update_f32(const float* partial9, const float* bias2, c
         return EFFI_ERR_BADARG;
     if (w & 3) return EFFI_ERR_UNSUPPORTED;
     const long n = (long)h * (w >> 2);
-    hipLaunchKernelGGL(head_update_kernel, dim3((unsigned)effi_cdiv(n, TPB)), dim3(TPB), 0, effi_s(stream), partial9, bias2, inv_depth,
-                       disp_range, n_range, h, w, out_inv, out_depth);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<head_update_kernel>(dim3((unsigned)effi_cdiv(n, TPB)), TPB, effi_s(stream), partial9, bias2, inv_depth, disp_range,
+                                           n_range, h, w, out_inv, out_depth);
+}
+
+// one sample (n_smp == 1: the strides unused) or a batch, grid.z = sample
+static int view_aggregate_launch(const float* sim_views, const float* weights, int S, int D, int hw, float* out, effi_stream_t stream,
+                                 int n_smp = 1, long sim_ss = 0, long weights_ss = 0, long out_ss = 0) {
+    if (!sim_views || !out || S < 1 || S > EFFI_MAX_VIEWS || D < 1 || hw < 1) return EFFI_ERR_BADARG;
+    const dim3 grid(effi_cdiv(hw, TPB), effi_cdiv(D, 8), n_smp);
+    if (n_smp > 1)
+        return effi_launch<view_aggregate_batch_kernel>(grid, TPB, effi_s(stream), sim_views, sim_ss, weights, weights_ss, S, D, hw, out, out_ss);
+    return effi_launch<view_aggregate_kernel>(grid, TPB, effi_s(stream), sim_views, weights, S, D, hw, out);
 }
 
 extern "C" int effi_view_aggregate_f32(const float* sim_views, const float* weights, int S, int D, int hw,
                                        float* out, effi_stream_t stream) {
-    if (!sim_views || !out || S < 1 || S > EFFI_MAX_VIEWS || D < 1 || hw < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(view_aggregate_kernel, dim3(effi_cdiv(hw, TPB), effi_cdiv(D, 8)), dim3(TPB), 0, effi_s(stream),
-                       sim_views, weights, S, D, hw, out);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return view_aggregate_launch(sim_views, weights, S, D, hw, out, stream);
 }
 
 extern "C" int effi_view_aggregate_f32_batch(const float* sim_views, const float* weights, int S, int D, int hw, float* out, int n_smp,
                                              long sim_sstride, long weights_sstride, long out_sstride, effi_stream_t stream) {
     if (n_smp < 1 || n_smp > 65535 || sim_sstride < 0 || weights_sstride < 0 || out_sstride < 0) return EFFI_ERR_BADARG;
-    if (n_smp == 1) return effi_view_aggregate_f32(sim_views, weights, S, D, hw, out, stream);
-    if (!sim_views || !out || S < 1 || S > EFFI_MAX_VIEWS || D < 1 || hw < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(view_aggregate_batch_kernel, dim3(effi_cdiv(hw, TPB), effi_cdiv(D, 8), n_smp), dim3(TPB), 0, effi_s(stream),
-                       sim_views, sim_sstride, weights, weights_sstride, S, D, hw, out, out_sstride);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return view_aggregate_launch(sim_views, weights, S, D, hw, out, stream, n_smp, sim_sstride, weights_sstride, out_sstride);
 }
 
-// bt == nullptr: the single-sample launch
+// bt == nullptr: the single-sample launch.  The register kernel for the D of the cascades, the generic one for any other.
 static int softmax_regress_conf_launch(const float* logits, const float* depth, long dds, long dps, int D, int hw, float* out_depth,
                                        float* out_conf, const float* disp_range, int n_range, float* out_depth_inv,
                                        float* out_conf_up, int w, int f, effi_stream_t stream, const SoftmaxBatch* bt = nullptr,
@@ -682,47 +670,24 @@ static int softmax_regress_conf_launch(const float* logits, const float* depth, 
     if (!logits || !depth || !out_depth || !out_conf || D < 1 || hw < 1) return EFFI_ERR_BADARG;
     if (out_depth_inv && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
     if (out_conf_up && (w < 1 || f < 1 || hw % w != 0)) return EFFI_ERR_BADARG;
-    if (out_conf_up && f == 4 && (reinterpret_cast<uintptr_t>(out_conf_up) & 15)) return EFFI_ERR_BADARG;
+    if (out_conf_up && f == 4 && (!aligned16(out_conf_up) || (bt && (bt->out_conf_up & 3)))) return EFFI_ERR_BADARG;   // 16-byte stores, in every sample
     hipStream_t st = effi_s(stream);
-    if (bt) {
-        if (out_conf_up && f == 4 && (bt->out_conf_up & 3)) return EFFI_ERR_BADARG;           // 16-byte stores in every sample
-        const dim3 bgrid(effi_cdiv(hw, 64), n_smp);
-#define EFFI_SMB(DT)                                                                                                              \
-    hipLaunchKernelGGL(softmax_regress_conf_reg_batch_kernel<DT>, bgrid, dim3(64), 0, st, logits, depth, dds, dps, hw, out_depth, \
-                       out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f, *bt)
-        switch (D) {
-            case 8: EFFI_SMB(8); break;
-            case 16: EFFI_SMB(16); break;
-            case 32: EFFI_SMB(32); break;
-            case 48: EFFI_SMB(48); break;
-            case 64: EFFI_SMB(64); break;
-            case 96: EFFI_SMB(96); break;
-            default:
-                hipLaunchKernelGGL(softmax_regress_conf_batch_kernel, bgrid, dim3(64), 0, st, logits, depth, dds, dps, D, hw, out_depth,
-                                   out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f, *bt);
-        }
-#undef EFFI_SMB
-        EFFI_LAUNCH_CHECK();
-        return EFFI_OK;
-    }
-    const dim3 grid(effi_cdiv(hw, 64));
-#define EFFI_SM(DT)                                                                                                      \
-    hipLaunchKernelGGL(softmax_regress_conf_reg_kernel<DT>, grid, dim3(64), 0, st, logits, depth, dds, dps, hw, out_depth, \
-                       out_conf, disp_range, n_range, out_depth_inv, out_conf_up, w, f)
-    switch (D) {
-        case 8: EFFI_SM(8); break;
-        case 16: EFFI_SM(16); break;
-        case 32: EFFI_SM(32); break;
-        case 48: EFFI_SM(48); break;
-        case 64: EFFI_SM(64); break;
-        case 96: EFFI_SM(96); break;
-        default:
-            hipLaunchKernelGGL(softmax_regress_conf_kernel, grid, dim3(64), 0, st, logits, depth, dds, dps, D, hw, out_depth, out_conf,
-                               disp_range, n_range, out_depth_inv, out_conf_up, w, f);
-    }
-#undef EFFI_SM
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    const dim3 grid(effi_cdiv(hw, 64), bt ? n_smp : 1);
+    bool reg = false;                           // D has a register kernel
+    const int rc = effi_switch_or<8, 16, 32, 48, 64, 96>(EFFI_OK, D, [&](auto DT) {
+        reg = true;
+        if (bt)
+            return effi_launch<softmax_regress_conf_reg_batch_kernel<DT()>>(grid, 64, st, logits, depth, dds, dps, hw, out_depth, out_conf,
+                                                                            disp_range, n_range, out_depth_inv, out_conf_up, w, f, *bt);
+        return effi_launch<softmax_regress_conf_reg_kernel<DT()>>(grid, 64, st, logits, depth, dds, dps, hw, out_depth, out_conf, disp_range,
+                                                                  n_range, out_depth_inv, out_conf_up, w, f);
+    });
+    if (reg) return rc;
+    if (bt)
+        return effi_launch<softmax_regress_conf_batch_kernel>(grid, 64, st, logits, depth, dds, dps, D, hw, out_depth, out_conf, disp_range,
+                                                              n_range, out_depth_inv, out_conf_up, w, f, *bt);
+    return effi_launch<softmax_regress_conf_kernel>(grid, 64, st, logits, depth, dds, dps, D, hw, out_depth, out_conf, disp_range, n_range,
+                                                    out_depth_inv, out_conf_up, w, f);
 }
 
 extern "C" int effi_softmax_regress_conf_f32(const float* logits, const float* depth, long dds, long dps, int D,
@@ -780,29 +745,42 @@ extern "C" int effi_vol_lookup1d_f32(const float* vol, long vds, long vps, int D
                                      long qys, long qxs, int nq, const float* dmin, const float* dmax, long rps,
                                      int h, int w, float* out, effi_stream_t stream) {
     if (!vol || !query || !dmin || !dmax || !out || Dp < 2 || nq < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(vol_lookup1d_kernel, dim3(effi_cdiv((long)h * w, TPB)), dim3(TPB), 0, effi_s(stream), vol, vds,
-                       vps, Dp, query, qds, qys, qxs, nq, dmin, dmax, rps, h, w, out, nullptr, nullptr);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    const float* const no_vol = nullptr;
+    float* const no_out = nullptr;
+    return effi_launch<vol_lookup1d_kernel>(dim3(effi_cdiv((long)h * w, TPB)), TPB, effi_s(stream), vol, vds, vps, Dp, query, qds, qys, qxs, nq,
+                                            dmin, dmax, rps, h, w, out, no_vol, no_out);
 }
 
 extern "C" int effi_bilinear_sampler1d_f32(const float* img, int N, int C, int W, const float* coords, long nq, float* out,
                                            float* mask, effi_stream_t stream) {
     if (!img || !coords || !out || N < 1 || C < 1 || W < 1 || nq < 1) return EFFI_ERR_BADARG;
     const long total = (long)N * nq;
-    hipLaunchKernelGGL(bilinear_sampler1d_kernel, dim3(effi_cdiv(total, TPB)), dim3(TPB), 0, effi_s(stream), img, C, W, coords, nq,
-                       total, out, mask);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<bilinear_sampler1d_kernel>(dim3(effi_cdiv(total, TPB)), TPB, effi_s(stream), img, C, W, coords, nq, total, out, mask);
 }
 
 extern "C" int effi_vol_lookup1d_pair_f32(const float* vol_a, const float* vol_b, long vds, long vps, int Dp, const float* query,
                                           long qds, long qys, long qxs, int nq, const float* dmin, const float* dmax, long rps,
                                           int h, int w, float* out_a, float* out_b, effi_stream_t stream) {
     if (!vol_a || !vol_b || !query || !dmin || !dmax || !out_a || !out_b || Dp < 2 || nq < 1 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(vol_lookup1d_kernel, dim3(effi_cdiv((long)h * w, TPB), 2), dim3(TPB), 0, effi_s(stream), vol_a, vds,
-                       vps, Dp, query, qds, qys, qxs, nq, dmin, dmax, rps, h, w, out_a, vol_b, out_b);
-    EFFI_LAUNCH_CHECK();
+    return effi_launch<vol_lookup1d_kernel>(dim3(effi_cdiv((long)h * w, TPB), 2), TPB, effi_s(stream), vol_a, vds, vps, Dp, query, qds, qys, qxs,
+                                            nq, dmin, dmax, rps, h, w, out_a, vol_b, out_b);
+}
+
+// The look-up block of the GetCost family (getcost, getcost_conv1x1, the encoder-input entries), validated in one place
+static bool lookup_ok(const float* inv_depth, const float* disp_range, int n_range, int input_is_depth, const float* interval,
+                      const float* cur_vol, int Dcur, const float* reg_vol, int Dreg, const float* dmin, const float* dmax, int h, int w) {
+    return inv_depth && interval && cur_vol && reg_vol && dmin && dmax && (input_is_depth || (disp_range && n_range >= 2)) && Dcur >= 2 &&
+           Dreg >= 2 && h >= 1 && w >= 1;
+}
+// ... and as the kernels that take GetcostConvArgs get it: the common prefix of the struct up to hw, and off32.  What an entry
+// launches beyond the look-up (weights, outputs) it assigns itself.
+static int fill_lookup(GetcostConvArgs& g, const float* inv_depth, const float* disp_range, int n_range, int input_is_depth,
+                       const float* interval, const float* cur_vol, long cds, long cps, int Dcur, const float* reg_vol, long rds, long rps,
+                       int Dreg, const float* dmin, const float* dmax, long range_ps, int h, int w) {
+    if (!lookup_ok(inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, Dcur, reg_vol, Dreg, dmin, dmax, h, w)) return EFFI_ERR_BADARG;
+    g = GetcostConvArgs{inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
+                        Dreg, dmin, dmax, range_ps, h * w};
+    g.off32 = effi_lookup_fits32((long)h * w, cps, Dcur, cds, rps, Dreg, rds);
     return EFFI_OK;
 }
 
@@ -811,14 +789,10 @@ extern "C" int effi_getcost_f32(const float* inv_depth, const float* disp_range,
                                 const float* cur_vol, long cds, long cps, int Dcur, const float* reg_vol, long rds,
                                 long rps, int Dreg, const float* dmin, const float* dmax, long range_ps, int nq, int h,
                                 int w, float* cost, effi_stream_t stream) {
-    if (!inv_depth || !interval || !cur_vol || !reg_vol || !dmin || !dmax || !cost) return EFFI_ERR_BADARG;
-    if (!input_is_depth && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
-    if ( Dcur < 2 || Dreg < 2 || nq < 2 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(getcost_kernel, dim3(effi_cdiv((long)h * w, TPB)), dim3(TPB), 0, effi_s(stream), inv_depth,
-                       disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg, dmin, dmax,
-                       range_ps, nq, h * w, cost);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    if (!cost || nq < 2 || !lookup_ok(inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, Dcur, reg_vol, Dreg, dmin, dmax, h, w))
+        return EFFI_ERR_BADARG;
+    return effi_launch<getcost_kernel>(dim3(effi_cdiv((long)h * w, TPB)), TPB, effi_s(stream), inv_depth, disp_range, n_range, input_is_depth,
+                                       interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg, dmin, dmax, range_ps, nq, h * w, cost);
 }
 
 extern "C" int effi_getcost_conv1x1_f32(const float* inv_depth, const float* disp_range, int n_range, int input_is_depth,
@@ -826,25 +800,15 @@ extern "C" int effi_getcost_conv1x1_f32(const float* inv_depth, const float* dis
                                         const float* reg_vol, long rds, long rps, int Dreg, const float* dmin,
                                         const float* dmax, long range_ps, int nq, int h, int w, const float* weight,
                                         const float* bias, int cout, int relu, float* out, effi_stream_t stream) {
-    if (!inv_depth || !interval || !cur_vol || !reg_vol || !dmin || !dmax || !weight || !bias || !out) return EFFI_ERR_BADARG;
-    if (!input_is_depth && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
-    if (Dcur < 2 || Dreg < 2 || h < 1 || w < 1 || cout < 8) return EFFI_ERR_BADARG;
+    GetcostConvArgs g;
+    if (!weight || !bias || !out || cout < 8) return EFFI_ERR_BADARG;
+    if (const int rc = fill_lookup(g, inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg,
+                                   dmin, dmax, range_ps, h, w))
+        return rc;
     if (cout % 8) return EFFI_ERR_UNSUPPORTED;
-    const dim3 grid(effi_cdiv((long)h * w, TPB));
+    g.weight = weight, g.bias = bias, g.cout = cout, g.relu = relu, g.out = out;
     hipStream_t st = effi_s(stream);
-    GetcostConvArgs g{inv_depth, disp_range, n_range, input_is_depth, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
-                      Dreg, dmin, dmax, range_ps, h * w, weight, bias, cout, relu, out};
-    g.off32 = effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds);
-#define EFFI_GC(NQ) hipLaunchKernelGGL(getcost_conv1x1_kernel<NQ>, grid, dim3(TPB), 0, st, g)
-    switch (nq) {
-        case 2: EFFI_GC(2); break;
-        case 3: EFFI_GC(3); break;
-        case 4: EFFI_GC(4); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-#undef EFFI_GC
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_switch_nt<2, 3, 4>(nq, [&](auto NQ) { return effi_launch<getcost_conv1x1_kernel<NQ()>>(dim3(effi_cdiv(g.hw, TPB)), TPB, st, g); });
 }
 
 static int encoder_inputs_launch(bool x3, const float* inv_depth, const float* disp_range, int n_range, const float* interval,
@@ -854,33 +818,24 @@ static int encoder_inputs_launch(bool x3, const float* inv_depth, const float* d
                                  const float* bias_d1, int cout, float* out_c1, float* out_d1, effi_stream_t stream,
                                  void* sr_c1 = nullptr, void* sr_d1 = nullptr, int hp = 0, int wp = 0) {
     const bool sr = sr_c1 != nullptr;
-    if (!inv_depth || !interval || !cur_vol || !reg_vol || !dmin || !dmax || !weight_c1 || !bias_c1 || !weight_d1 || !bias_d1 ||
-        (!sr && (!out_c1 || !out_d1)) || !disp_range || n_range < 2)
-        return EFFI_ERR_BADARG;
-    if (sr && (!sr_d1 || !x3 || hp < h + 2 || wp < w + 2 || ((reinterpret_cast<uintptr_t>(sr_c1) | reinterpret_cast<uintptr_t>(sr_d1)) & 15)))
-        return EFFI_ERR_BADARG;
-    if (Dcur < 2 || Dreg < 2 || h < 1 || w < 1) return EFFI_ERR_BADARG;
-    if (nq != 3 || (cout != 16 && cout != 32 && cout != 48)) return EFFI_ERR_UNSUPPORTED;
+    GetcostConvArgs g;
+    if (!weight_c1 || !bias_c1 || !weight_d1 || !bias_d1 || (!sr && (!out_c1 || !out_d1))) return EFFI_ERR_BADARG;
+    if (sr && (!sr_d1 || !x3 || !sr_geometry_ok(h, w, hp, wp) || !aligned16(sr_c1, sr_d1))) return EFFI_ERR_BADARG;
+    if (const int rc = fill_lookup(g, inv_depth, disp_range, n_range, 0, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg, dmin, dmax,
+                                   range_ps, h, w))
+        return rc;
+    if (nq != 3) return EFFI_ERR_UNSUPPORTED;
+    g.weight = weight_c1, g.bias = bias_c1, g.cout = cout, g.relu = 1, g.out = out_c1;
+    g.out_sr = reinterpret_cast<unsigned short*>(sr_c1), g.out7_sr = reinterpret_cast<unsigned short*>(sr_d1);
+    g.w = w, g.sr_hp = hp, g.sr_wp = wp;
     const int gx = effi_cdiv(w, EFFI_C1K7_TX), gy = effi_cdiv(h, EFFI_C1K7_TY), n7 = gx * gy * (x3 ? 1 : cout / 16);
-    const dim3 grid(n7 + effi_cdiv((long)h * w, TPB));
+    const dim3 grid(n7 + effi_cdiv(g.hw, TPB));
     hipStream_t st = effi_s(stream);
-    const GetcostConvArgs g{inv_depth, disp_range, n_range, 0, interval, cur_vol, cds, cps, Dcur, reg_vol, rds, rps,
-                            Dreg, dmin, dmax, range_ps, h * w, weight_c1, bias_c1, cout, 1, out_c1,
-                            reinterpret_cast<unsigned short*>(sr_c1), reinterpret_cast<unsigned short*>(sr_d1), w, hp, wp,
-                            effi_vol_fits32((long)h * w, cps, Dcur, cds) && effi_vol_fits32((long)h * w, rps, Dreg, rds)};
-#define EFFI_EI(CO)                                                                                                                     \
-    do {                                                                                                                                \
-        if (x3) hipLaunchKernelGGL((encoder_inputs_kernel<3, CO, true>), grid, dim3(TPB), 0, st, g, weight_d1, bias_d1, h, w, out_d1, gx, gy, n7);  \
-        else hipLaunchKernelGGL((encoder_inputs_kernel<3, CO, false>), grid, dim3(TPB), 0, st, g, weight_d1, bias_d1, h, w, out_d1, gx, gy, n7);    \
-    } while (0)
-    switch (cout) {
-        case 16: EFFI_EI(16); break;
-        case 32: EFFI_EI(32); break;
-        default: EFFI_EI(48); break;
-    }
-#undef EFFI_EI
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_switch_nt<16, 32, 48>(cout, [&](auto CO) {
+        return effi_switch<0, 1>(x3, [&](auto X3) {
+            return effi_launch<encoder_inputs_kernel<3, CO(), X3() != 0>>(grid, TPB, st, g, weight_d1, bias_d1, h, w, out_d1, gx, gy, n7);
+        });
+    });
 }
 
 extern "C" int effi_encoder_inputs_f32(const float* inv_depth, const float* disp_range, int n_range, const float* interval,
@@ -1050,26 +1005,20 @@ extern "C" int effi_sr_clear_border(void* const* maps, const int* planes, const 
     int blocks = 0;
     for (int k = 0; k < 4; ++k) {
         const int j = k < n_groups ? k : 0;
-        if (!maps[j] || planes[j] < 1 || h[j] < 1 || w[j] < 1 || hp[j] < h[j] + 2 || wp[j] < w[j] + 2 || (reinterpret_cast<uintptr_t>(maps[j]) & 15))
-            return EFFI_ERR_BADARG;
+        if (!maps[j] || planes[j] < 1 || h[j] < 1 || w[j] < 1 || !sr_geometry_ok(h[j], w[j], hp[j], wp[j]) || !aligned16(maps[j])) return EFFI_ERR_BADARG;
         a.base[k] = reinterpret_cast<unsigned short*>(maps[j]);
         a.planes[k] = planes[j]; a.h[k] = h[j]; a.w[k] = w[j]; a.hp[k] = hp[j]; a.wp[k] = wp[j];
         a.first[k] = blocks;
-        if (k < n_groups) blocks += effi_cdiv((long)planes[j] * ((long)(hp[j] - h[j]) * wp[j] + (long)h[j] * (wp[j] - w[j])), TPB);
+        if (k < n_groups) blocks += effi_cdiv(sr_border_units(planes[j], h[j], w[j], hp[j], wp[j]), TPB);
     }
     a.first[4] = blocks;
-    hipLaunchKernelGGL(sr_clear_border_kernel, dim3(blocks), dim3(TPB), 0, effi_s(stream), a);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<sr_clear_border_kernel>(dim3(blocks), TPB, effi_s(stream), a);
 }
 
 extern "C" int effi_sr_from_planar_f32(const float* in, int channels, int h, int w, void* sr, int hp, int wp, effi_stream_t stream) {
-    if (!in || !sr || channels < 8 || (channels & 7) || h < 1 || w < 1 || hp < h + 2 || wp < w + 2 || (reinterpret_cast<uintptr_t>(sr) & 15))
-        return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(sr_from_planar_kernel, dim3(effi_cdiv((long)(channels >> 3) * h * w, TPB)), dim3(TPB), 0, effi_s(stream), in,
-                       channels, h, w, reinterpret_cast<unsigned short*>(sr), hp, wp);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    if (!in || !sr || channels < 8 || (channels & 7) || h < 1 || w < 1 || !sr_geometry_ok(h, w, hp, wp) || !aligned16(sr)) return EFFI_ERR_BADARG;
+    return effi_launch<sr_from_planar_kernel>(dim3(effi_cdiv((long)(channels >> 3) * h * w, TPB)), TPB, effi_s(stream), in, channels, h, w,
+                                              reinterpret_cast<unsigned short*>(sr), hp, wp);
 }
 
 static int split_tanh_relu_stages_sr_launch(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
@@ -1083,23 +1032,20 @@ static int split_tanh_relu_stages_sr_launch(const float* const* ctx, const int* 
         const int j = k < n_stages ? k : 0;
         if (!ctx[j] || !hidden[j] || !hidden_sr[j] || !inp[j] || hd[j] < 8 || cd[j] < 4 || h[j] < 1 || w[j] < 1) return EFFI_ERR_BADARG;
         if ((hd[j] & 7) || (cd[j] & 3)) return EFFI_ERR_UNSUPPORTED;
-        if (hp[j] < h[j] + 2 || wp[j] < w[j] + 2 || (reinterpret_cast<uintptr_t>(hidden_sr[j]) & 15)) return EFFI_ERR_BADARG;
+        if (!sr_geometry_ok(h[j], w[j], hp[j], wp[j]) || !aligned16(hidden_sr[j])) return EFFI_ERR_BADARG;
         a.ctx[k] = ctx[j]; a.hidden[k] = hidden[j]; a.inp[k] = inp[j]; a.hidden_sr[k] = reinterpret_cast<unsigned short*>(hidden_sr[j]);
         a.hd[k] = hd[j]; a.cd[k] = cd[j]; a.h[k] = h[j]; a.w[k] = w[j]; a.hp[k] = hp[j]; a.wp[k] = wp[j];
         a.q4[k] = hidden_q4 ? hidden_q4[j] : 0;
-        if (a.q4[k] && (reinterpret_cast<uintptr_t>(hidden[j]) & 15)) return EFFI_ERR_BADARG;
+        if (a.q4[k] && !aligned16(hidden[j])) return EFFI_ERR_BADARG;
         a.first[k] = blocks;
         a.nsplit[k] = effi_cdiv((long)h[j] * w[j] * ((hd[j] >> 3) + (cd[j] >> 2)), TPB);
         a.clear_base[k] = clear_base ? reinterpret_cast<unsigned short*>(clear_base[j]) : nullptr;
         a.clear_planes[k] = clear_base ? clear_planes[j] : 0;
-        if (clear_base && (!clear_base[j] || clear_planes[j] < 1 || (reinterpret_cast<uintptr_t>(clear_base[j]) & 15))) return EFFI_ERR_BADARG;
-        if (k < n_stages)
-            blocks += a.nsplit[k] + effi_cdiv((long)a.clear_planes[k] * ((long)(hp[j] - h[j]) * wp[j] + (long)h[j] * (wp[j] - w[j])), TPB);
+        if (clear_base && (!clear_base[j] || clear_planes[j] < 1 || !aligned16(clear_base[j]))) return EFFI_ERR_BADARG;
+        if (k < n_stages) blocks += a.nsplit[k] + effi_cdiv(sr_border_units(a.clear_planes[k], h[j], w[j], hp[j], wp[j]), TPB);
     }
     a.first[4] = blocks;
-    hipLaunchKernelGGL(split_tanh_relu_stages_sr_kernel, dim3(blocks), dim3(TPB), 0, effi_s(stream), a);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<split_tanh_relu_stages_sr_kernel>(dim3(blocks), TPB, effi_s(stream), a);
 }
 
 extern "C" int effi_split_tanh_relu_stages_sr_f32(const float* const* ctx, const int* hd, const int* cd, const int* h, const int* w,
@@ -1130,14 +1076,7 @@ extern "C" int effi_conv2d_c1k7_relu_bf16x3_f32(const float* in, const float* we
     if (!in || !weight || !bias || !out || h < 1 || w < 1) return EFFI_ERR_BADARG;
     const dim3 grid(effi_cdiv(w, EFFI_C1K7_TX), effi_cdiv(h, EFFI_C1K7_TY));
     hipStream_t st = effi_s(stream);
-    switch (cout) {
-        case 16: hipLaunchKernelGGL(conv2d_c1k7_relu_x3_kernel<16>, grid, dim3(TPB), 0, st, in, weight, bias, h, w, out); break;
-        case 32: hipLaunchKernelGGL(conv2d_c1k7_relu_x3_kernel<32>, grid, dim3(TPB), 0, st, in, weight, bias, h, w, out); break;
-        case 48: hipLaunchKernelGGL(conv2d_c1k7_relu_x3_kernel<48>, grid, dim3(TPB), 0, st, in, weight, bias, h, w, out); break;
-        default: return EFFI_ERR_UNSUPPORTED;
-    }
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_switch_nt<16, 32, 48>(cout, [&](auto CO) { return effi_launch<conv2d_c1k7_relu_x3_kernel<CO()>>(grid, TPB, st, in, weight, bias, h, w, out); });
 }
 
 extern "C" int effi_convex_upsample2x_f32(const float* inv_depth, const float* mask, const float* disp_range,
@@ -1146,8 +1085,6 @@ extern "C" int effi_convex_upsample2x_f32(const float* inv_depth, const float* m
     if (!inv_depth || !mask || (!out_inv && !out_depth) || h < 1 || w < 1) return EFFI_ERR_BADARG;
     if (out_depth && (!disp_range || n_range < 2)) return EFFI_ERR_BADARG;
     if (out_depth_inv && !out_depth) return EFFI_ERR_BADARG;
-    hipLaunchKernelGGL(convex_upsample2x_kernel, dim3(effi_cdiv((long)h * w, TPB)), dim3(TPB), 0, effi_s(stream),
-                       inv_depth, mask, disp_range, n_range, h, w, out_inv, out_depth, out_depth_inv);
-    EFFI_LAUNCH_CHECK();
-    return EFFI_OK;
+    return effi_launch<convex_upsample2x_kernel>(dim3(effi_cdiv((long)h * w, TPB)), TPB, effi_s(stream), inv_depth, mask, disp_range, n_range, h,
+                                                 w, out_inv, out_depth, out_depth_inv);
 }

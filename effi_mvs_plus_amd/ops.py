@@ -165,7 +165,7 @@ class options:
 
 # launcher ids and flags of effi_launch_form (include/effi_mvs_hip.h: EFFI_LF_*)
 LAUNCHERS = {"x3": 0, "x3_batch": 1, "x3_zb_batch": 2, "x3_pair": 3, "conv2d": 4, "planes3d": 5, "k5s2": 6, "s2_x3": 7, "roll": 8,
-             "deconv_x3": 9, "c3_planes": 10, "deconv_k3": 11}
+             "deconv_x3": 9, "c3_planes": 10, "deconv_k3": 11, "c3_zpt": 12}
 LaunchForm = collections.namedtuple("LaunchForm", "rows cols waves planes variant")
 
 
@@ -1765,23 +1765,55 @@ def _range_ptr(r, h, w):
     raise ValueError(f"depth range with {r.numel()} elements does not match {h}x{w}")
 
 
-def vol_lookup1d(vol, query, dmin, dmax, h, w):
-    """query [nq, h', w'] with (h', w') == (h, w) or exactly 2x (read nearest-downsampled)."""
-    vol, vds, vps, Dp = _vol_strides(vol, h, w)
-    _t(query, "query")
-    nq, qh, qw = query.shape
-    if (qh, qw) == (h, w):
-        qys, qxs = qw, 1
-    elif (qh // 2, qw // 2) == (h, w):
-        qys, qxs = 2 * qw, 2        # F.interpolate(nearest) to half size picks the even samples
-    else:
-        raise ValueError("query resolution must equal the volume's or be twice it")
+def _ranges(dmin, dmax, h, w):
+    """The two bounds of the depth range, both global or both per-pixel -> (dmin tensor, dmax tensor, pixel stride)."""
     dmin_t, rps = _range_ptr(dmin, h, w)
     dmax_t, rps2 = _range_ptr(dmax, h, w)
     if rps != rps2:
         raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    return dmin_t, dmax_t, rps
+
+
+def _query_strides(query, h, w):
+    """query [nq, h', w'] with (h', w') == (h, w) or exactly 2x (read nearest-downsampled) -> (nq, plane, row, column stride)."""
+    _t(query, "query")
+    nq, qh, qw = query.shape
+    if (qh, qw) == (h, w):
+        return nq, qh * qw, qw, 1
+    if (qh // 2, qw // 2) == (h, w):
+        return nq, qh * qw, 2 * qw, 2   # F.interpolate(nearest) to half size picks the even samples
+    raise ValueError("query resolution must equal the volume's or be twice it")
+
+
+def _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w):
+    """The look-up block of the GetCost family as its entries take it (cur_vol, cds, cps, Dcur, reg_vol, rds, rps, Dreg, dmin, dmax,
+    range_ps) -> (args, Dcur, Dreg, keep); ``keep`` holds the tensors behind the pointers in ``args`` (contiguous copies among
+    them), for the caller to keep alive until it has launched."""
+    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
+    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
+    dmin_t, dmax_t, gps = _ranges(dmin, dmax, h, w)
+    return (_p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t), gps), Dc, Dr, (cur_vol, reg_vol, dmin_t, dmax_t)
+
+
+def _pair_outputs(srcs_a, srcs_b, what, mismatch, cout, out_dims=lambda D, h, w: (D, h, w)):
+    """The two calls of a 3-D pair launch: source lists of [c,D,h,w] tensors (``what`` in their errors) with the same shapes (else
+    ValueError(mismatch)) -> (out_a, out_b, cin, D, h, w): outputs [cout, *out_dims(D, h, w)], cin = the channels of a list."""
+    for s in list(srcs_a) + list(srcs_b):
+        _t(s, what)
+    if [tuple(s.shape) for s in srcs_a] != [tuple(s.shape) for s in srcs_b]:
+        raise ValueError(mismatch)
+    _, D, h, w = srcs_a[0].shape
+    out_a = torch.empty(cout, *out_dims(D, h, w), device=srcs_a[0].device, dtype=torch.float32)
+    return out_a, torch.empty_like(out_a), sum(s.shape[0] for s in srcs_a), D, h, w
+
+
+def vol_lookup1d(vol, query, dmin, dmax, h, w):
+    """query [nq, h', w'] with (h', w') == (h, w) or exactly 2x (read nearest-downsampled)."""
+    vol, vds, vps, Dp = _vol_strides(vol, h, w)
+    nq, qds, qys, qxs = _query_strides(query, h, w)
+    dmin_t, dmax_t, rps = _ranges(dmin, dmax, h, w)
     out = torch.empty(nq, h, w, device=query.device, dtype=torch.float32)
-    check(_lib.lib().effi_vol_lookup1d_f32(_p(vol), vds, vps, Dp, _p(query), qh * qw, qys, qxs, nq, _p(dmin_t),
+    check(_lib.lib().effi_vol_lookup1d_f32(_p(vol), vds, vps, Dp, _p(query), qds, qys, qxs, nq, _p(dmin_t),
                                             _p(dmax_t), rps, h, w, _p(out), _stream()), "effi_vol_lookup1d_f32")
     return out
 
@@ -1807,34 +1839,20 @@ def vol_lookup1d_pair(vol_a, vol_b, query, dmin, dmax, h, w):
     vol_b, vds_b, vps_b, Dp_b = _vol_strides(vol_b, h, w)
     if (vds, vps, Dp) != (vds_b, vps_b, Dp_b):
         raise ValueError("vol_lookup1d_pair: the two volumes must share shape and layout")
-    _t(query, "query")
-    nq, qh, qw = query.shape
-    if (qh, qw) == (h, w):
-        qys, qxs = qw, 1
-    elif (qh // 2, qw // 2) == (h, w):
-        qys, qxs = 2 * qw, 2
-    else:
-        raise ValueError("query resolution must equal the volume's or be twice it")
-    dmin_t, rps = _range_ptr(dmin, h, w)
-    dmax_t, rps2 = _range_ptr(dmax, h, w)
-    if rps != rps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    nq, qds, qys, qxs = _query_strides(query, h, w)
+    dmin_t, dmax_t, rps = _ranges(dmin, dmax, h, w)
     out_a = torch.empty(nq, h, w, device=query.device, dtype=torch.float32)
     out_b = torch.empty_like(out_a)
-    check(_lib.lib().effi_vol_lookup1d_pair_f32(_p(vol_a), _p(vol_b), vds, vps, Dp, _p(query), qh * qw, qys, qxs, nq, _p(dmin_t),
+    check(_lib.lib().effi_vol_lookup1d_pair_f32(_p(vol_a), _p(vol_b), vds, vps, Dp, _p(query), qds, qys, qxs, nq, _p(dmin_t),
                                                  _p(dmax_t), rps, h, w, _p(out_a), _p(out_b), _stream()), "effi_vol_lookup1d_pair_f32")
     return out_a, out_b
 
 
 def conv3d_k3_pair(x_a, weight_a, bias_a, x_b, weight_b, bias_b, cout, sxy=1, relu=True):
     """``conv3d_k3`` of two single-source convolutions of the same shape (cout 8, stride (1,sxy,sxy)) in one launch."""
-    _t(x_a, "conv3d input"), _t(x_b, "conv3d input")
-    if x_a.shape != x_b.shape:
-        raise ValueError("conv3d_k3_pair: the two inputs must share their shape")
-    cin, D, h, w = x_a.shape
-    ho, wo = (h - 1) // sxy + 1, (w - 1) // sxy + 1
-    out_a = torch.empty(cout, D, ho, wo, device=x_a.device, dtype=torch.float32)
-    out_b = torch.empty_like(out_a)
+    out_a, out_b, cin, D, h, w = _pair_outputs([x_a], [x_b], "conv3d input", "conv3d_k3_pair: the two inputs must share their shape", cout,
+                                               lambda D, h, w: (D, (h - 1) // sxy + 1, (w - 1) // sxy + 1))
+    ho, wo = out_a.shape[2:]
     work = lambda: {"flops": 2.0 * 2 * 27 * cin * cout * D * ho * wo, "bytes": 2 * 4.0 * (cin * D * h * w + cout * D * ho * wo)}
     check(_call(f"conv3d_pair_c8_s1{sxy}", work, _lib.lib().effi_conv3d_k3_pair_f32, _p(x_a), _p(weight_a), _p(bias_a), _p(out_a),
                 _p(x_b), _p(weight_b), _p(bias_b), _p(out_b), cin, cout, D, h, w, sxy, int(relu), _stream()), "effi_conv3d_k3_pair_f32")
@@ -1866,14 +1884,8 @@ def csp_gen_roll_pair(x, prior_a, w0_a, b0_a, wc_a, bc_a, w1_a, b1_a, prior_b, w
 
 def conv3d_k3s1_roll_pair(srcs_a, wpack_a, bias_a, srcs_b, wpack_b, bias_b, cout, relu=True):
     """``conv3d_k3s1_roll`` of two convolutions with the same source split and shape in one launch."""
-    for s in list(srcs_a) + list(srcs_b):
-        _t(s, "conv3d input")
-    if [tuple(s.shape) for s in srcs_a] != [tuple(s.shape) for s in srcs_b]:
-        raise ValueError("conv3d_k3s1_roll_pair: the two source lists must share their shapes")
-    _, D, h, w = srcs_a[0].shape
-    cin = sum(s.shape[0] for s in srcs_a)
-    out_a = torch.empty(cout, D, h, w, device=srcs_a[0].device, dtype=torch.float32)
-    out_b = torch.empty_like(out_a)
+    out_a, out_b, cin, D, h, w = _pair_outputs(srcs_a, srcs_b, "conv3d input",
+                                               "conv3d_k3s1_roll_pair: the two source lists must share their shapes", cout)
     work = lambda: {"flops": 2 * 2.0 * 27 * cin * cout * D * h * w, "bytes": 2 * 4.0 * (cin + cout) * D * h * w}
     check(_call(f"conv3d_roll_pair_oct{cin // 8}", work, _x3("effi_conv3d_k3s1_roll_bf16x3_pair_f32"), _ptr_array(srcs_a),
                 _p(wpack_a), _p(bias_a), _p(out_a), _ptr_array(srcs_b), _p(wpack_b), _p(bias_b), _p(out_b),
@@ -1884,12 +1896,8 @@ def conv3d_k3s1_roll_pair(srcs_a, wpack_a, bias_a, srcs_b, wpack_b, bias_b, cout
 
 def deconv3d_k3_pair(x_a, weight_a, bias_a, x_b, weight_b, bias_b, cout, sz=1, relu=True):
     """``deconv3d_k3`` (stride (1,2,2), cout 1) of two inputs of the same shape in one launch."""
-    _t(x_a, "deconv3d input"), _t(x_b, "deconv3d input")
-    if x_a.shape != x_b.shape:
-        raise ValueError("deconv3d_k3_pair: the two inputs must share their shape")
-    cin, D, h, w = x_a.shape
-    out_a = torch.empty(cout, sz * D, 2 * h, 2 * w, device=x_a.device, dtype=torch.float32)
-    out_b = torch.empty_like(out_a)
+    out_a, out_b, cin, D, h, w = _pair_outputs([x_a], [x_b], "deconv3d input", "deconv3d_k3_pair: the two inputs must share their shape", cout,
+                                               lambda D, h, w: (sz * D, 2 * h, 2 * w))
     work = lambda: {"flops": 2 * 2.0 * 27 * cin * cout * D * h * w, "bytes": 2 * 4.0 * (cin * D * h * w + cout * sz * D * 4 * h * w)}
     check(_call("deconv3d_pair_c1_s1", work, _lib.lib().effi_deconv3d_k3_pair_f32, _p(x_a), _p(weight_a), _p(bias_a), _p(out_a),
                 _p(x_b), _p(weight_b), _p(bias_b), _p(out_b), cin, cout, D, h, w, sz, int(relu), _stream()), "effi_deconv3d_k3_pair_f32")
@@ -1898,18 +1906,12 @@ def deconv3d_k3_pair(x_a, weight_a, bias_a, x_b, weight_b, bias_b, cout, sz=1, r
 
 def getcost(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, nq, h, w, input_is_depth=False, out=None):
     _t(x, "inv_depth"), _t(interval, "interval")
-    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
-    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, gps2 = _range_ptr(dmax, h, w)
-    if gps != gps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    look, _, _, _keep = _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w)
     if out is None:
         out = torch.empty(2 * nq, h, w, device=x.device, dtype=torch.float32)
     n_range = 0 if disp_range is None else disp_range.numel()
-    check(_lib.lib().effi_getcost_f32(_p(x), _p(disp_range), n_range, int(input_is_depth), _p(interval),
-                                       _p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t), gps,
-                                       nq, h, w, _p(out), _stream()), "effi_getcost_f32")
+    check(_lib.lib().effi_getcost_f32(_p(x), _p(disp_range), n_range, int(input_is_depth), _p(interval), *look, nq, h, w, _p(out), _stream()),
+          "effi_getcost_f32")
     return out
 
 
@@ -1917,19 +1919,14 @@ def getcost_conv1x1(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, nq, h
                     input_is_depth=False, out=None):
     """``getcost`` + 1x1 convolution (weight [2*nq, cout], bias [cout]) + ReLU in one kernel -> [cout,h,w]."""
     _t(x, "inv_depth"), _t(interval, "interval"), _t(weight, "weight"), _t(bias, "bias")
-    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
-    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, gps2 = _range_ptr(dmax, h, w)
-    if gps != gps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    look, Dc, Dr, _keep = _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w)
     if out is None:
         out = torch.empty(cout, h, w, device=x.device, dtype=torch.float32)
     n_range = 0 if disp_range is None else disp_range.numel()
     work = lambda: {"flops": 2.0 * h * w * 2 * nq * cout, "bytes": 4.0 * h * w * (cout + 1 + Dc + Dr)}
     check(_call("getcost_conv1x1", work, _lib.lib().effi_getcost_conv1x1_f32, _p(x), _p(disp_range), n_range,
-                int(input_is_depth), _p(interval), _p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t),
-                gps, nq, h, w, _p(weight), _p(bias), cout, int(relu), _p(out), _stream()), "effi_getcost_conv1x1_f32")
+                int(input_is_depth), _p(interval), *look, nq, h, w, _p(weight), _p(bias), cout, int(relu), _p(out), _stream()),
+          "effi_getcost_conv1x1_f32")
     return out
 
 
@@ -1940,12 +1937,7 @@ def encoder_inputs(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, nq, h,
     _t(x, "inv_depth"), _t(interval, "interval"), _t(disp_range, "disp_range")
     for t_ in (weight_c1, bias_c1, weight_d1, bias_d1):
         _t(t_, "encoder weights")
-    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
-    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, gps2 = _range_ptr(dmax, h, w)
-    if gps != gps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    look, Dc, Dr, _keep = _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w)
     if out_c1 is None:
         out_c1 = torch.empty(cout, h, w, device=x.device, dtype=torch.float32)
     if out_d1 is None:
@@ -1954,8 +1946,7 @@ def encoder_inputs(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, nq, h,
     # split / bf16 precision: the 7x7 half on the matrix cores (EFFI_C1K7_MFMA=0: the exact-fp32 vector form, as "fp32" precision uses)
     x3 = uses_split() and _PY_OPTS["c1k7_mfma"] != 0
     fn = _lib.lib().effi_encoder_inputs_bf16x3_f32 if x3 else _lib.lib().effi_encoder_inputs_f32
-    check(_call("encoder_inputs", work, fn, _p(x), _p(disp_range), disp_range.numel(),
-                _p(interval), _p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t), gps, nq, h, w,
+    check(_call("encoder_inputs", work, fn, _p(x), _p(disp_range), disp_range.numel(), _p(interval), *look, nq, h, w,
                 _p(weight_c1), _p(bias_c1), _p(weight_d1), _p(bias_d1), cout, _p(out_c1), _p(out_d1), _stream()),
           "effi_encoder_inputs_bf16x3_f32" if x3 else "effi_encoder_inputs_f32")
     return out_c1, out_d1
@@ -2207,19 +2198,13 @@ def encoder_inputs_sr(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, nq,
     for t_ in (weight_c1, bias_c1, weight_d1, bias_d1):
         _t(t_, "encoder weights")
     _sr(out_c1, "out_c1"), _sr(out_d1, "out_d1")
-    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
-    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, gps2 = _range_ptr(dmax, h, w)
-    if gps != gps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    look, Dc, Dr, _keep = _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w)
     if (out_c1.channels, out_c1.h, out_c1.w) != (cout, h, w) or (out_d1.channels, out_d1.h, out_d1.w) != (cout, h, w):
         raise ValueError("encoder_inputs_sr: output maps must be [cout,h,w]")
     work = lambda: {"flops": 2.0 * h * w * (2 * nq + 49) * cout, "bytes": 4.0 * h * w * (2 * cout + 1 + Dc + Dr)}
     check(_call("encoder_inputs", work, _lib.lib().effi_encoder_inputs_bf16x3_sr, _p(x), _p(disp_range), disp_range.numel(),
-                _p(interval), _p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t), gps, nq, h, w,
-                _p(weight_c1), _p(bias_c1), _p(weight_d1), _p(bias_d1), cout, _p(out_c1.t), _p(out_d1.t), out_c1.hp, out_c1.wp,
-                _stream()), "effi_encoder_inputs_bf16x3_sr")
+                _p(interval), *look, nq, h, w, _p(weight_c1), _p(bias_c1), _p(weight_d1), _p(bias_d1), cout, _p(out_c1.t), _p(out_d1.t),
+                out_c1.hp, out_c1.wp, _stream()), "effi_encoder_inputs_bf16x3_sr")
     return out_c1, out_d1
 
 
@@ -2231,17 +2216,12 @@ def encoder_pair_gen_sr(x, disp_range, interval, cur_vol, reg_vol, dmin, dmax, n
     for t_ in (weight_c1, bias_c1, weight_d1, bias_d1):
         _t(t_, "encoder weights")
     g = _sr_srcs([out_c2, out_d2])
-    cur_vol, cds, cps, Dc = _vol_strides(cur_vol, h, w)
-    reg_vol, rds, rps, Dr = _vol_strides(reg_vol, h, w)
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, gps2 = _range_ptr(dmax, h, w)
-    if gps != gps2:
-        raise ValueError("depth_min / depth_max must both be global or both per-pixel")
+    look, Dc, Dr, _keep = _lookup_args(cur_vol, reg_vol, dmin, dmax, h, w)
     if (g.channels, g.h, g.w) != (cout, h, w) or tuple(x.shape[-2:]) != (h, w):
         raise ValueError("encoder_pair_gen_sr: output maps must be [cout,h,w]")
     work = lambda: {"flops": 2.0 * h * w * ((2 * nq + 49) * hd + 2 * 9 * hd * cout), "bytes": 4.0 * h * w * (2 * cout + 1 + Dc + Dr)}
     check(_call(f"encgen_pair_nt{(cout + 15) // 16}", work, _x3("effi_encoder_pair_gen_bf16x3_sr"), _p(x), _p(disp_range),
-                disp_range.numel(), _p(interval), _p(cur_vol), cds, cps, Dc, _p(reg_vol), rds, rps, Dr, _p(dmin_t), _p(dmax_t), gps, nq,
+                disp_range.numel(), _p(interval), *look, nq,
                 h, w, _p(weight_c1), _p(bias_c1), _p(weight_d1), _p(bias_d1), hd, _p(wpack_c2), _p(bias_c2), _p(out_c2.t), _p(wpack_d2),
                 _p(bias_d2), _p(out_d2.t), cout, g.hp, g.wp, act, _stream()), "effi_encoder_pair_gen_bf16x3_sr")
     return out_c2, out_d2
@@ -2825,18 +2805,11 @@ def inv_to_depth_ranged_bwd(g, inv, depth_values, out=None):
 
 def vol_lookup1d_bwd(gout, Dp, query, dmin, dmax, h, w):
     """Gradient of ``vol_lookup1d`` w.r.t. a planar [Dp,h,w] volume: gout [nq,h,w] -> [Dp,h,w]."""
-    _t(gout, "grad"), _t(query, "query")
-    nq, qh, qw = query.shape
-    if (qh, qw) == (h, w):
-        qys, qxs = qw, 1
-    elif (qh // 2, qw // 2) == (h, w):
-        qys, qxs = 2 * qw, 2
-    else:
-        raise ValueError("query resolution must equal the volume's or be twice it")
-    dmin_t, rps = _range_ptr(dmin, h, w)
-    dmax_t, _ = _range_ptr(dmax, h, w)
+    _t(gout, "grad")
+    nq, qds, qys, qxs = _query_strides(query, h, w)
+    dmin_t, dmax_t, rps = _ranges(dmin, dmax, h, w)
     gvol = torch.zeros(Dp, h, w, device=gout.device, dtype=torch.float32)
-    check(_lib.lib().effi_vol_lookup1d_bwd_f32(_p(gvol), h * w, 1, Dp, _p(query), qh * qw, qys, qxs, nq, _p(dmin_t), _p(dmax_t), rps, h, w,
+    check(_lib.lib().effi_vol_lookup1d_bwd_f32(_p(gvol), h * w, 1, Dp, _p(query), qds, qys, qxs, nq, _p(dmin_t), _p(dmax_t), rps, h, w,
                                                _p(gout), _stream()), "effi_vol_lookup1d_bwd_f32")
     return gvol
 
@@ -2844,8 +2817,7 @@ def vol_lookup1d_bwd(gout, Dp, query, dmin, dmax, h, w):
 def getcost_bwd(gcost, x, disp_range, interval, Dcur, Dreg, dmin, dmax, nq, h, w, input_is_depth=False):
     """Gradient of ``getcost`` w.r.t. planar cur [Dcur,h,w] and reg [Dreg,h,w] volumes: gcost [2nq,h,w] -> (gcur, greg)."""
     _t(gcost, "grad"), _t(x, "inv_depth"), _t(interval, "interval")
-    dmin_t, gps = _range_ptr(dmin, h, w)
-    dmax_t, _ = _range_ptr(dmax, h, w)
+    dmin_t, dmax_t, gps = _ranges(dmin, dmax, h, w)
     gcur = torch.zeros(Dcur, h, w, device=x.device, dtype=torch.float32)
     greg = torch.zeros(Dreg, h, w, device=x.device, dtype=torch.float32)
     n_range = 0 if disp_range is None else disp_range.numel()

@@ -269,6 +269,16 @@ VOL_BATCH_CASES = [
     ("c3_planes", "c3_planes", 13, "fp32", 512, (1, 32, 4, 8, 0)),     # 8 -> 1 transposed: input 5 x 6 x 10: 1 * 1 * 512 = 512
     ("deconv_k3", "deconv_k3", 12, "fp32", 256, (1, 32, 4, 8, 0)),     # 8 -> 8 stride 2: input 2 x 5 x 6: 1 tile * 2 planes * 256 = 512
 ]
+# Planes per thread of the general vector-ALU 3-D kernel (effi_pick_c3_zpt): 4 (2 at stride (2,2,2)) from 384 workgroups of that form,
+# 1 below.  Host rows only, at both sides of the threshold on ONE tile of the 32 x 8 output map (7 x 29): (row, s2, N-tiles of 8 output
+# channels, output planes, calls / samples, planes per thread, the record of csrc/vol_host_check.cpp that launches it).
+C3_ZPT_FORM_CASES = [
+    ("c3_zpt", False, 1, 1532, 1, 1, "s111 1 tile D1532: 383"), ("c3_zpt", False, 1, 1533, 1, 4, "s111 1 tile D1533: 384"),
+    ("c3_zpt s2", True, 1, 766, 1, 1, "s222 1 tile D1532: 766 output planes, 383"), ("c3_zpt s2", True, 1, 767, 1, 2, "s222 1 tile D1533: 384"),
+    ("c3_zpt", False, 1, 508, 3, 1, "s111 1 tile D508 n_smp3: 127 x 3 = 381"), ("c3_zpt", False, 1, 512, 3, 4, "s111 1 tile D512 n_smp3: 384"),
+    ("c3_zpt", False, 1, 764, 2, 1, "pair cin4 s1 1 tile D764: 191 x 2 = 382"), ("c3_zpt", False, 1, 765, 2, 4, "pair cin4 s1 1 tile D765: 384"),
+    ("c3_zpt", False, 2, 764, 1, 1, "two tiles of 8 output channels: 382"), ("c3_zpt", False, 2, 765, 1, 4, "two tiles of 8 output channels: 384"),
+]
 # 5x5 stride 2, both arithmetics (fp32: 512 tiles of 8 output rows; split: 400): (input h, w), images, form.  17 x 8192 -> output 9 x 4096:
 # 256 * 2 = 512 tiles; two images of 17 x 4096 -> 128 * 2 * 2 = 512 (one alone: 256, one row per wave -- the form it is compared with)
 K5S2_FORM_CASES = [((17, 8192), 1, MR2), ((17, 4096), 2, MR2)]
@@ -370,6 +380,9 @@ def form_cases():
         out.append(FormCase(row, vol_query(launcher, i, n), {}, form, f"{n} samples of VOL case {i}: the rule"))
         small = {MR2: MR1, MR4: MR1}.get(form, (1, 32, 4, 4, 0))
         out.append(FormCase(row, vol_query(launcher, i, 1), {}, small, f"VOL case {i} in test_conv3d_every_branch_bounded: the rule"))
+    for row, s2, nt, planes, count, zpt, how in C3_ZPT_FORM_CASES:
+        out.append(FormCase(row, dict(launcher="c3_zpt", h=7, w=29, nt=nt, planes=planes, count=count, s2=s2), {}, (1, 32, 4, zpt, 0),
+                            f"vol_host_check, {how}: the rule"))
     (kc, kco), (h, w) = K5S2_FORM_CHANNELS, (21, 28)
     for hw, n, form in K5S2_FORM_CASES + [((21, 28), 1, MR1)]:
         q = dict(h=(hw[0] - 1) // 2 + 1, w=(hw[1] - 1) // 2 + 1, nt=(kco + 15) // 16, count=n)
@@ -435,6 +448,8 @@ def workload_queries():
                     yield "deconv_k3", dict(launcher="deconv_k3", h=h, w=w, planes=D, cout=cout, count=n), D
                 yield "c3_planes", dict(launcher="c3_planes", h=h, w=w, planes=D, count=n), D
                 for nt in (1, 2):
+                    yield "c3_zpt", dict(launcher="c3_zpt", h=h, w=w, nt=nt, planes=D, count=n), D
+                    yield "c3_zpt s2", dict(launcher="c3_zpt", h=h, w=w, nt=nt, planes=D, count=n, s2=True), D
                     yield "planes3d", dict(launcher="planes3d", h=h, w=w, nt=nt, planes=D, count=n), D
                     yield "planes3d s2", dict(launcher="planes3d", h=h, w=w, nt=nt, planes=D, count=n, s2=True), D
                     yield "s2_x3 3-D", dict(launcher="s2_x3", h=h, w=w, nt=nt, planes=D, count=n), D
