@@ -39,6 +39,9 @@ SIGNATURES = {
     "effi_fusion_compact_scan_tile": [],
     "effi_fusion_compact_count_u8": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "effi_fusion_compact_scatter_f32": [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp],
+    # Gipuma / fusibile fusion (csrc/gipuma.hip; misc/gipuma.py:160-236)
+    "effi_fusion_gipuma_prob_f32": [_vp, _vp, _l, _f, _vp, _vp],
+    "effi_fusion_gipuma_view_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # DTU evaluation of a fused cloud (csrc/dtu_eval.hip)
     "effi_dtu_cell_keys_f32": [_vp, _l, _d, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "effi_dtu_reduce_blocks": [_l],

@@ -1293,6 +1293,71 @@ def fusion_compact(mask, points, images, layout="hwc", pairs=None):
     return xyz, rgb, offsets
 
 
+# ---- Gipuma / fusibile fusion (csrc/gipuma.hip; the driver is effi_mvs_plus_amd/gipuma.py) ----
+GIPUMA_MAX_SOURCES = 64
+
+
+def gipuma_check_sources(n_views, ref, sources):
+    """Host only (no GPU, no library): what ``fusion_gipuma_view`` refuses before any launch -> the source ids as a list of ints."""
+    ref, srcs = int(ref), [int(s) for s in sources]
+    if not 0 <= ref < n_views:
+        raise ValueError(f"gipuma: reference view {ref} outside [0, {n_views})")
+    if not 1 <= len(srcs) <= GIPUMA_MAX_SOURCES:
+        raise ValueError(f"gipuma: reference view {ref} has {len(srcs)} sources; 1 .. {GIPUMA_MAX_SOURCES} are supported")
+    for s in srcs:
+        if not 0 <= s < n_views:
+            raise ValueError(f"gipuma: source view {s} of reference view {ref} outside [0, {n_views})")
+        if s == ref:
+            raise ValueError(f"gipuma: reference view {ref} is listed as its own source")
+    return srcs
+
+
+def fusion_gipuma_prob(depths, confidences, prob_threshold):
+    """probability_filter (misc/gipuma.py:177,188) on the device: depths where ``confidences > prob_threshold``, else 0; same shapes."""
+    _t(depths, "depths"), _t(confidences, "confidences")
+    if depths.shape != confidences.shape or depths.numel() < 1:
+        raise ValueError(f"fusion_gipuma_prob: depths {tuple(depths.shape)} and confidences {tuple(confidences.shape)} must have one size")
+    out = torch.empty_like(depths)
+    n = depths.numel()
+    work = lambda: {"flops": 0.0, "bytes": 12.0 * n}
+    check(_call("fusion_gipuma_prob", work, _lib.lib().effi_fusion_gipuma_prob_f32, _p(depths), _p(confidences), n, float(prob_threshold),
+                _p(out), _stream()), "effi_fusion_gipuma_prob_f32")
+    return out
+
+
+def fusion_gipuma_view(depths, cams, images, ref, sources, used, disp_threshold=0.25, num_consistent=4, depth_min=0.001,
+                       depth_max=100000.0):
+    """ONE reference view of the Gipuma / fusibile fusion (misc/gipuma.py:192-213 without the external program).
+    depths [n_views,h,w] (probability-filtered); cams [n_views,2,4,4]; images [n_views,h,w,3] fp32 in [0,1] or None; ``sources``: the
+    ordered source ids of ``ref`` (1 .. 64, none equal to ``ref``: ValueError before any launch); ``used`` [n_views,h,w] uint8, read
+    and UPDATED in place -- the calls of a scan must follow each other in reference order on one stream -> dict(points [3,h,w] and
+    colour [h,w,3] or None: valid where mask is set, mask [h,w] uint8, count [h,w] uint8 = consistent sources per pixel)."""
+    _t(depths, "depths"), _t(cams, "cams")
+    if depths.dim() != 3 or tuple(cams.shape) != (depths.shape[0], 2, 4, 4):
+        raise ValueError(f"fusion_gipuma_view: depths [n_views,h,w] and cams [n_views,2,4,4] expected, got {tuple(depths.shape)} / {tuple(cams.shape)}")
+    n_views, h, w = depths.shape
+    if images is not None:
+        _t(images, "images")
+        if tuple(images.shape) != (n_views, h, w, 3):
+            raise ValueError(f"fusion_gipuma_view: images [n_views,h,w,3] = {(n_views, h, w, 3)} expected, got {tuple(images.shape)}")
+    if not isinstance(used, torch.Tensor) or used.dtype != torch.uint8 or used.device != depths.device or not used.is_contiguous() \
+            or tuple(used.shape) != (n_views, h, w):
+        raise TypeError("fusion_gipuma_view: used must be a contiguous uint8 tensor [n_views,h,w] on the depths' device")
+    srcs = gipuma_check_sources(n_views, ref, sources)
+    dev = depths.device
+    src_host = torch.tensor(srcs, dtype=torch.int32)
+    src_dev = src_host.to(dev)
+    z = lambda *sh, dt=torch.float32: torch.empty(*sh, device=dev, dtype=dt)
+    out = {"points": z(3, h, w), "colour": None if images is None else z(h, w, 3), "mask": z(h, w, dt=torch.uint8),
+           "count": z(h, w, dt=torch.uint8)}
+    scratch = z(32 * (len(srcs) + 1))
+    work = lambda: {"flops": 0.0, "bytes": 4.0 * h * w * (1 + len(srcs)) + 3.0 * h * w}
+    check(_call("fusion_gipuma_view", work, _lib.lib().effi_fusion_gipuma_view_f32, _p(depths), _p(cams), _p(images), n_views, int(ref),
+                _p(src_host), _p(src_dev), len(srcs), h, w, float(disp_threshold), int(num_consistent), float(depth_min), float(depth_max),
+                _p(scratch), C.c_void_p(used.data_ptr()), *map(_p, out.values()), _stream()), "effi_fusion_gipuma_view_f32")
+    return out
+
+
 # ---- DTU evaluation of a fused cloud (csrc/dtu_eval.hip; the driver is effi_mvs_plus_amd/dtu_eval.py) ----
 def _dtu_points(x, name, cols=3):
     _t(x, name)

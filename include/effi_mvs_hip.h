@@ -942,6 +942,31 @@ int effi_fusion_compact_scatter_f32(const unsigned char* mask, const float* poin
                                     long pix_stride, long ch_stride, int n_ref, int h, int w, const int* block_base, float* xyz,
                                     unsigned char* rgb, effi_stream_t stream);
 
+/* ---- Gipuma / fusibile depth-map fusion (misc/gipuma.py:160-236: probability_filter, then the external `fusibile` executable with
+ * normal_thresh = 360, i.e. without its normal test), csrc/gipuma.hip.  PARITY WITH THE EXTERNAL BINARY UNPINNED: neither its source
+ * nor its output is available; the method is the consistency fusion of Galliani et al. 2015 as DESIGN.md section 7.10 specifies it.
+ * ORDER DEPENDENT: the reference views of a scan are fused one call after the other, and a fused point marks the source pixels that
+ * supported it in `used`, so that later reference views do not emit the same surface again.
+ * effi_fusion_gipuma_prob_f32: out[i] = conf[i] > prob_threshold ? depth[i] : 0 over n elements (gipuma.py:177,188).
+ * effi_fusion_gipuma_view_f32: ONE reference view `ref` of a scan.  depths [n_views][h][w] (after the probability filter), cams
+ * [n_views][2][4][4] (extrinsic; intrinsic in the top-left 3x3), images [n_views][h][w][3] fp32 or NULL, sources [n_src] view ids in
+ * device memory and sources_host the same list in HOST memory, checked before anything is launched: 1 <= n_src <= 64, every id in
+ * [0, n_views) and != ref, ref in [0, n_views), n_views*h*w < 2^31, thresholds not NaN (else EFFI_ERR_BADARG).  Per pixel p = (x, y),
+ * with ok(d) := depth_min <= d <= depth_max: nothing is emitted unless ok(D_ref[p]) and used[ref][p] == 0; X = R^T (d K^-1 (x, y, 1) - t);
+ * a source s is CONSISTENT iff z = (R_s X + t_s)_z > 0, q = floor((K_s Y)_xy / (K_s Y)_z + 0.5) lies inside the image, ok(D_s[q]) and
+ * |f b / z - f b / D_s[q]| < disp_threshold (f = K_ref[0][0], b = |C_ref - C_s|).  With n consistent sources the pixel is fused iff
+ * n >= num_consistent: point = (X + sum X_s) / (n + 1) with X_s the back-projection of the integer pixel q at D_s[q], colour likewise,
+ * sums in source order in fp32; out_mask[p] = 1, used[ref][p] = 1 and used[s][q] = 1 for every consistent (s, q) (plain byte stores of
+ * the value 1: deterministic).  out_points [3][h][w] and out_colour [h][w][3] (NULL iff images is NULL) are written for fused pixels
+ * only; out_mask [h][w] and out_count [h][w] (n, bytes) for every pixel.  used [n_views][h][w] bytes is read and written.
+ * mats_scratch: 32 * (n_src + 1) floats. */
+int effi_fusion_gipuma_prob_f32(const float* depth, const float* conf, long n, float prob_threshold, float* out, effi_stream_t stream);
+int effi_fusion_gipuma_view_f32(const float* depths, const float* cams, const float* images, int n_views, int ref,
+                                const int* sources_host, const int* sources, int n_src, int h, int w, float disp_threshold,
+                                int num_consistent, float depth_min, float depth_max, float* mats_scratch, unsigned char* used,
+                                float* out_points, float* out_colour, unsigned char* out_mask, unsigned char* out_count,
+                                effi_stream_t stream);
+
 /* ---- The DTU evaluation of a fused cloud (evaluations/dtu/BaseEvalMain_web.m:57,69-78 -> PointCompareMain.m -> reducePts_haa.m,
  * MaxDistCP.m), csrc/dtu_eval.hip.  MATLAB works in double: every decision is made in fp64 on the fp32 coordinates converted to fp64,
  * and a squared distance is always (dx*dx + dy*dy) + dz*dz, unfused.  Point sets are [n][3] fp32.  The uniform grid of a set is
